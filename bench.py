@@ -1,6 +1,6 @@
 """Benchmark of the DiG pre-training step on MI355X (the driver's contract).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = one full `train_one_epoch` iteration of `pretrain_simmim_moco_ori_vit_small_patch4_32x128` on a synthetic
@@ -15,11 +15,6 @@ import os
 import sys
 import time
 import types
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")        # before HIP initialises: see dig_amd/__init__.py
-# this process also measures the captured (HIP-graph) form of the step beside the eager one (`step_graph` in the line): the graph executor's
-# queue count for it (dig_amd/__init__.py sets it only under DIG_STEP_GRAPH=1); eager launches -- the headline -- do not read it
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "2")
 
 import numpy as np
 import torch
@@ -388,6 +383,27 @@ def cpu_baseline(model_name, budget_s=20.0):
                       f"(`value`; one untimed step at that batch first), {n4} steps at batch 4 (BASELINE configs[0])"}
 
 
+DUMP_SAMPLE = 1 << 20                     # --dump-outputs: elements kept per state buffer larger than this (fixed, seeded positions)
+
+
+def step_outputs(stats, model, opt):
+    """What the timed path hands its caller after its last step, on the host: the meters train_one_epoch returns (float64) and the
+    state that step wrote (fp32) -- online weights, their gradients, momentum weights, both AdamW moments, BatchNorm running
+    statistics.  Buffers above DUMP_SAMPLE elements are sampled at positions drawn from a fixed seed, so the files stay well under
+    64 MB and two runs or two builds compare position for position."""
+    out = {f"stat_{k}": np.asarray(v, dtype=np.float64) for k, v in sorted(stats.items())}
+    bufs = {"online_params": model._flat["online"], "grads": model._flat["grad"], "momentum_params": model._flat["momentum"],
+            "adam_exp_avg": opt.exp_avg, "adam_exp_avg_sq": opt.exp_avg_sq, "bn_stats": model._flat["bn_stats"]}
+    for name, t in bufs.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    return out
+
+
 def _self_launch(n):
     """Re-executes this command under `python -m torch.distributed.run --nnodes=1 --nproc-per-node n` on 127.0.0.1 with a free port.  With
     DIG_SHARE_GPU=1 (test harness: every rank on device 0) the backend defaults to gloo -- RCCL refuses two ranks on one device."""
@@ -429,6 +445,9 @@ def main():
                          "in the same JSON line under `mim_only` / `mim_moco`.")
     ap.add_argument("--no-step-graph", action="store_true", help="skip the extra measurement of the HIP-graph replay of the step")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (train_one_epoch's meters, sampled weights / gradients / "
+                         "optimizer state) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
     if a.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU over RCCL -- the reference's own launch line is
@@ -504,6 +523,7 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = step_outputs(stats, model, opt) if a.dump_outputs and rank == 0 else None      # (outside the timed region)
     # ---- the other BASELINE workload on the same model state: reported beside the headline
     mim_only = None
     if not a.no_mim_only:
@@ -540,7 +560,7 @@ def main():
         graphed = {"ms_per_step": dt2 / a.steps * 1e3, "value": a.steps * B / dt2, "unit": "images/sec",
                    "host_ms_per_step": model._host_launch[0] / max(model._host_launch[1], 1) * 1e3,
                    "replays": model._step_graph.replays, "note": "opt-in (DIG_STEP_GRAPH=1): same launches, bit-identical results, one "
-                   "hipGraphLaunch per step; ROCm's graph executor runs the two-branch graph slower than the two eager streams"}
+                   "hipGraphLaunch per step; captured from one stream, so it runs without the eager step's two-stream overlap"}
         model.step_graph = False
     # ---- one-rank RCCL path (DIG_FORCE_DIST=1 under torch.distributed.run with one rank): the collectives of a step, counted on an extra step
     dist_info = None
@@ -674,6 +694,11 @@ def main():
             "roofline": roof, ("mim_only" if a.workload == "mim_moco" else "mim_moco"): mim_only}
     if not a.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(model_name, a.cpu_budget)
+    if dumped is not None:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
+        line["dump_outputs"] = {"dir": a.dump_outputs, "arrays": len(dumped), "bytes": sum(v.nbytes for v in dumped.values())}
     print(json.dumps(line), flush=True)
 
 

@@ -16,8 +16,6 @@ import sys
 import time
 import types
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 import torch
 

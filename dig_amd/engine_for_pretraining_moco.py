@@ -247,8 +247,15 @@ def train_one_epoch(model: torch.nn.Module, teacher_model, teacher_model_without
             sig, (s_img, s_aug, s_mask) = sg.set_inputs(images, aug_images, bool_vis_masked_pos)
             key = (sig, w_contrast != 0.0, bool(normlize_target), core._per_sample_mask, float(args.loss_weight_pixel), bool(args.only_mim_on_ori_img),
                    bool(getattr(core, "overlap_streams", True)))
-            dev_vals = sg.run(key, lambda: _step_body(model, core, optimizer, loss_scaler, max_norm, args, normlize_target, s_img, s_aug, s_mask,
-                                                      sg.scalars[6:8], sg.scalars[8], w_contrast != 0.0, sg.scalars[0:6])[0])
+            # the captured body runs on the caller's stream alone: a graph forked over two streams is not replayed reliably by the
+            # runtime's graph executor (dig_amd/step_graph.py)
+            overlap = getattr(core, "overlap_streams", True)
+            core.overlap_streams = False
+            try:
+                dev_vals = sg.run(key, lambda: _step_body(model, core, optimizer, loss_scaler, max_norm, args, normlize_target, s_img, s_aug,
+                                                          s_mask, sg.scalars[6:8], sg.scalars[8], w_contrast != 0.0, sg.scalars[0:6])[0])
+            finally:
+                core.overlap_streams = overlap
             optimizer._step += 1
             has_grad_norm = True
         else:

@@ -13,13 +13,13 @@ once and replayed, the same launches cost the host one hipGraphLaunch.  What mak
   dependencies.
 
 Measured on one MI355X (tools/gpu_step_graph_probe.py, ViT-S, B = 128, A/B in one process): eager 25.0 ms per step with 10.3 ms of
-host work to queue it; replayed 26.3 ms with 1.9 ms of host work.  The replay is SLOWER on the GPU: ROCm's graph executor spreads
-the nodes of a forked graph over DEBUG_HIP_FORCE_GRAPH_QUEUES internal queues (4 by default: 35.1 ms; 8: 42.0 ms; 3: 36.9 ms; 2:
-26.3 ms; 1: 28.6 ms) without regard to which capture stream a node came from, so the long data-gradient chain hops between queues
-at every fork and pays a cross-queue barrier each time; stream priorities are lost as well.  A graph captured from ONE stream
-replays exactly as fast as the eager launches (27.77 vs 27.80 ms, 0.34 ms of host work), but one stream costs 2.8 ms per step
-against two (`model.overlap_streams = False` selects that form).  dig_amd/__init__.py therefore sets the queue count to 2, and the captured step is OPT-IN (`DIG_STEP_GRAPH=1` or
-`model.step_graph = True`): it is the mode for a host that cannot keep 10 ms per step free (a busy data-loading process, a slow
+host work to queue it.  A graph captured from two streams replays SLOWER on the GPU: ROCm's graph executor spreads the nodes of a
+forked graph over its internal queues (35.1 ms with the runtime's defaults) without regard to which capture stream a node came from,
+so the long data-gradient chain hops between queues at every fork and pays a cross-queue barrier each time; stream priorities are
+lost as well, and with few hardware queues per process the replay of a forked graph is not reliable.  The step is therefore captured
+from ONE stream (the engine turns `overlap_streams` off around warm-up, capture and replay): that graph replays exactly as fast as
+the eager one-stream launches (27.77 vs 27.80 ms, 0.34 ms of host work), but one stream costs 2.8 ms per step against two, so the
+captured step is OPT-IN (`DIG_STEP_GRAPH=1` or `model.step_graph = True`): it is the mode for a host that cannot keep 10 ms per step free (a busy data-loading process, a slow
 core), not a throughput gain.  bench.py reports both modes (`step_graph` in the JSON line).  Grouping the weight-gradient launches
 into one or two forks per encoder block did not help either mode (eager 25.0 -> 25.5 ms, replay unchanged).
 

@@ -29,8 +29,6 @@ import random
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")          # before HIP initialises: see dig_amd/__init__.py
-
 import numpy as np
 import torch
 
