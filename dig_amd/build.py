@@ -14,7 +14,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # hazard padding and are no faster than two scalar ops on this chip (MI355X_MICROARCH.md: an anti-lever beside MFMAs): 205 -> 44 s_nop in
 # the fused-MLP S-wave loop, and 24.28 -> 24.15 ms per step with it on every file (A/B on one box)
 FLAGS.append("-fno-slp-vectorize")
-EXTRA_FLAGS = {}                                       # per-file extras (none at present)
+# per-file extras.  keyview.hip: the key-view augmentation is defined by float32 arithmetic without contraction (its numpy model and the
+# plain-C++ build follow it bit for bit); under -ffp-contract=fast the backend fuses multiply-adds whatever `#pragma clang fp contract(off)`
+# says, so that file is compiled with contraction off
+EXTRA_FLAGS = {"keyview.hip": ["-ffp-contract=off"]}
 
 
 def sources():
@@ -85,7 +88,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
 # ---- the hot kernels of the pre-training step (the families on top of profiles/*_kernel_stats.csv): none may use scratch memory
 HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, false>", "mlp_chain_kernel<0, true, false>",
                "wgrad_wide_kernel<3, 7>", "attn_block_kernel<true, 2>", "attn_block_kernel<false, 2>", "attn_bwd_kernel<false, 3, false>", "attn_bwd_kernel<false, 3, true>",
-               "gemm_wide_kernel<false, true, 0, 4, 3, 2, 2, false, 64, 2, false>", "gemm_pwide_kernel<4, false, false>")
+               "gemm_wide_kernel<false, true, 0, 4, 3, 2, 2, false, 64, 2, false>", "gemm_pwide_kernel<4, false, false>",
+               # the key-view augmentation of the input path (keyview.hip): the sampler's and the stages' per-thread state stays in registers
+               "keyview_sample_kernel", "keyview_stage_a_kernel", "keyview_stage_b_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

@@ -5,7 +5,7 @@
 //       (dataset/datasets.py:27-42 on the PIL crops of dataset/dataset_image.py:128-160).  Resize on a PIL image is
 //       Pillow's ImagingResample: separable horizontal-then-vertical passes on 8-bit pixels, double-precision bicubic
 //       (a = -0.5) coefficients over a support of 2*max(scale,1), normalised, rounded to 22-bit fixed point, int32
-//       accumulation from 1<<21, clip to [0,255] after >>22 (restated in oracle/input_oracle.py, pinned against Pillow).
+//       accumulation from 1<<21, clip to [0,255] after >>22 (pillow_resize.h; restated in oracle/input_oracle.py, pinned against Pillow).
 //   dig_random_masks : RandomMaskingGenerator (masking_generator.py:12-49) as a device generator: each row is a uniformly
 //       random subset of exactly num_mask patches, chosen as the num_mask smallest Philox4x32-10 keys.
 //
@@ -18,49 +18,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "pillow_resize.h"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-__device__ __forceinline__ double bicubic_filter(double x) {
-#pragma clang fp contract(off)
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// Pillow precompute_coeffs + normalize_coeffs_8bpc for output index xx (same operation order, no FMA contraction)
-__device__ void coeffs_for(int xx, int in_size, int out_size, int ksize, int* __restrict__ kk, int* __restrict__ bounds) {
-#pragma clang fp contract(off)
-  double scale = (double)in_size / (double)out_size;
-  double filterscale = scale;
-  if (filterscale < 1.0) filterscale = 1.0;
-  const double support = 2.0 * filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += bicubic_filter(((double)(x + xmin) - center + 0.5) * ss);
-  for (int x = 0; x < xmax; ++x) {
-    double w = bicubic_filter(((double)(x + xmin) - center + 0.5) * ss);
-    if (ww != 0.0) w /= ww;
-    kk[xx * ksize + x] = w < 0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-  }
-  bounds[2 * xx] = xmin;
-  bounds[2 * xx + 1] = xmax;
-}
-
-__device__ __forceinline__ int clip8(int v) {
-  v >>= PRECISION_BITS;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
+using dig_pillow::coeffs_for;
+using dig_pillow::ksize_for;
+using dig_pillow::philox_first;
 
 __global__ __launch_bounds__(256) void resize_normalize_kernel(const unsigned char* __restrict__ packed,
                                                                const long long* __restrict__ offsets,
@@ -85,52 +49,14 @@ __global__ __launch_bounds__(256) void resize_normalize_kernel(const unsigned ch
   float* o = out + (size_t)img * 3 * plane;
   for (int p = threadIdx.x; p < out_h * out_w; p += blockDim.x) {
     const int yy = p / out_w, xx = p - yy * out_w;
-    const int x0 = pass_h ? bh[2 * xx] : xx, nx = pass_h ? bh[2 * xx + 1] : 1;
-    const int y0 = pass_v ? bv[2 * yy] : yy, ny = pass_v ? bv[2 * yy + 1] : 1;
-    const int* kx = kh + xx * ksh;
-    const int* ky = kv + yy * ksv;
-    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    int r0 = 0, r1 = 0, r2 = 0;
-    for (int y = 0; y < ny; ++y) {
-      const unsigned char* row = src + ((size_t)(y0 + y) * w + x0) * 3;
-      int h0, h1, h2;
-      if (pass_h) {
-        int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
-        for (int x = 0; x < nx; ++x) {
-          const int k = kx[x];
-          s0 += (int)row[3 * x] * k;
-          s1 += (int)row[3 * x + 1] * k;
-          s2 += (int)row[3 * x + 2] * k;
-        }
-        h0 = clip8(s0); h1 = clip8(s1); h2 = clip8(s2);
-      } else {
-        h0 = row[0]; h1 = row[1]; h2 = row[2];
-      }
-      if (pass_v) {
-        const int k = ky[y];
-        a0 += h0 * k; a1 += h1 * k; a2 += h2 * k;
-      } else {
-        r0 = h0; r1 = h1; r2 = h2;
-      }
-    }
-    if (pass_v) { r0 = clip8(a0); r1 = clip8(a1); r2 = clip8(a2); }
+    int r[3];
+    dig_pillow::resize_pixel(src, w, pass_h, pass_v, kh, bh, kv, bv, ksh, ksv, yy, xx, r);
+    const int r0 = r[0], r1 = r[1], r2 = r[2];
     // ToTensor: uint8 / 255 in fp32; Normalize: (x - mean) / std  (IEEE division: this file is built without fast-math)
     o[p] = ((float)r0 / 255.0f - mean) / stdv;
     o[plane + p] = ((float)r1 / 255.0f - mean) / stdv;
     o[2 * plane + p] = ((float)r2 / 255.0f - mean) / stdv;
   }
-}
-
-// ---- Philox4x32-10
-__device__ __forceinline__ unsigned philox_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
 }
 
 // one wave per mask row: the num_mask patches with the smallest (key, index) are set
@@ -149,12 +75,6 @@ __global__ __launch_bounds__(64) void random_masks_kernel(unsigned char* __restr
     }
     mask[(size_t)r * n_patches + p] = rank < num_mask ? 1 : 0;
   }
-}
-
-int ksize_for(int in_size, int out_size) {
-  double fs = (double)in_size / out_size;
-  if (fs < 1.0) fs = 1.0;
-  return (int)std::ceil(2.0 * fs) * 2 + 1;
 }
 
 }  // namespace

@@ -9,6 +9,9 @@ per view produces the normalised fp32 batch bit-exactly as Pillow + torchvision 
 
     tf = GpuBatchTransform(args)                       # args.input_h/input_w/window_size/mask_ratio/num_view as in the reference
     images, aug_images, masks = tf(crops, aug_crops)   # lists of HxWx3 uint8 arrays -> the `batch` triple of train_one_epoch
+
+With `key_view_aug="seqclr"` and no `aug_crops`, the second view is the reference's augmented key view (seqCLR ops + ColorJitter +
+RandomGrayscale), drawn and applied on the device from the first view's upload (dig_amd/augment.py).
 """
 import ctypes
 
@@ -16,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .augment import KeyViewAugment, PackedCrops, pack_crops
 
 
 class RandomMaskingGenerator:
@@ -47,42 +51,37 @@ class RandomMaskingGenerator:
 
 
 def resize_normalize(crops, out_h=32, out_w=128, mean=0.5, std=0.5, device="cuda"):
-    """List of HxWx3 uint8 numpy arrays -> fp32 [n, 3, out_h, out_w] on `device`:
+    """List of HxWx3 uint8 numpy arrays (or a PackedCrops upload of them) -> fp32 [n, 3, out_h, out_w] on `device`:
     Normalize(mean, std)(ToTensor(Resize((out_h, out_w), interpolation=BICUBIC)(PIL crop)))  (datasets.py:31-37)."""
-    n = len(crops)
-    hs = np.array([c.shape[0] for c in crops], dtype=np.int32)
-    ws = np.array([c.shape[1] for c in crops], dtype=np.int32)
-    sizes = hs.astype(np.int64) * ws.astype(np.int64) * 3
-    offs = np.zeros(n, dtype=np.int64)
-    np.cumsum(sizes[:-1], out=offs[1:])
-    dev = torch.device(device)
-    pin = (lambda t: t.pin_memory()) if dev.type == "cuda" else (lambda t: t)       # (pinned staging only where there is a device to copy to)
-    packed = pin(torch.empty(int(sizes.sum()), dtype=torch.uint8))
-    flat = packed.numpy()
-    for c, o, s in zip(crops, offs, sizes):
-        if c.dtype != np.uint8 or c.ndim != 3 or c.shape[2] != 3:
-            raise ValueError("crops must be HxWx3 uint8 (the RGB image PIL decodes)")
-        flat[o:o + s] = np.ascontiguousarray(c).reshape(-1)
-    d_packed = packed.to(dev, non_blocking=True)
-    d_meta = pin(torch.from_numpy(np.concatenate([offs, hs.astype(np.int64), ws.astype(np.int64)]))).to(dev, non_blocking=True)
-    d_off, d_h, d_w = d_meta[:n], d_meta[n:2 * n].to(torch.int32), d_meta[2 * n:].to(torch.int32)
-    out = torch.empty((n, 3, out_h, out_w), device=dev, dtype=torch.float32)
-    L.call("dig_resize_bicubic_normalize_u8", L.ptr(d_packed), L.ptr(d_off), L.ptr(d_h), L.ptr(d_w), n, L.ptr(out), out_h, out_w,
-           ctypes.c_float(mean), ctypes.c_float(std), int(hs.max()), int(ws.max()), L.stream())
+    pk = crops if isinstance(crops, PackedCrops) else pack_crops(crops, device)
+    out = torch.empty((pk.n, 3, out_h, out_w), device=pk.data.device, dtype=torch.float32)
+    L.call("dig_resize_bicubic_normalize_u8", L.ptr(pk.data), L.ptr(pk.offsets), L.ptr(pk.heights), L.ptr(pk.widths), pk.n, L.ptr(out), out_h,
+           out_w, ctypes.c_float(mean), ctypes.c_float(std), pk.max_h, pk.max_w, L.stream())
     return out
 
 
 class GpuBatchTransform:
-    """Batch form of DataAugmentationForMAE.__call__ (datasets.py:41-42): (crops, aug_crops) -> (images, aug_images, masks)."""
+    """Batch form of DataAugmentationForMAE.__call__ (datasets.py:41-42): (crops, aug_crops) -> (images, aug_images, masks).
 
-    def __init__(self, args, seed=0, device="cuda"):
+    key_view_aug="seqclr": without explicit `aug_crops` the second view is the reference's augmented key view (dataset_image.py:39-50,
+    88-120,145-149), built on the device from the same upload as the first view (dig_amd/augment.py).  Explicit `aug_crops`, or
+    key_view_aug=None, give the plain transform of what is passed (None -> no second view)."""
+
+    def __init__(self, args, seed=0, device="cuda", key_view_aug=None):
         self.h, self.w = args.input_h, args.input_w
         self.device = device
         self.masked_position_generator = RandomMaskingGenerator(args.window_size, args.mask_ratio, num_view=args.num_view,
                                                                 seed=seed, device=device)
+        if key_view_aug not in (None, "seqclr"):
+            raise ValueError(f"key_view_aug must be None or 'seqclr', not {key_view_aug!r}")
+        self.key_view = KeyViewAugment(seed, device, self.h, self.w) if key_view_aug == "seqclr" else None
 
     def __call__(self, crops, aug_crops=None):
-        images = resize_normalize(crops, self.h, self.w, device=self.device)
-        aug = resize_normalize(aug_crops, self.h, self.w, device=self.device) if aug_crops is not None else None
+        packed = pack_crops(crops, self.device)
+        images = resize_normalize(packed, self.h, self.w)
+        if aug_crops is not None:
+            aug = resize_normalize(aug_crops, self.h, self.w, device=self.device)
+        else:
+            aug = self.key_view(packed) if self.key_view is not None else None
         masks = self.masked_position_generator(len(crops))
         return images, aug, masks

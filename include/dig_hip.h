@@ -27,6 +27,8 @@ extern "C" {
 typedef struct ihipStream_t* hipStream_t;
 #endif
 
+#include "dig_aug_types.h"
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Matrix-core GEMM.  Replaces F.linear / nn.Linear and its autograd (modeling_finetune.py:53-60,91-93,119;
  * modeling_pretrain_moco_mim_ori.py:414-426,463-482).
@@ -438,6 +440,27 @@ int dig_resize_bicubic_normalize_u8(const unsigned char* packed, const long long
  * Philox4x32-10 key of counter (r, p, step, 0) under key (seed), the num_mask smallest (key, p) are masked. */
 int dig_random_masks(unsigned char* mask, int n_rows, int n_patches, int num_mask, unsigned long long seed, unsigned step,
                      hipStream_t stream);
+
+/* ---- key-view augmentation of MoCo pre-training (dataset/dataset_image.py:39-50,88-120,145-149): imgaug SomeOf((2, 5), 10 seqCLR ops) at
+ * the crop's resolution, Resize((out_h, out_w), BICUBIC), RandomApply(ColorJitter(0.4, 0.4, 0.2, 0.1), 0.8), RandomGrayscale(0.2), ToTensor,
+ * Normalize.  One dig_kv_params table per image (include/dig_aug_types.h; the semantics in dig_amd/csrc/keyview.inc); crops as for
+ * dig_resize_bicubic_normalize_u8.  Tables may be drawn by dig_keyview_sample or built by the caller.
+ * dig_keyview_sample: params[i] from Philox4x32-10 under key (seed), counter (i, step, draw index, 0x4B455956); the derived coefficients
+ *   need the image's heights[i] x widths[i].
+ * dig_keyview_workspace_bytes: bytes of `work` for crops packed into packed_bytes (two copies of the packed layout, 256-byte rounded).
+ * dig_keyview_stage_a_u8: the seqCLR ops of every image (uint8 after every op); the result lands in the first half of `work`, image i at
+ *   work + offsets[i] (same layout as packed, which is only read).  work_bytes from dig_keyview_workspace_bytes.
+ * dig_keyview_stage_b: stage_a (the first half of `work`) -> out[n_img][3][out_h][out_w] fp32: Pillow's bicubic resize, the jitter ops,
+ *   grayscale, (v / 255 - mean) / std, bit-exact with Pillow + torchvision.  max_h / max_w bound the crop sizes. */
+int dig_keyview_sample(struct dig_kv_params* params, const int* heights, const int* widths, int n_img, unsigned long long seed, unsigned step,
+                       hipStream_t stream);
+long long dig_keyview_workspace_bytes(long long packed_bytes, int n_img);
+int dig_keyview_stage_a_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
+                           const struct dig_kv_params* params, unsigned char* work, long long work_bytes, int max_h, int max_w,
+                           hipStream_t stream);
+int dig_keyview_stage_b(const unsigned char* stage_a, const long long* offsets, const int* heights, const int* widths, int n_img,
+                        const struct dig_kv_params* params, float* out, int out_h, int out_w, float mean, float std_, int max_h, int max_w,
+                        hipStream_t stream);
 
 /* ---- greedy decode with a K/V cache (models/decoder.py:173-252, models/transformer_layer.py:238-281)
  * One decode step of TFDecoder.forward_test per call sequence: dig_decode_embed (token embedding + position row t), then per

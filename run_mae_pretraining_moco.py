@@ -17,8 +17,12 @@ What is different, on purpose: the input pipeline.  The reference decodes LMDB c
 (dataset/dataset_image.py -- lmdb, cv2 and imgaug are not part of this image and are out of scope).  Here the data
 source is either `--synthetic N` / `--data_path synthetic` (N samples of U(-1,1) crops per epoch: the benchmark's data) or a directory tree
 of image files under `--image_alone_path` / `--data_path` (decoded with Pillow to uint8 crops; resize + normalisation + mask drawing happen on the MI355X,
-dig_amd/datasets.py).  The augmented view is produced by `--aug_module pkg.fn` (a callable `fn(list_of_uint8_crops) -> list_of_uint8_crops`
-run on the host) -- without it the second view is the crop itself.
+dig_amd/datasets.py).  The second (key) view of `--num_view 2`:
+  --key_view_aug seqclr   the reference's augmentation of that view (dataset/dataset_image.py:39-50,88-120,145-149: imgaug SomeOf((2, 5))
+                          of its 10 seqCLR ops, Resize, ColorJitter(0.4, 0.4, 0.2, 0.1) with p = 0.8, RandomGrayscale(0.2)), drawn and run
+                          on the MI355X from the crops already uploaded for the first view (dig_amd/augment.py);
+  --aug_module pkg.fn     a callable `fn(list_of_uint8_crops) -> list_of_uint8_crops` run on the host (not combinable with the above);
+  neither (the default, --key_view_aug none): the second view is the crop itself.
 """
 import argparse
 import datetime
@@ -81,6 +85,8 @@ def get_args(argv=None):
     a("--image_alone_path", nargs="+", type=str, default="", help="directory tree(s) of image files (png / jpg / bmp ...)")
     a("--synthetic", type=int, default=0, help="N > 0: N synthetic samples per epoch instead of --image_alone_path")
     a("--aug_module", type=str, default="", help="pkg.module.fn: host callable producing the augmented crops of the second view")
+    a("--key_view_aug", type=str, default="none", choices=("none", "seqclr"),
+      help="seqclr: the reference's key-view augmentation (seqCLR ops + ColorJitter + RandomGrayscale) on the device; none: the crop itself")
     a("--num_workers", type=int, default=10)
     # run
     a("--output_dir", type=str, default="")
@@ -111,6 +117,8 @@ def get_args(argv=None):
     given = [n for n in REFERENCE_ONLY_SWITCHES if getattr(args, n[2:])] + [n for n in REFERENCE_ONLY_VALUES if getattr(args, n[2:]) is not None]
     if given:
         print("flags of the reference that its pre-training path does not read either (accepted, not used): " + " ".join(given))
+    if args.key_view_aug != "none" and args.aug_module:
+        raise SystemExit("--key_view_aug and --aug_module both produce the second view: give one of them")
     if args.use_ema:
         raise SystemExit("--use_ema (teacher-student mode, run_mae_pretraining_moco.py:326-338) is not built")
     return args
@@ -194,6 +202,11 @@ class ImageFolderCrops:
                 pending = nxt
 
 
+def _key_view_on_device(crops):
+    """ImageFolderCrops' host hook under --key_view_aug: no host-side second view, so GpuBatchTransform builds it on the device."""
+    return None
+
+
 def main(args):
     import dig_amd.utils as utils
     from dig_amd.datasets import GpuBatchTransform, RandomMaskingGenerator
@@ -235,6 +248,8 @@ def main(args):
         # (the reference mixes --data_path and --image_alone_path datasets when both are given: one list of directory trees here)
         alone = args.image_alone_path if isinstance(args.image_alone_path, (list, tuple)) else ([args.image_alone_path] if args.image_alone_path else [])
         args.image_alone_path = data_path + list(alone)
+    if args.synthetic > 0 and args.key_view_aug != "none":
+        print("--key_view_aug: the synthetic source hands over normalised views, not crops; no key-view augmentation")
     if args.synthetic > 0:
         gen = RandomMaskingGenerator(args.window_size, args.mask_ratio, num_view=args.num_view, seed=seed, device=device)
         loader = SyntheticCrops(args.synthetic // world, args.batch_size, device, seed, gen)
@@ -243,8 +258,11 @@ def main(args):
         if args.aug_module:
             mod, fn = args.aug_module.rsplit(".", 1)
             aug = getattr(importlib.import_module(mod), fn)
+        elif args.key_view_aug == "seqclr":
+            aug = _key_view_on_device
         roots = args.image_alone_path if isinstance(args.image_alone_path, (list, tuple)) else [args.image_alone_path]
-        loader = ImageFolderCrops(roots, args.batch_size, rank, world, GpuBatchTransform(args, seed=seed, device=device), aug, args.num_workers,
+        tf = GpuBatchTransform(args, seed=seed, device=device, key_view_aug=None if args.key_view_aug == "none" else args.key_view_aug)
+        loader = ImageFolderCrops(roots, args.batch_size, rank, world, tf, aug, args.num_workers,
                                   cap=min(args.num_samples, args.aloneimage_num_samples))
     steps_per_epoch = len(loader)
     if steps_per_epoch == 0:
