@@ -122,3 +122,133 @@ def _workspace_bytes(packed_bytes, n_img):
     if ws <= 0:
         L.check(int(ws), "dig_keyview_workspace_bytes")
     return ws
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# ABINet augmentation of fine-tuning (--num_view 2 --use_abi_aug): transforms.py:188-504 / dataset/dataset_lmdb.py:36-47 of the reference.
+
+# field order and sizes of struct dig_abi_params / dig_abi_run (include/dig_aug_types.h)
+ABI_PARAMS_DTYPE = np.dtype([
+    ("geom", "<i4"), ("det", "<i4"), ("jit", "<i4"), ("geom_interp", "<i4"), ("angle", "<f4"), ("scale", "<f4"), ("shear", "<f4", 2),
+    ("persp_ow", "<i4", 4), ("persp_oh", "<i4", 4), ("h", "<i4"), ("w", "<i4"), ("wh", "<i4"), ("ww", "<i4"), ("minv", "<f4", 9),
+    ("rs_interp", "<i4", 2), ("mb_k", "<f4", 25), ("jit_order", "<i4", 4), ("jit_factor", "<f4", 4), ("hue_shift", "<i4"),
+    ("noise_key", "<u4", 2), ("noise_step", "<u4"), ("final_buf", "<i4"), ("pad0", "<i4"), ("ws_off", "<i8"), ("pad", "<i4", 24)])
+ABI_PARAMS_WORDS = 96
+assert ABI_PARAMS_DTYPE.itemsize == 4 * ABI_PARAMS_WORDS
+ABI_RUN_DTYPE = np.dtype([("geom_type", "<i4"), ("noise_var", "<i4"), ("mb_size", "<i4"), ("mb_angle", "<f4"), ("rescale_factor", "<i4"),
+                          ("det_order", "<i4", 3)])
+assert ABI_RUN_DTYPE.itemsize == 32
+
+GEOM_NAMES = ("rotation", "affine", "perspective")
+DET_NAMES = ("noise", "motion_blur", "rescale")
+
+
+def draw_abi_run(seed):
+    """The run parameters the reference's constructors draw once per dataset object (CVGeometry, CVGaussianNoise, CVMotionBlur,
+    CVRescale, CVDeterioration's shuffle), from numpy's RandomState(seed): a record of ABI_RUN_DTYPE."""
+    rs = np.random.RandomState(seed & 0xFFFFFFFF)
+    r = np.zeros((), dtype=ABI_RUN_DTYPE)
+    t = rs.random_sample()
+    r["geom_type"] = 0 if t < 0.33 else (1 if t < 0.66 else 2)
+    r["noise_var"] = max(int(rs.beta(1, 4) * 20), 1)
+    r["mb_size"] = max(int(rs.beta(1, 4) * 6), 1)
+    r["mb_angle"] = rs.uniform(-90, 90)
+    r["rescale_factor"] = round(rs.uniform(0, 4))
+    r["det_order"] = rs.permutation(3)
+    return r
+
+
+def abi_params_to_numpy(params):
+    """Device / host table tensor (int32 [n, 96]) -> numpy structured array of ABI_PARAMS_DTYPE."""
+    return params.cpu().numpy().view(ABI_PARAMS_DTYPE).reshape(-1)
+
+
+def abi_params_from_numpy(table, device):
+    """numpy structured array of ABI_PARAMS_DTYPE -> int32 [n, 96] tensor on `device` (a caller-built table)."""
+    a = np.ascontiguousarray(np.asarray(table, dtype=ABI_PARAMS_DTYPE))
+    return torch.from_numpy(a.view(np.int32).reshape(-1, ABI_PARAMS_WORDS).copy()).to(device)
+
+
+class AbiAugment:
+    """The fine-tune training view of a packed batch of crops, on the device: CVGeometry (p 0.5), CVDeterioration (p 0.25), CVColorJitter
+    (p 0.25), Resize((out_h, out_w), BICUBIC), ToTensor, Normalize -- the reference's `--num_view 2 --use_abi_aug` transform.
+
+    `run` holds what the reference fixes per dataset object (geometry type, noise variance, motion-blur size and angle, rescale factor,
+    deterioration order), drawn from `seed` at construction; a caller may set it.  `__call__` draws the per-image tables for
+    (seed, step) -- Philox4x32-10 -- runs the stages and advances its step counter.
+
+    The warped images live in a workspace sized by the sampler (`info[0]`, one 32-byte readback per batch): with the affine scale up to 2
+    and the rotation / shear canvases a warped image can hold several times the crop's pixels, and a bound from (n, max_h, max_w) alone
+    would reserve that for every image."""
+
+    def __init__(self, seed=0, device="cuda", out_h=32, out_w=128, mean=0.5, std=0.5):
+        self.seed, self.step, self.device = int(seed), 0, torch.device(device)
+        self.out_h, self.out_w, self.mean, self.std = out_h, out_w, mean, std
+        self.run = draw_abi_run(self.seed)
+
+    def _run_ptr(self):
+        self._run_buf = np.ascontiguousarray(np.asarray(self.run, dtype=ABI_RUN_DTYPE).reshape(1))
+        return ctypes.c_void_p(self._run_buf.ctypes.data)
+
+    def sample(self, packed, step=None):
+        """(int32 [n, 96] tables at (seed, step), int64 [4] info on the device: workspace bytes, max warped height / width, images with a
+        workspace).  The counter is not advanced."""
+        params = torch.empty((packed.n, ABI_PARAMS_WORDS), device=packed.data.device, dtype=torch.int32)
+        info = torch.empty(4, device=packed.data.device, dtype=torch.int64)
+        L.call("dig_abiaug_sample", L.ptr(params), L.ptr(info), L.ptr(packed.heights), L.ptr(packed.widths), packed.n, self._run_ptr(),
+               ctypes.c_ulonglong(self.seed), ctypes.c_uint((self.step if step is None else step) & 0xFFFFFFFF), L.stream())
+        return params, info
+
+    def _common(self, packed, params, work):
+        return (L.ptr(packed.data), L.ptr(packed.offsets), L.ptr(packed.heights), L.ptr(packed.widths), packed.n, L.ptr(params),
+                self._run_ptr(), L.ptr(work) if work.numel() else None, work.numel())
+
+    def workspace(self, info):
+        """(uint8 workspace, max warped height, max warped width) for a sampler's info (one readback)."""
+        total, mh, mw, _ = (int(v) for v in info.cpu())
+        return torch.empty(total, device=info.device, dtype=torch.uint8), mh, mw
+
+    def warp(self, packed, params, work, max_wh, max_ww):
+        L.call("dig_abiaug_warp_u8", *self._common(packed, params, work), max(max_wh, packed.max_h), max(max_ww, packed.max_w), L.stream())
+
+    def deteriorate(self, packed, params, work, max_wh, max_ww):
+        L.call("dig_abiaug_deteriorate_u8", *self._common(packed, params, work), max(max_wh, packed.max_h), max(max_ww, packed.max_w),
+               L.stream())
+
+    def tail(self, packed, params, work, max_wh, max_ww):
+        out = torch.empty((packed.n, 3, self.out_h, self.out_w), device=packed.data.device, dtype=torch.float32)
+        L.call("dig_abiaug_tail", *self._common(packed, params, work), L.ptr(out), self.out_h, self.out_w, ctypes.c_float(self.mean),
+               ctypes.c_float(self.std), max(max_wh, packed.max_h), max(max_ww, packed.max_w), L.stream())
+        return out
+
+    def apply(self, packed, params, info=None):
+        """All stages with the given tables: fp32 [n, 3, out_h, out_w].  `info` as `sample` returns it; None: derived from the tables."""
+        if info is None:
+            t = abi_params_to_numpy(params)
+            total = int(max((t["ws_off"] + [workspace_bytes(g, d, h, w, self.run) for g, d, h, w in zip(t["geom"], t["det"], t["wh"], t["ww"])]).max(), 0))
+            info = torch.tensor([total, int(t["wh"].max()), int(t["ww"].max()), 0], dtype=torch.int64)
+        work, mh, mw = self.workspace(info)
+        work = work.to(packed.data.device)
+        self.warp(packed, params, work, mh, mw)
+        self.deteriorate(packed, params, work, mh, mw)
+        return self.tail(packed, params, work, mh, mw)
+
+    def __call__(self, packed):
+        if not isinstance(packed, PackedCrops):
+            packed = pack_crops(packed, self.device)
+        params, info = self.sample(packed)
+        out = self.apply(packed, params, info)
+        self.step += 1
+        return out
+
+
+def workspace_bytes(geom, det, wh, ww, run):
+    """Workspace bytes of one image (dig_abiaug_workspace_bytes)."""
+    f = L.lib().dig_abiaug_workspace_bytes
+    f.restype = ctypes.c_longlong
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    buf = np.ascontiguousarray(np.asarray(run, dtype=ABI_RUN_DTYPE).reshape(1))
+    b = f(int(geom), int(det), int(wh), int(ww), ctypes.c_void_p(buf.ctypes.data))
+    if b < 0:
+        L.check(int(b), "dig_abiaug_workspace_bytes")
+    return b

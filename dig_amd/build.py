@@ -14,10 +14,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # hazard padding and are no faster than two scalar ops on this chip (MI355X_MICROARCH.md: an anti-lever beside MFMAs): 205 -> 44 s_nop in
 # the fused-MLP S-wave loop, and 24.28 -> 24.15 ms per step with it on every file (A/B on one box)
 FLAGS.append("-fno-slp-vectorize")
-# per-file extras.  keyview.hip: the key-view augmentation is defined by float32 arithmetic without contraction (its numpy model and the
-# plain-C++ build follow it bit for bit); under -ffp-contract=fast the backend fuses multiply-adds whatever `#pragma clang fp contract(off)`
-# says, so that file is compiled with contraction off
-EXTRA_FLAGS = {"keyview.hip": ["-ffp-contract=off"]}
+# per-file extras.  keyview.hip / abiaug.hip: the key-view and ABINet augmentations are defined by float32 / double arithmetic without
+# contraction (their numpy models and the plain-C++ build follow them bit for bit); under -ffp-contract=fast the backend fuses
+# multiply-adds whatever `#pragma clang fp contract(off)` says, so those files are compiled with contraction off
+EXTRA_FLAGS = {"keyview.hip": ["-ffp-contract=off"], "abiaug.hip": ["-ffp-contract=off"]}
 
 
 def sources():
@@ -90,7 +90,9 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                "wgrad_wide_kernel<3, 7>", "attn_block_kernel<true, 2>", "attn_block_kernel<false, 2>", "attn_bwd_kernel<false, 3, false>", "attn_bwd_kernel<false, 3, true>",
                "gemm_wide_kernel<false, true, 0, 4, 3, 2, 2, false, 64, 2, false>", "gemm_pwide_kernel<4, false, false>",
                # the key-view augmentation of the input path (keyview.hip): the sampler's and the stages' per-thread state stays in registers
-               "keyview_sample_kernel", "keyview_stage_a_kernel", "keyview_stage_b_kernel")
+               "keyview_sample_kernel", "keyview_stage_a_kernel", "keyview_stage_b_kernel",
+               # the ABINet augmentation of fine-tuning (abiaug.hip): the same
+               "abiaug_sample_kernel", "abiaug_warp_kernel", "abiaug_det_kernel", "abiaug_tail_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

@@ -111,7 +111,8 @@ struct Rng {
 };
 
 // Fisher-Yates over the nibbles of a 64-bit word (no runtime-indexed array)
-DIG_HD inline unsigned long long shuffle_nibbles(const Rng& g, unsigned d0, int n, unsigned long long perm) {
+template <class G>
+DIG_HD inline unsigned long long shuffle_nibbles(const G& g, unsigned d0, int n, unsigned long long perm) {
   for (int i = n - 1; i >= 1; --i) {
     const int j = (int)g.below(d0 + (unsigned)(n - 1 - i), (unsigned)(i + 1));
     const unsigned long long a = (perm >> (4 * i)) & 15ull, b = (perm >> (4 * j)) & 15ull;
@@ -440,9 +441,9 @@ DIG_HD inline void hsv2rgb(int h, int s, int v, int* r, int* g, int* b) {
   }
 }
 
-// one jitter op on one pixel (contrast: d = the image's mean L, computed by the caller)
-DIG_HD inline void jitter_pixel(int op, const dig_kv_params& P, int contrast_mean, int* c) {
-  const float f = P.jit_factor[op & 3];
+// one jitter op on one pixel (contrast: d = the image's mean L, computed by the caller); factors / hue_shift as in dig_kv_params
+DIG_HD inline void jitter_apply(int op, const float* jit_factor, int hue_shift, int contrast_mean, int* c) {
+  const float f = jit_factor[op & 3];
   switch (op & 3) {
     case 0: for (int k = 0; k < 3; ++k) c[k] = blend(0, c[k], f); break;
     case 1: for (int k = 0; k < 3; ++k) c[k] = blend(contrast_mean, c[k], f); break;
@@ -454,9 +455,12 @@ DIG_HD inline void jitter_pixel(int op, const dig_kv_params& P, int contrast_mea
     default: {
       int h, s, v;
       rgb2hsv(c[0], c[1], c[2], &h, &s, &v);
-      hsv2rgb((h + P.hue_shift) & 255, s, v, &c[0], &c[1], &c[2]);
+      hsv2rgb((h + hue_shift) & 255, s, v, &c[0], &c[1], &c[2]);
     }
   }
+}
+DIG_HD inline void jitter_pixel(int op, const dig_kv_params& P, int contrast_mean, int* c) {
+  jitter_apply(op, P.jit_factor, P.hue_shift, contrast_mean, c);
 }
 
 // dynamic LDS bytes of stage B: the resize coefficient tables, four 8-byte contrast sums, the out_h x out_w x 3 image

@@ -68,8 +68,14 @@ inline int ksize_for(int in_size, int out_size) {
 // the three channels of output pixel (yy, xx) of an HWC uint8 image (h x w at src): the horizontal pass is evaluated on the fly for the
 // rows the vertical window needs (an 8-bit intermediate exactly as Pillow's).  kh / bh: [out_w][ksh] / [out_w][2], kv / bv: [out_h][ksv] /
 // [out_h][2] from coeffs_for.
-DIG_HD inline void resize_pixel(const unsigned char* __restrict__ src, int w, bool pass_h, bool pass_v, const int* kh, const int* bh,
-                                const int* kv, const int* bv, int ksh, int ksv, int yy, int xx, int r[3]) {
+// `fetch(row pointer of pixel, c[3])` yields the three channels of one source pixel: the identity below, or a per-pixel pass applied on
+// the fly (the ABINet augmentation's ColorJitter at the source resolution).
+struct FetchU8 {
+  DIG_HD void operator()(const unsigned char* p, int c[3]) const { c[0] = p[0]; c[1] = p[1]; c[2] = p[2]; }
+};
+template <class Fetch>
+DIG_HD inline void resize_pixel_f(const unsigned char* __restrict__ src, int w, bool pass_h, bool pass_v, const int* kh, const int* bh,
+                                  const int* kv, const int* bv, int ksh, int ksv, int yy, int xx, int r[3], const Fetch& fetch) {
   const int x0 = pass_h ? bh[2 * xx] : xx, nx = pass_h ? bh[2 * xx + 1] : 1;
   const int y0 = pass_v ? bv[2 * yy] : yy, ny = pass_v ? bv[2 * yy + 1] : 1;
   const int* kx = kh + xx * ksh;
@@ -83,13 +89,17 @@ DIG_HD inline void resize_pixel(const unsigned char* __restrict__ src, int w, bo
       int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
       for (int x = 0; x < nx; ++x) {
         const int k = kx[x];
-        s0 += (int)row[3 * x] * k;
-        s1 += (int)row[3 * x + 1] * k;
-        s2 += (int)row[3 * x + 2] * k;
+        int c[3];
+        fetch(row + 3 * x, c);
+        s0 += c[0] * k;
+        s1 += c[1] * k;
+        s2 += c[2] * k;
       }
       h0 = clip8(s0); h1 = clip8(s1); h2 = clip8(s2);
     } else {
-      h0 = row[0]; h1 = row[1]; h2 = row[2];
+      int c[3];
+      fetch(row, c);
+      h0 = c[0]; h1 = c[1]; h2 = c[2];
     }
     if (pass_v) {
       const int k = ky[y];
@@ -100,6 +110,10 @@ DIG_HD inline void resize_pixel(const unsigned char* __restrict__ src, int w, bo
   }
   if (pass_v) { r0 = clip8(a0); r1 = clip8(a1); r2 = clip8(a2); }
   r[0] = r0; r[1] = r1; r[2] = r2;
+}
+DIG_HD inline void resize_pixel(const unsigned char* __restrict__ src, int w, bool pass_h, bool pass_v, const int* kh, const int* bh,
+                                const int* kv, const int* bv, int ksh, int ksv, int yy, int xx, int r[3]) {
+  resize_pixel_f(src, w, pass_h, pass_v, kh, bh, kv, bv, ksh, ksv, yy, xx, r, FetchU8{});
 }
 
 // Philox4x32-10, first output word of counter (c0, c1, c2, c3) under key (k0, k1)

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .augment import KeyViewAugment, PackedCrops, pack_crops
+from .augment import AbiAugment, KeyViewAugment, PackedCrops, pack_crops
 
 
 class RandomMaskingGenerator:
@@ -85,3 +85,29 @@ class GpuBatchTransform:
             aug = self.key_view(packed) if self.key_view is not None else None
         masks = self.masked_position_generator(len(crops))
         return images, aug, masks
+
+
+class FinetuneBatchTransform:
+    """The fine-tune input transform for whole batches, with build_dataset's rule (dataset/datasets.py:68,110-116 of the reference):
+    crops (a list of HxWx3 uint8 arrays or a PackedCrops) -> fp32 [n, 3, input_h, input_w] on the device.
+
+      not training, or num_view <= 1      resize_normalize (the reference's eval / single-view transform)
+      num_view > 1 and use_abi_aug        AbiAugment (CVGeometry, CVDeterioration, CVColorJitter, Resize, Normalize)
+      num_view > 1 without it             KeyViewAugment (ImageLmdb.sequential_aug + aug_transformer = the MoCo key view)
+
+    Labels stay with the caller."""
+
+    def __init__(self, args, is_train, seed=0, device="cuda"):
+        self.h, self.w, self.device = args.input_h, args.input_w, device
+        if not is_train or getattr(args, "num_view", 1) <= 1:
+            self.kind, self.aug = "resize", None
+        elif getattr(args, "use_abi_aug", False):
+            self.kind, self.aug = "abi", AbiAugment(seed, device, self.h, self.w)
+        else:
+            self.kind, self.aug = "keyview", KeyViewAugment(seed, device, self.h, self.w)
+
+    def __call__(self, crops):
+        packed = crops if isinstance(crops, PackedCrops) else pack_crops(crops, self.device)
+        if self.aug is None:
+            return resize_normalize(packed, self.h, self.w)
+        return self.aug(packed)

@@ -57,4 +57,53 @@ typedef struct dig_kv_params {
 static_assert(sizeof(dig_kv_params) == DIG_KV_WORDS * 4, "dig_kv_params is DIG_KV_WORDS words");
 #endif
 
+
+/* ---- the fine-tune ABINet augmentation (--num_view 2 --use_abi_aug; transforms.py:188-504 and dataset/dataset_lmdb.py:36-47 of the
+ * reference): CVGeometry(45, (0, 0), (0.5, 2), (45, 15), 0.5, p 0.5), CVDeterioration(20, 6, 4, p 0.25), CVColorJitter(0.5, 0.5, 0.5, 0.1,
+ * p 0.25), Resize((32, 128), BICUBIC), ToTensor, Normalize.  Semantics of every field: dig_amd/csrc/abiaug.inc.
+ *
+ * dig_abi_run: what the reference draws once per dataset object (CVGeometry / CVDeterioration constructors), fixed for a whole run.
+ * dig_abi_params: one table of DIG_ABI_WORDS words per image, filled by dig_abiaug_sample (raw draws, the warp map, the warped size, the
+ * motion-blur kernel and the image's workspace offset).  A hand-built table (tests) must fill all of them. */
+#define DIG_ABI_WORDS 96
+#define DIG_ABI_MB_MAX 5           /* motion-blur kernel size max(int(Beta(1,4) 6), 1) <= 5 */
+
+typedef struct dig_abi_run {
+  int geom_type;             /* 0 rotation, 1 affine, 2 perspective */
+  int noise_var;             /* Gaussian noise variance, 1..19 */
+  int mb_size;               /* motion-blur kernel size, 1..5 */
+  float mb_angle;            /* motion-blur angle, degrees, U(-90, 90) */
+  int rescale_factor;        /* pyrDown steps, 0..4 (0: the rescale op is the identity and is skipped) */
+  int det_order[3];          /* the deterioration ops in the order they run: 0 noise, 1 motion blur, 2 rescale */
+} dig_abi_run;
+
+typedef struct dig_abi_params {
+  int geom, det, jit;        /* the three gates (p 0.5, 0.25, 0.25) */
+  int geom_interp;           /* 0 nearest, 1 linear, 2 cubic, 3 area (a warp treats area as linear) */
+  float angle, scale;        /* rotation / affine angle sym(45) (degrees), affine scale U(0.5, 2) */
+  float shear[2];            /* affine shear sym(45), sym(15) (degrees) */
+  int persp_ow[4];           /* perspective corner offsets along x, int(Beta(1,4) 0.5 W / 2): TL TR BR BL */
+  int persp_oh[4];           /* ... along y, int(Beta(1,4) 0.5 H / 2) */
+  int h, w;                  /* the crop's size */
+  int wh, ww;                /* the size after the geometry (h, w when geom == 0) */
+  float minv[9];             /* warp map, output (x, y) -> source ((m0 x + m1 y + m2) / d, (m3 x + m4 y + m5) / d), d = m6 x + m7 y + m8 */
+  int rs_interp[2];          /* rescale: interpolation of the resize to 128 x 512 and of the resize back (0..3 as geom_interp) */
+  float mb_k[DIG_ABI_MB_MAX * DIG_ABI_MB_MAX]; /* motion-blur kernel of the run, row-major mb_size x mb_size (the rest 0) */
+  int jit_order[4];          /* permutation of the jitter ops 0 brightness, 1 contrast, 2 saturation, 3 hue */
+  float jit_factor[4];       /* brightness, contrast, saturation U(0.5, 1.5), hue U(-0.1, 0.1) */
+  int hue_shift;             /* trunc(hue 255) mod 256 */
+  unsigned noise_key[2];     /* Philox key of the Gaussian noise (the sampler's seed, lo / hi) */
+  unsigned noise_step;       /* ... and its step */
+  int final_buf;             /* the image the tail reads: 0 the crop, 1 region A, 2 region B of the image's workspace */
+  int pad0;
+  long long ws_off;          /* byte offset of the image's workspace (regions A, B, R: abiaug.inc) */
+  int pad[24];
+} dig_abi_params;
+
+#ifdef __cplusplus
+static_assert(sizeof(dig_abi_run) == 8 * 4, "dig_abi_run is 8 words");
+static_assert(sizeof(dig_abi_params) == DIG_ABI_WORDS * 4, "dig_abi_params is DIG_ABI_WORDS words");
+static_assert(__builtin_offsetof(dig_abi_params, ws_off) % 8 == 0, "ws_off is 8-byte aligned");
+#endif
+
 #endif /* DIG_AUG_TYPES_H */

@@ -462,6 +462,35 @@ int dig_keyview_stage_b(const unsigned char* stage_a, const long long* offsets, 
                         const struct dig_kv_params* params, float* out, int out_h, int out_w, float mean, float std_, int max_h, int max_w,
                         hipStream_t stream);
 
+/* ---- ABINet augmentation of fine-tuning (--num_view 2 --use_abi_aug; transforms.py:188-504 of the reference): CVGeometry (p 0.5),
+ * CVDeterioration (p 0.25), CVColorJitter (p 0.25), Resize((out_h, out_w), BICUBIC), ToTensor, Normalize.  Run parameters in one
+ * dig_abi_run (a HOST pointer: the kernels take it by value), one dig_abi_params table per image (include/dig_aug_types.h; semantics,
+ * rounding and the workspace layout in dig_amd/csrc/abiaug.inc).  Crops as for dig_resize_bicubic_normalize_u8.  A run is rejected
+ * (DIG_ERR_ARG) unless geom_type is 0..2, noise_var >= 0, mb_size 1..5, rescale_factor 0..4.
+ * dig_abiaug_sample: params[i] from Philox4x32-10 under key (seed), counter (i, step, draw index, 0x41424941), each with its warped size and
+ *   its workspace offset; info[4] (device): total workspace bytes, max warped height, max warped width, images with a workspace.
+ * dig_abiaug_workspace_bytes: the workspace bytes of one image with the given gates and warped size (what the sampler adds up), or
+ *   DIG_ERR_ARG.
+ * dig_abiaug_warp_u8: the geometry of every image whose gate fired, into its region A of `work`.  work_bytes >= info[0] (0: nothing to
+ *   do, work may be NULL); max_wh / max_ww >= the warped sizes (info[1], info[2]) and the crops' sizes.  An image whose table places it
+ *   outside work_bytes is skipped.
+ * dig_abiaug_deteriorate_u8: the run's deterioration ops, in its order, on every image whose gate fired (same arguments).
+ * dig_abiaug_tail: every image (the crop, or its last workspace region) -> out[n_img][3][out_h][out_w] fp32: the jitter ops at the image's
+ *   resolution, Pillow's bicubic resize, (v / 255 - mean) / std, bit-exact with Pillow + torchvision.  DIG_ERR_UNSUPPORTED when the
+ *   coefficient tables for max_wh x max_ww do not fit in LDS. */
+int dig_abiaug_sample(struct dig_abi_params* params, long long* info, const int* heights, const int* widths, int n_img,
+                      const struct dig_abi_run* run, unsigned long long seed, unsigned step, hipStream_t stream);
+long long dig_abiaug_workspace_bytes(int geom, int det, int wh, int ww, const struct dig_abi_run* run);
+int dig_abiaug_warp_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
+                       const struct dig_abi_params* params, const struct dig_abi_run* run, unsigned char* work, long long work_bytes,
+                       int max_wh, int max_ww, hipStream_t stream);
+int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
+                              const struct dig_abi_params* params, const struct dig_abi_run* run, unsigned char* work, long long work_bytes,
+                              int max_wh, int max_ww, hipStream_t stream);
+int dig_abiaug_tail(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
+                    const struct dig_abi_params* params, const struct dig_abi_run* run, const unsigned char* work, long long work_bytes,
+                    float* out, int out_h, int out_w, float mean, float std_, int max_wh, int max_ww, hipStream_t stream);
+
 /* ---- greedy decode with a K/V cache (models/decoder.py:173-252, models/transformer_layer.py:238-281)
  * One decode step of TFDecoder.forward_test per call sequence: dig_decode_embed (token embedding + position row t), then per
  * layer LayerNorm / dig_gemm_bf16 for the projections (the fused q|k|v GEMM writes row t of the [B, T, 3*heads*64] cache in
