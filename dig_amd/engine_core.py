@@ -15,6 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import encoder_blocks as EB
 from . import ops
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -160,10 +161,6 @@ class _BlockSaved:
         return (x, ln1, mu1, rs1) + tuple(self.view(k) for k in ("qkv", "ctx", "lse", "x_mid", "ln2", "mu2", "rs2", "pre", "act"))
 
 
-def _saved_tensors(s):
-    return s.tensors() if isinstance(s, _BlockSaved) else s
-
-
 class _Step:
     def __init__(self, model):
         self._keep = []                             # tensors the side stream still reads (see _on_side)
@@ -196,67 +193,19 @@ class _Step:
             ops.L.call("dig_patch_embed_fwd", ops.L.ptr(im), ops.L.ptr(ew.pe_w), ops.L.ptr(ew.pe_b),
                        ops.L.ptr(mask_u8[half * B:(half + 1) * B]), ops.L.ptr(ew.mask_token), ops.L.ptr(M._pos),
                        ops.L.ptr(x[half * B * N:(half + 1) * B * N]), B, M.gh, M.gw, D, ops.L.stream())
-        saved = []
-        scale = (D // H) ** -0.5
         chain = ops.mlp_chain_supported(D, M.F, R) and bool(ops.MLP_CHAIN_MASK & (2 if save else 1))
-        chain_ln = chain and ops.MLP_CHAIN_LN and M.F <= 2048
-        nxt = None                                                      # (ln1, mean, rstd) of this block, made by the previous block's launch
-        if chain_ln and ops.BLOCK_CALLS and D == H * 64 and path is None:
+        plan = EB.Plan(chain=chain, chain_ln=chain and ops.MLP_CHAIN_LN and M.F <= 2048,
+                       attn_block=ops.attn_block_supported(H, D, B if views == 1 else None))
+        if plan.chain_ln and ops.BLOCK_CALLS and D == H * 64 and path is None:
             return self._encoder_forward_calls(ew, x, views * B, save, single_view=views == 1)
-        for i, blk in enumerate(ew.blocks):
-            ln1, mu1, rs1 = nxt if nxt is not None else ops.layernorm_fwd(x, blk["norm1.weight"], blk["norm1.bias"], M.ln_eps)
-            nxt = None
-            ds = path[i] if path is not None else None                 # x + drop_path(branch): per-sample keep / scale in the producing epilogue
-            fused_attn = ops.attn_block_supported(H, D, B if views == 1 else None) and ds is None
-            if fused_attn:
-                # qkv Linear -> attention -> proj Linear + residual in one launch (csrc/attn_block.hip); qkv / lse exist only where kept
-                x_mid, ctx, qkv, lse = ops.attn_block_fwd(ln1, x, blk["attn.qkv.weight"], blk["qkv_bias"], blk["attn.proj.weight"],
-                                                          blk["attn.proj.bias"], views * B, H, D, scale, save=save)
-            else:
-                qkv = ops.linear_fwd(ln1, blk["attn.qkv.weight"], bias=blk["qkv_bias"], alpha=scale, alpha_cols=D)
-                ctx, lse = ops.attn_fwd(qkv, views * B, H, D)
-            if chain_ln:
-                # norm2 -> fc1 -> GELU -> fc2 (+ residual) -> the NEXT block's norm1 in one launch: between two blocks the residual stream
-                # is written once and no LayerNorm launch remains (the first block's norm1 is the only stand-alone one); norm2 is taken on
-                # the way into the MLP launch
-                nb = ew.blocks[i + 1] if i + 1 < len(ew.blocks) else None
-                if not fused_attn:
-                    x_mid = ops.linear_fwd(ctx, blk["attn.proj.weight"], bias=blk["attn.proj.bias"], resid=x, drop=ds[0] if ds else None)
-                r = ops.mlp_chain_fwd_ln(x_mid, blk["norm2.weight"], blk["norm2.bias"], M.ln_eps, blk["mlp.fc1.weight"], blk["mlp.fc1.bias"],
-                                         blk["mlp.fc2.weight"], blk["mlp.fc2.bias"], nb["norm1.weight"] if nb else None,
-                                         nb["norm1.bias"] if nb else None, save=save, drop=ds[1] if ds else None)
-                ln2, mu2, rs2 = r["ln"], r["ln_mean"], r["ln_rstd"]
-                if save:
-                    saved.append((x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, r["pre"], r["act"]))
-                if nb is not None:
-                    nxt = (r["nln"], r["nln_mean"], r["nln_rstd"])
-                x = r["out"]
-                continue
-            if not fused_attn:
-                x_mid = ops.linear_fwd(ctx, blk["attn.proj.weight"], bias=blk["attn.proj.bias"], resid=x, drop=ds[0] if ds else None)
-            ln2, mu2, rs2 = ops.layernorm_fwd(x_mid, blk["norm2.weight"], blk["norm2.bias"], M.ln_eps)
-            if chain and ds is None:
-                # fc1 -> GELU -> fc2 (+ residual) in one launch: the [R, F] hidden tensor is never a GEMM operand in HBM; the online
-                # branch still writes the pre-activation and the GELU output (the backward's inputs), the momentum branch nothing
-                if save:
-                    x_out, pre, act = ops.mlp_chain_fwd(ln2, blk["mlp.fc1.weight"], blk["mlp.fc1.bias"], blk["mlp.fc2.weight"],
-                                                        blk["mlp.fc2.bias"], x_mid, save=True)
-                else:
-                    pre = act = None
-                    x_out = ops.mlp_chain_fwd(ln2, blk["mlp.fc1.weight"], blk["mlp.fc1.bias"], blk["mlp.fc2.weight"], blk["mlp.fc2.bias"], x_mid)
-            else:
-                pre = torch.empty((R, M.F), device=x.device, dtype=BF16) if save else None
-                act = ops.linear_fwd(ln2, blk["mlp.fc1.weight"], bias=blk["mlp.fc1.bias"], act=1, pre=pre)
-                x_out = ops.linear_fwd(act, blk["mlp.fc2.weight"], bias=blk["mlp.fc2.bias"], resid=x_mid, drop=ds[1] if ds else None)
-            if save:
-                saved.append((x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, pre, act))
-            x = x_out
+        drops = [ds and (None, ds[0], ds[1]) for ds in path] if path is not None else None
+        x, saved, _ = EB.forward(plan, ew.blocks, x, views * B, H, M.ln_eps, save, drops=drops)
         return x, saved
 
     def _encoder_forward_calls(self, ew, x, n_img, save, single_view=False):
         """The block loop of encoder_forward with ONE FFI crossing per block (dig_encoder_block_fwd: qkv GEMM -> attention -> proj GEMM +
         residual -> norm2 + MLP + residual + the next block's norm1) and two allocations per block (a bf16 buffer, an fp32 one) instead of
-        four crossings and thirteen allocations.  Same kernels, same arguments, same order: bit-identical to the loop above."""
+        four crossings and thirteen allocations.  Same kernels, same arguments, same order: bit-identical to encoder_blocks.forward."""
         M = self.m
         D, Fh, H = M.D, M.F, M.H
         R, dev = x.shape[0], x.device
@@ -306,7 +255,7 @@ class _Step:
     def _encoder_backward_calls(self, ew, saved, dx, wT, plan, n_img, R):
         """The block loop of encoder_backward with ONE FFI crossing per block (dig_encoder_block_bwd: the data-gradient chain with the grouped
         weight gradients in it on this stream, the five parameter-gradient reductions on the side stream behind one event) and two
-        allocations per block.  Same kernels, same arguments, same order as the loop in encoder_backward.  Returns the gradient w.r.t. the
+        allocations per block.  Same kernels, same arguments, same order as encoder_blocks.backward.  Returns the gradient w.r.t. the
         patch embedding's output rows."""
         M = self.m
         D, Fh, H = M.D, M.F, M.H
@@ -526,6 +475,30 @@ class _Step:
         else:
             self.comm.grad_ready(self.m, key)
 
+    def _backward_plan(self, chain, have_wT, rows, path):
+        """The per-entry-point backward's plan (encoder_blocks.Plan) from this module's and ops' switches as they stand NOW.
+        Grouped weight gradients: shapes the grouped kernel does not take (tiny test models) keep the per-layer launches.  red_defer: single
+        process (the 512-wide model, single-view encoders): the blocks' bias / LayerNorm column-sum launches held back as in
+        _encoder_backward_calls -- collected over ALL blocks and folded in one dig_colsum_partials_multi launch behind the walk."""
+        D, Fh = self.m.D, self.m.F
+        grouped = (ops.WGRAD_GROUP and WGRAD_GROUPING != "off" and
+                   all(ops.wgrad_group_route(o, i_, rows) is not None for o, i_ in ((Fh, D), (D, Fh), (3 * D, D), (D, D))))
+        return EB.Plan(chain_bwd=chain, chain_every=CHAIN_BWD_EVERY, chain_phase=CHAIN_BWD_PHASE, chain_lnb=ops.MLP_CHAIN_LNB,
+                       chain_proj=ops.MLP_CHAIN_PROJ, direct=have_wT, fused_qv=FUSED_QV_BIAS_SUMS,
+                       attn_proj=bool(ops.ATTN_BWD_PROJ and FUSED_QV_BIAS_SUMS and have_wT and ops.attn_bwd_proj_supported(D)
+                                      and not ops.attn_bwd_mode()),
+                       grouping=WGRAD_GROUPING if grouped else "off", inline=WGRAD_INLINE, batch_reduce=BATCH_REDUCE,
+                       red_defer=bool(RED_DEFER and self.comm is LOCAL and path is None and not BATCH_REDUCE and PHASE_MARKS is None))
+
+    @staticmethod
+    def _takes_block_calls(plan, path, saved, dx):
+        """Whether the block-call backward (_encoder_backward_calls) computes what `plan` asks for: it is the default plan -- one grouped launch
+        per block in the chain, the fused MLP backward in every block, fused q / v bias sums -- without stochastic depth, batched reductions
+        or phase marks, behind a block-call forward."""
+        return (ops.BLOCK_CALLS and plan.grouping == "block" and plan.inline and plan.chain_bwd and plan.chain_every == 1 and plan.fused_qv
+                and path is None and not plan.batch_reduce and PHASE_MARKS is None and all(isinstance(s_, _BlockSaved) for s_ in saved)
+                and dx.is_contiguous())
+
     def encoder_backward(self, ew, saved, dx, images, aug, mask_u8, views=2):
         """dx: bf16 [R, D] gradient w.r.t. the encoder output (consumed).
         The data-gradient chain (dgrad GEMMs, attention backward, LayerNorm backward) runs on the caller's stream; the
@@ -533,15 +506,10 @@ class _Step:
         second HIP stream and overlap the chain (both are latency-bound kernels that leave CU resources idle)."""
         M = self.m
         B, D, H, N = images.shape[0], M.D, M.H, M.N
-        scale = (D // H) ** -0.5
         dev = dx.device
         main, side = self._streams(dev)
-
-        def on_side(fn, *tensors):
-            self._on_side(dev, fn, *tensors)
-
-        chain_any = ops.mlp_chain_supported(D, M.F, views * B * N) and bool(ops.MLP_CHAIN_MASK & 4)
-        chain = chain_any
+        n_img, R = views * B, views * B * N
+        chain = ops.mlp_chain_supported(D, M.F, R) and bool(ops.MLP_CHAIN_MASK & 4)
         wT = getattr(self, "wT", None)
         if chain and wT is None:
             wT = self.mlp_weight_transposes(ew)
@@ -549,210 +517,26 @@ class _Step:
             for pair_ in wT:                                            # made on the side stream in forward(), read here on the main one
                 for t in pair_:
                     t.record_stream(main)
-        # The four weight gradients of a block as ONE grouped launch on the side stream (csrc/wgrad.hip), issued as soon as the block's last
-        # operand (dqkv) exists; its slabs are folded into the gradient arena by the next block's launch (or the flush after block 0), so
-        # block i's bucket is final -- and its all-reduce is issued -- one launch later.  Shapes the grouped kernel does not take (tiny test
-        # models) and the batched-reduction mode keep the per-layer launches.
-        Rg = (B * N) if views == 1 else (2 * B * N)
-        grouped = (ops.WGRAD_GROUP and WGRAD_GROUPING != "off" and
-                   all(ops.wgrad_group_route(o, i_, Rg) is not None for o, i_ in ((M.F, D), (D, M.F), (3 * D, D), (D, D))))
         path = getattr(self, "path_on", None)
-        if (grouped and chain_any and ops.BLOCK_CALLS and WGRAD_INLINE and WGRAD_GROUPING == "block" and CHAIN_BWD_EVERY == 1 and FUSED_QV_BIAS_SUMS
-                and path is None and not BATCH_REDUCE and PHASE_MARKS is None and all(isinstance(s_, _BlockSaved) for s_ in saved) and dx.is_contiguous()):
-            plan = ops.wgrad_block_plan(dev, Rg, D, M.F)
-            if plan is not None:
-                dx = self._encoder_backward_calls(ew, saved, dx, wT, plan, B if views == 1 else 2 * B, Rg)
-                grouped = None                                           # the blocks are done: only the patch embedding is left
-        grp = ops.WgradGroup(dev) if grouped else None
-        prev_block = None
-        # single process, per-entry-point path (the 512-wide model, single-view encoders): the blocks' bias / LayerNorm column-sum launches held
-        # back as in _encoder_backward_calls -- collected over ALL blocks and folded in one dig_colsum_partials_multi launch behind the loop
-        vred = ops.GradReduceBatch() if (RED_DEFER and grp and self.comm is LOCAL and path is None and not BATCH_REDUCE and PHASE_MARKS is None
-                                         and grouped is not None) else None
+        plan = self._backward_plan(chain, wT is not None, R, path)
+        blocks_done = False
+        if self._takes_block_calls(plan, path, saved, dx):
+            wplan = ops.wgrad_block_plan(dev, R, D, M.F)
+            if wplan is not None:
+                dx = self._encoder_backward_calls(ew, saved, dx, wT, wplan, n_img, R)
+                blocks_done = True                                       # only the patch embedding is left
+        if not blocks_done:
+            def on_side(fn, *tensors):
+                self._on_side(dev, fn, *tensors)
 
-        def launch_group(*tensors):
-            if WGRAD_INLINE:
-                grp.launch()                                             # in the data-gradient chain itself (see WGRAD_INLINE)
-            else:
-                on_side(grp.launch, *tensors)
-
-        for i in reversed(range(M.depth if grouped is not None else 0)):
-            blk, g = ew.blocks[i], ew.blocks[i]["g"]
-            x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, pre, act = _saved_tensors(saved[i])
-            saved[i] = None
-            chain = chain_any and (i % CHAIN_BWD_EVERY == CHAIN_BWD_PHASE % CHAIN_BWD_EVERY)
-            if views == 1:            # only view 0 carries a gradient (zero contrastive weight): rows [0, B*N) of everything
-                Rh = B * N
-                x, ln1, mu1, rs1, qkv, ctx, x_mid, ln2, mu2, rs2, pre, act = (t[:Rh] for t in (x, ln1, mu1, rs1, qkv, ctx, x_mid, ln2, mu2, rs2, pre, act))
-                lse = lse[:B * H]
-            # x_out = x_mid + fc2(gelu(fc1(ln2)))
-            # The reductions this block leaves behind (four split-R slab sums, five bias / LayerNorm-parameter column sums) are
-            # collected in `red` and issued as two launches after the block's last weight-gradient GEMM (ops.GradReduceBatch).
-            red = ops.GradReduceBatch() if BATCH_REDUCE else None
-            wg = red.wgrad if red else ops.linear_wgrad
-            csum = red.colsum_partials if red else ops.colsum_partials
-            held = []                                                        # operands of the grouped launch (kept alive until the streams join)
-            # With the grouped launch, everything this block hands to the second stream -- the bias / LayerNorm-parameter column sums: five
-            # small launches that only consume what the chain has produced -- goes over in ONE hand-over at the end of the block (one
-            # wait_stream + one stream switch on the host instead of five; the kernels are off the critical path either way)
-            late, late_t = [], []
-
-            def side_later(fn, *tensors):
-                if grp:
-                    late.append(fn)
-                    late_t.extend(tensors)
-                else:
-                    on_side(fn, *tensors)
-            if grp:
-                def wg(dy_, x_, dw_):
-                    if not grp.add(dy_, x_, dw_):                    # (never inside an assert: python -O would drop the weight gradient)
-                        raise RuntimeError("grouped weight gradient: a problem of this block does not fit the group's plan")
-                    held.extend((dy_, x_))
-            # stochastic depth: a dropped branch back-propagates the residual gradient under the same per-sample mask (dz); its bias gradient is
-            # the column sum of the MASKED gradient, so the LayerNorm kernel's fused residual column sum is switched off for it
-            ds = path[i] if path is not None else None
-            dz = ops.dropout_apply(dx, ds[1]) if ds else dx
-            if ds:
-                on_side(lambda dz=dz: ops.colsum(dz, g["mlp.fc2.bias"]), dz)
-            if grp:
-                wg(dz, act, g["mlp.fc2.weight"])
-            else:
-                on_side(lambda dz=dz: wg(dz, act, g["mlp.fc2.weight"]), dz, act)
-            if chain:
-                # data gradient through fc2, GELU' and fc1 in one launch (d(pre-activation) leaves it as a side output for the fc1
-                # weight gradient, with its column sums = the fc1 bias gradient)
-                w2t, w1t, projt, qkvt = wT[i]
-                dctx = None
-                if ds:
-                    dln2, dact, bparts = ops.mlp_chain_bwd(dz, w2t, pre, w1t)
-                    lnp = None
-                elif ops.MLP_CHAIN_LNB and red is None and ops.MLP_CHAIN_PROJ:
-                    dx_mid, dact, bparts, lnp, dctx = ops.mlp_chain_bwd_ln(dx, w2t, pre, w1t, x_mid, blk["norm2.weight"], mu2, rs2, projt=projt)
-                    dln2 = dx_mid
-                elif ops.MLP_CHAIN_LNB and red is None:
-                    # ... with norm2's backward in the same launch: dx_mid = dx + LN2'(d ln2) leaves it, the three parameter-gradient
-                    # sums of norm2 / fc2's bias as partial rows
-                    dx_mid, dact, bparts, lnp = ops.mlp_chain_bwd_ln(dx, w2t, pre, w1t, x_mid, blk["norm2.weight"], mu2, rs2)
-                    dln2 = dx_mid
-                else:
-                    dln2, dact, bparts = ops.mlp_chain_bwd(dx, w2t, pre, w1t)
-                    lnp = None
-                _mark("blk: fused MLP backward", dev)
-            else:
-                dact, bparts = ops.linear_dgrad(dz, blk["mlp.fc2.weight"], gelu_pre=pre, colsum=True)   # d(pre-activation): GELU' and
-                dln2 = None                                                                              # the fc1 bias sums fused
-            if grp:
-                wg(dact, ln2, g["mlp.fc1.weight"])
-                if vred:
-                    vred.colsum_partials(bparts, g["mlp.fc1.bias"])
-                else:
-                    side_later(lambda: csum(bparts, g["mlp.fc1.bias"]), bparts)
-                if WGRAD_GROUPING == "pair":
-                    launch_group(*held)
-            else:
-                on_side(lambda: (wg(dact, ln2, g["mlp.fc1.weight"]), csum(bparts, g["mlp.fc1.bias"])), dact, ln2, bparts)   # (0.3 ms/step vs a 201 MB pass)
-            if dln2 is None:
-                dln2 = ops.dgrad_direct(dact, wT[i][1]) if wT is not None else None        # (direct form on fc1.weight^T where it pays)
-                if dln2 is None:
-                    dln2 = ops.linear_dgrad(dact, blk["mlp.fc1.weight"])
-            if chain and lnp is not None and vred:
-                vred.layernorm_finalize_parts(lnp, g["norm2.weight"], g["norm2.bias"], g["mlp.fc2.bias"])
-            elif chain and lnp is not None:
-                side_later(lambda lnp=lnp, g=g: ops.layernorm_finalize_parts(lnp, g["norm2.weight"], g["norm2.bias"], g["mlp.fc2.bias"]), lnp)
-            else:
-                dx_mid, fin2, ws2 = ops.layernorm_bwd(dln2, x_mid, blk["norm2.weight"], blk["norm2.bias"], mu2, rs2, dx, g["norm2.weight"],
-                                                      g["norm2.bias"], out=dln2, dres_colsum=None if ds else g["mlp.fc2.bias"], defer=True)
-                if red or vred:                                               # norm2 grads + colsum(dx) = fc2 bias grad: off the chain
-                    (red or vred).layernorm_finalize(ws2, x_mid.shape[0], D, g["norm2.weight"], g["norm2.bias"], None if ds else g["mlp.fc2.bias"])
-                else:
-                    side_later(fin2, ws2)
-            # x_mid = x + proj(attn(ln1))
-            dzp = ops.dropout_apply(dx_mid, ds[0]) if ds else dx_mid
-            if ds:
-                on_side(lambda dzp=dzp: ops.colsum(dzp, g["attn.proj.bias"]), dzp)
-            if grp:
-                wg(dzp, ctx, g["attn.proj.weight"])
-            else:
-                on_side(lambda dzp=dzp: wg(dzp, ctx, g["attn.proj.weight"]), dzp, ctx)
-            _mark("blk: LayerNorm backward (norm2)", dev)
-            # (the projection's data gradient inside the attention backward launch where that form exists: no GEMM, no d(ctx) rows)
-            proj_attn = ((not chain or dctx is None) and ops.ATTN_BWD_PROJ and FUSED_QV_BIAS_SUMS and wT is not None and not ds
-                         and ops.attn_bwd_proj_supported(D) and not ops.attn_bwd_mode())
-            if (not chain or dctx is None) and not proj_attn:
-                # (direct form on proj.weight^T where it pays: both operands K-contiguous, bit-identical to the transpose-read form)
-                dctx = ops.dgrad_direct(dzp, wT[i][2]) if wT is not None else None
-                if dctx is None:
-                    dctx = ops.linear_dgrad(dzp, blk["attn.proj.weight"])
-            _mark("blk: proj data gradient", dev)
-            gb = g["qkv_bias"]
-            if FUSED_QV_BIAS_SUMS:
-                # q_bias / v_bias gradients: per-image column sums of dQ (already carrying the q scale) and dV leave the attention
-                # kernel as [2B, D] fp32 partials (DPP row reductions of the accumulators, no extra pass over the 150 MB dqkv);
-                # K has no bias
-                if proj_attn:
-                    dqkv, qs, vs = ops.attn_bwd_proj(qkv, ctx, dzp, wT[i][2], lse, views * B, H, D, scale, bias_sums=True)
-                    dctx = None                                             # (no d(ctx) rows: the qkv data gradient below gets a buffer of its own)
-                else:
-                    dqkv, qs, vs = ops.attn_bwd(qkv, ctx, dctx, lse, views * B, H, D, scale, bias_sums=True)
-                _mark("blk: attention backward", dev)
-                if grp:
-                    wg(dqkv, ln1, g["attn.qkv.weight"])
-                    launch_group(*held)
-                    _mark("blk: grouped weight gradients", dev)
-                    if vred:
-                        vred.colsum_partials(qs, gb[:D]); vred.colsum_partials(vs, gb[2 * D:])
-                    else:
-                        side_later(lambda: (csum(qs, gb[:D]), csum(vs, gb[2 * D:])), qs, vs)
-                else:
-                    on_side(lambda: (wg(dqkv, ln1, g["attn.qkv.weight"]),
-                                     csum(qs, gb[:D]), csum(vs, gb[2 * D:])), dqkv, ln1, qs, vs)
-            else:
-                dqkv = ops.attn_bwd(qkv, ctx, dctx, lse, views * B, H, D, scale)
-                if grp:
-                    wg(dqkv, ln1, g["attn.qkv.weight"])
-                    launch_group(*held)
-                    side_later(lambda: (ops.colsum(dqkv, gb[:D], cols=D), ops.colsum(dqkv[:, 2 * D:], gb[2 * D:], cols=D)), dqkv)
-                else:
-                    on_side(lambda: (wg(dqkv, ln1, g["attn.qkv.weight"]),
-                                     ops.colsum(dqkv, gb[:D], cols=D), ops.colsum(dqkv[:, 2 * D:], gb[2 * D:], cols=D)), dqkv, ln1)
-            dln1 = ops.dgrad_direct(dqkv, wT[i][3], out=dctx) if wT is not None else None
-            if dln1 is None:
-                dln1 = ops.linear_dgrad(dqkv, blk["attn.qkv.weight"], out=dctx)
-            _mark("blk: qkv data gradient", dev)
-            dx, fin1, ws1 = ops.layernorm_bwd(dln1, x, blk["norm1.weight"], blk["norm1.bias"], mu1, rs1, dx_mid, g["norm1.weight"],
-                                              g["norm1.bias"], out=dln1, dres_colsum=None if ds else g["attn.proj.bias"], defer=True)
-            _mark("blk: LayerNorm backward (norm1)", dev)
-            if vred:
-                vred.layernorm_finalize(ws1, x.shape[0], D, g["norm1.weight"], g["norm1.bias"], g["attn.proj.bias"])
-            elif red:                                                         # norm1 grads + colsum(dx_mid) = proj bias grad
-                red.layernorm_finalize(ws1, x.shape[0], D, g["norm1.weight"], g["norm1.bias"], None if ds else g["attn.proj.bias"])
-                side_later(red.flush, *red.tensors())
-            else:
-                side_later(fin1, ws1)
-            if late:
-                fns = list(late)
-                on_side(lambda: [f() for f in fns], *late_t)
-            del dact, pre, act, dln2, dqkv, dctx, held, late, late_t, dz, dzp
-            self._mark_kept(dev)
-            self._release_kept(dev)
-            # this block's gradients are final once BOTH streams pass this point: the bucket's all-reduce is issued from the
-            # side stream after it has waited for the main chain, so the main chain itself never stalls on the collective.
-            # (Grouped weight gradients: block i's slabs are folded by the NEXT launch, so the bucket that is final here is block i + 1's.)
-            if grp:
-                if prev_block is not None:
-                    self._grad_ready(dev, f"encoder.blocks.{prev_block}")
-                prev_block = i
-            else:
-                self._grad_ready(dev, f"encoder.blocks.{i}")
-        if vred:
-            vred.flush()                                                     # (vectors only: one launch per 112 segments, on this stream)
-        if grp:
-            if WGRAD_INLINE:
-                grp.flush()
-            else:
-                on_side(grp.flush)
-            if prev_block is not None:
-                self._grad_ready(dev, f"encoder.blocks.{prev_block}")
+            def block_done():
+                self._mark_kept(dev)
+                self._release_kept(dev)
+            drops = [ds and (None, ds[0], ds[1]) for ds in path] if path is not None else None
+            # views == 1: only view 0 carries a gradient (zero contrastive weight): rows [0, B*N) of everything.  A bucket's all-reduce is issued
+            # from the side stream after it has waited for the main chain (_grad_ready), so the main chain never stalls on the collective
+            dx = EB.backward(plan, ew.blocks, saved, dx, wT, n_img, H, on_side, drops=drops, rows=R if views == 1 else None,
+                             block_done=block_done, grad_ready=lambda key: self._grad_ready(dev, key), mark=_mark)
         for half, im in enumerate((images, aug)[:views]):
             ops.patch_embed_bwd_mfma(dx[half * B * N:(half + 1) * B * N], im, mask_u8[half * B:(half + 1) * B], ew.g_pe_w, ew.g_pe_b,
                                      ew.g_mask_token, D, M.gh, M.gw)

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib as L
 from . import dropout as DR
+from . import encoder_blocks as EB
 from . import ops
 from .recognizer import RecModel, _encoder_pos, _sinusoid
 
@@ -210,6 +211,27 @@ class RecModelTrain(RecModel):
             st = self._side = torch.cuda.Stream(device=dev, priority=-1)   # (as the pre-training side stream)
         return st
 
+    def enc_blocks(self):
+        """The encoder blocks' accessors as encoder_blocks reads them (engine_core._EncWeights' key names: fp32 parameters, bf16 GEMM operands
+        from the shadow, "qkv_bias" = q_bias | 0 | v_bias of the arena layout, "g": the same names in the gradient arena), rebuilt when an
+        arena has been re-made (.to(), _prepare_train, a copy of the model with arenas of its own)."""
+        c = getattr(self, "_enc_blocks", None)
+        if c is None or c[0] is not self.flat_params or c[1] is not self.flat_grads or c[2] is not self._shadow:
+            blocks = []
+            for i in range(self.depth):
+                b = f"encoder.blocks.{i}."
+                qo = self._offsets[b + "attn.q_bias"][0]
+                f32 = ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")
+                w16 = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
+                d = {k: self._view(self.flat_params, b + k) for k in f32}
+                d.update({k: self._view(self._shadow, b + k) for k in w16})
+                d["qkv_bias"] = self.flat_params[qo:qo + 3 * self.D]
+                d["g"] = {k: self._view(self.flat_grads, b + k) for k in f32 + w16}
+                d["g"]["qkv_bias"] = self.flat_grads[qo:qo + 3 * self.D]
+                blocks.append(d)
+            c = self._enc_blocks = (self.flat_params, self.flat_grads, self._shadow, blocks)
+        return c[3]
+
     def refresh_shadow(self):
         ops.cast_f32_to_bf16(self.flat_params, self._shadow)
 
@@ -360,46 +382,15 @@ class _TrainStep:
         M.drop_step += 1
         pe, pa = M.drop_rate, M.attn_drop_rate
         self.ds_pos = None                              # PretrainVisionTransformerEncoder has no pos_drop (modeling_pretrain_vit.py:89-106)
-        self.ds_enc = [dict(attn=plan.spec(DR.enc_site(i, 0), pa),
-                            proj=plan.spec(DR.enc_site(i, 1), pe, DR.enc_site(i, 2), M.dpr[i], N),
-                            mlp=plan.spec(DR.enc_site(i, 3), pe, DR.enc_site(i, 4), M.dpr[i], N)) for i in range(M.depth)]
+        self.ds_enc = [(plan.spec(DR.enc_site(i, 0), pa),                                            # (attention, proj branch, MLP branch)
+                        plan.spec(DR.enc_site(i, 1), pe, DR.enc_site(i, 2), M.dpr[i], N),
+                        plan.spec(DR.enc_site(i, 3), pe, DR.enc_site(i, 4), M.dpr[i], N)) for i in range(M.depth)]
         x = ops.dropout_apply(x, self.ds_pos, out=x)
-        scale = (D // H) ** -0.5
-        self.enc_saved = []
-        self.use_chain = use_chain = FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(D, M.F, B * N)
-        ln_next = None                                                          # norm1 of the next block, when the fused MLP launch made it
-        for i in range(M.depth):
-            b = f"encoder.blocks.{i}."
-            ds = self.ds_enc[i]
-            qo = M._offsets[b + "attn.q_bias"][0]
-            qkv_bias = M.flat_params[qo:qo + 3 * D]                             # q_bias | 0 | v_bias (arena layout)
-            if ln_next is not None:
-                ln1, mu1, rs1 = ln_next
-            else:
-                ln1, mu1, rs1 = ops.layernorm_fwd(x, self.p(b + "norm1.weight"), self.p(b + "norm1.bias"), 1e-6)
-            qkv = ops.linear_fwd(ln1, self.w(b + "attn.qkv.weight"), bias=qkv_bias, alpha=scale, alpha_cols=D)
-            ctx, lse = ops.attn_fwd(qkv, B, H, D, drop=ds["attn"])
-            # x + drop_path(proj_drop(proj(.))) / x + drop_path(drop(fc2(.))) (modeling_finetune.py:120,59,156-158): GEMM epilogue
-            x_mid = ops.linear_fwd(ctx, self.w(b + "attn.proj.weight"), bias=self.p(b + "attn.proj.bias"), resid=x, drop=ds["proj"])
-            frozen = i < M.frozen_blocks                                        # no gradient flows into a frozen block: nothing is kept
-            ln_next = None
-            if use_chain:
-                # (the LayerNorm behind it -- the next block's norm1, or the encoder's final norm -- rides along where its statistics are kept)
-                nb = "encoder.norm." if i + 1 == M.depth else f"encoder.blocks.{i + 1}.norm1."
-                r = ops.mlp_chain_fwd_ln(x_mid, self.p(b + "norm2.weight"), self.p(b + "norm2.bias"), 1e-6, self.w(b + "mlp.fc1.weight"),
-                                         self.p(b + "mlp.fc1.bias"), self.w(b + "mlp.fc2.weight"), self.p(b + "mlp.fc2.bias"),
-                                         nln_g=None if frozen else self.p(nb + "weight"), nln_b=None if frozen else self.p(nb + "bias"),
-                                         save=not frozen, drop=ds["mlp"])
-                x_out, ln2, mu2, rs2, pre, act = r["out"], r["ln"], r["ln_mean"], r["ln_rstd"], r["pre"], r["act"]
-                if not frozen:
-                    ln_next = (r["nln"], r["nln_mean"], r["nln_rstd"])
-            else:
-                ln2, mu2, rs2 = ops.layernorm_fwd(x_mid, self.p(b + "norm2.weight"), self.p(b + "norm2.bias"), 1e-6)
-                pre = None if frozen else torch.empty((B * N, M.F), device=dev, dtype=BF16)
-                act = ops.linear_fwd(ln2, self.w(b + "mlp.fc1.weight"), bias=self.p(b + "mlp.fc1.bias"), act=1, pre=pre)
-                x_out = ops.linear_fwd(act, self.w(b + "mlp.fc2.weight"), bias=self.p(b + "mlp.fc2.bias"), resid=x_mid, drop=ds["mlp"])
-            self.enc_saved.append(None if frozen else (x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, pre, act))
-            x = x_out
+        self.use_chain = FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(D, M.F, B * N)
+        # x + drop_path(proj_drop(proj(.))) / x + drop_path(drop(fc2(.))) (modeling_finetune.py:120,59,156-158): GEMM epilogues.  With the chain, the
+        # LayerNorm behind a block (the next norm1 / the final norm) rides along; no gradient flows into a frozen block: nothing of it is kept
+        x, self.enc_saved, ln_next = EB.forward(EB.Plan(chain_ln=self.use_chain), M.enc_blocks(), x, B, H, 1e-6, True, drops=self.ds_enc,
+                                                tail=(self.p("encoder.norm.weight"), self.p("encoder.norm.bias")), frozen=M.frozen_blocks)
         if ln_next is not None:
             enc, emu, ers = ln_next
         else:
@@ -479,12 +470,7 @@ class _TrainStep:
                 # ceil(T / 32) query blocks only (rows T..31 are zero queries with a zero output gradient: no contribution).
                 fused, ev = kv_ready[i]
                 torch.cuda.current_stream(dev).wait_event(ev)
-                fq = fused.view(B, N, 3 * hk)[:, :, :hk]
-                Tp = (T + 31) // 32 * 32                                          # the kernels work on whole 32-query blocks
-                fq[:, T:Tp].zero_()
-                fq[:, :T] = (q2 * sc).view(B, T, hk)                              # sc = 2^-3: exact in bf16
-                ctx2, lse2 = ops.attn_fwd(fused, B, nh, hk, drop=ds["cattn"], q_rows=T)   # query blocks past T are not computed
-                a2 = ctx2.view(B, N, hk)[:, :T].reshape(B * T, hk)
+                a2, ctx2, lse2 = EB.cross_attn_fwd(fused, q2, B, T, nh, hk, sc, drop=ds["cattn"])
                 kvm, lse2 = fused, (lse2, ctx2)
             else:
                 kvm = ops.linear_fwd(mem, wkv)
@@ -518,93 +504,20 @@ class _TrainStep:
         x_last, emu, ers, enc = self.enc_last
         dx = ops.layernorm_bwd(denc, x_last, self.p("encoder.norm.weight"), self.p("encoder.norm.bias"), emu, ers, None, self.g("encoder.norm.weight"),
                                self.g("encoder.norm.bias"))
-        # ---- encoder (same chain as the pre-training backward, one view, no masking)
-        scale = (D // H) ** -0.5
-        # the four weight gradients of a block as ONE grouped launch (csrc/wgrad.hip), folded into the gradient arena by the next block's
-        # launch / the flush below -- as in the pre-training backward (engine_core.encoder_backward)
-        Rg = self.B * N
+        # ---- encoder blocks (encoder_blocks.backward: one view, no masking; frozen blocks are a prefix: the chain stops above them).  The four
+        # weight gradients of a block as ONE grouped launch on the second stream, every reduction handed over as it becomes ready
+        blocks = M.enc_blocks()
         grouped = (ops.WGRAD_GROUP and not FT_BATCH_REDUCE and
-                   all(ops.wgrad_group_route(o, i_, Rg) is not None for o, i_ in ((M.F, D), (D, M.F), (3 * D, D), (D, D))))
-        grp = ops.WgradGroup(dev) if grouped else None
+                   all(ops.wgrad_group_route(o, i_, self.B * N) is not None for o, i_ in ((M.F, D), (D, M.F), (3 * D, D), (D, D))))
         wT = None
         if getattr(self, "use_chain", False) and M.frozen_blocks < M.depth:
             # K-contiguous copies of the MLP weights for the fused backward (one launch per weight shape, 1.2 MB per matrix)
-            blocks = [f"encoder.blocks.{i}." for i in range(M.frozen_blocks, M.depth)]
-            wT = dict(zip(blocks, zip(ops.transpose_bf16_multi([self.w(b_ + "mlp.fc2.weight") for b_ in blocks]),
-                                      ops.transpose_bf16_multi([self.w(b_ + "mlp.fc1.weight") for b_ in blocks]))))
-        for i in reversed(range(M.frozen_blocks, M.depth)):                   # (frozen blocks are a prefix: the chain stops above them)
-            b = f"encoder.blocks.{i}."
-            x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, pre, act = self.enc_saved[i]
-            self.enc_saved[i] = None
-            ds = self.ds_enc[i]
-            # a dropped branch (dropout and/or drop-path) back-propagates the residual gradient under the same mask; its bias
-            # gradient is then the column sum of the MASKED gradient, so the LayerNorm kernel's fused residual column sum is off
-            # the block's reductions (slab sums of its four weight gradients, bias / LayerNorm-parameter column sums) go out as two
-            # launches after its last weight-gradient GEMM (ops.GradReduceBatch), as in the pre-training backward
-            red = ops.GradReduceBatch() if FT_BATCH_REDUCE else None
-            wg = red.wgrad if red else ops.linear_wgrad
-            csum = red.colsum_partials if red else ops.colsum_partials
-            held = []
-            if grp:
-                def side_wg(dy_, x_, dw_):
-                    if not grp.add(dy_, x_, dw_):                    # (never inside an assert: python -O would drop the weight gradient)
-                        raise RuntimeError("grouped weight gradient: a problem of this block does not fit the group's plan")
-                    held.extend((dy_, x_))
-            else:
-                def side_wg(dy_, x_, dw_):
-                    self.side(lambda: wg(dy_, x_, dw_), dy_, x_)
-            dz = ops.dropout_apply(dx, ds["mlp"])
-            if ds["mlp"] is not None:
-                self.side(lambda: ops.colsum(dz, self.g(b + "mlp.fc2.bias")), dz)
-            side_wg(dz, act, self.g(b + "mlp.fc2.weight"))
-            if wT is not None:                                                  # both data gradients of the MLP in one launch
-                dln2, dact, bparts = ops.mlp_chain_bwd(dz, wT[b][0], pre, wT[b][1])
-            else:
-                dact, bparts = ops.linear_dgrad(dz, self.w(b + "mlp.fc2.weight"), gelu_pre=pre, colsum=True)
-                dln2 = None
-            self.side(lambda: csum(bparts, self.g(b + "mlp.fc1.bias")), bparts)
-            side_wg(dact, ln2, self.g(b + "mlp.fc1.weight"))
-            if dln2 is None:
-                dln2 = ops.linear_dgrad(dact, self.w(b + "mlp.fc1.weight"))
-            dx_mid, fin2, ws2 = ops.layernorm_bwd(dln2, x_mid, self.p(b + "norm2.weight"), self.p(b + "norm2.bias"), mu2, rs2, dx,
-                                                  self.g(b + "norm2.weight"), self.g(b + "norm2.bias"), out=dln2,
-                                                  dres_colsum=self.g(b + "mlp.fc2.bias") if ds["mlp"] is None else None, defer=True)
-            if red:                                                                    # parameter-gradient reduction: off the chain
-                red.layernorm_finalize(ws2, x_mid.shape[0], D, self.g(b + "norm2.weight"), self.g(b + "norm2.bias"),
-                                       self.g(b + "mlp.fc2.bias") if ds["mlp"] is None else None)
-            else:
-                self.side(fin2, ws2)
-            dz = ops.dropout_apply(dx_mid, ds["proj"])
-            if ds["proj"] is not None:
-                self.side(lambda: ops.colsum(dz, self.g(b + "attn.proj.bias")), dz)
-            side_wg(dz, ctx, self.g(b + "attn.proj.weight"))
-            dctx = ops.linear_dgrad(dz, self.w(b + "attn.proj.weight"))
-            # q_bias / v_bias gradients leave the attention kernel as per-image partial sums (no pass over the 150 MB dqkv)
-            if FT_FUSED_QV:
-                dqkv, qs, vs = ops.attn_bwd(qkv, ctx, dctx, lse, self.B, H, D, scale, drop=ds["attn"], bias_sums=True)
-                side_wg(dqkv, ln1, self.g(b + "attn.qkv.weight"))
-                if grp:
-                    self.side(grp.launch, *held)
-                self.side(lambda: (csum(qs, self.g(b + "attn.q_bias")), csum(vs, self.g(b + "attn.v_bias"))), qs, vs)
-            else:
-                dqkv = ops.attn_bwd(qkv, ctx, dctx, lse, self.B, H, D, scale, drop=ds["attn"])
-                side_wg(dqkv, ln1, self.g(b + "attn.qkv.weight"))
-                if grp:
-                    self.side(grp.launch, *held)
-                self.side(lambda: ops.colsum(dqkv, self.g(b + "attn.q_bias"), cols=D), dqkv)
-                self.side(lambda: ops.colsum(dqkv[:, 2 * D:], self.g(b + "attn.v_bias"), cols=D))
-            dln1 = ops.linear_dgrad(dqkv, self.w(b + "attn.qkv.weight"), out=dctx)
-            dx, fin1, ws1 = ops.layernorm_bwd(dln1, x, self.p(b + "norm1.weight"), self.p(b + "norm1.bias"), mu1, rs1, dx_mid,
-                                              self.g(b + "norm1.weight"), self.g(b + "norm1.bias"), out=dln1,
-                                              dres_colsum=self.g(b + "attn.proj.bias") if ds["proj"] is None else None, defer=True)
-            if red:
-                red.layernorm_finalize(ws1, x.shape[0], D, self.g(b + "norm1.weight"), self.g(b + "norm1.bias"),
-                                       self.g(b + "attn.proj.bias") if ds["proj"] is None else None)
-                self.side(red.flush, *red.tensors())
-            else:
-                self.side(fin1, ws1)
-        if grp:
-            self.side(grp.flush)                                                # the last block's slabs: folded by a fold-only launch
+            live = blocks[M.frozen_blocks:]
+            wT = [None] * M.frozen_blocks + list(zip(ops.transpose_bf16_multi([b_["mlp.fc2.weight"] for b_ in live]),
+                                                     ops.transpose_bf16_multi([b_["mlp.fc1.weight"] for b_ in live])))
+        plan = EB.Plan(chain_bwd=wT is not None, fused_qv=FT_FUSED_QV, grouping="block" if grouped else "off", side_each=True,
+                       batch_reduce=FT_BATCH_REDUCE)
+        dx = EB.backward(plan, blocks, self.enc_saved, dx, wT, self.B, H, self.side, first=M.frozen_blocks, drops=self.ds_enc)
         if "encoder.patch_embed.proj.weight" in M.frozen:
             return
         dx = ops.dropout_apply(dx, self.ds_pos, out=dx)
@@ -657,13 +570,7 @@ class _TrainStep:
             o2, n2, _ = M._offsets[p + "enc_attn.linear_k.weight"]
             if isinstance(lse2, tuple):                                           # MFMA path (see forward)
                 lse2, ctx2 = lse2                                                 # padded rows: finite outputs, zero dO -> delta = 0
-                dctx2 = torch.empty((B * N, hk), device=dev, dtype=BF16)
-                dv_ = dctx2.view(B, N, hk)
-                dv_[:, T:(T + 31) // 32 * 32].zero_()
-                dv_[:, :T] = da2.view(B, T, hk)
-                dfused = ops.attn_bwd(kvm, ctx2, dctx2, lse2, B, nh, hk, sc, drop=ds["cattn"], q_rows=T)   # kvm = the fused q|k|v buffer
-                dq2 = dfused.view(B, N, 3 * hk)[:, :T, :hk].reshape(B * T, hk)
-                dkvm = dfused[:, hk:]                                             # [B*N, 2hk] view, row stride 3hk
+                dq2, dkvm = EB.cross_attn_bwd(kvm, ctx2, lse2, da2, B, T, nh, hk, sc, drop=ds["cattn"])   # kvm = the fused q|k|v buffer
             else:
                 dq2 = torch.empty_like(q2)
                 dkvm = torch.empty_like(kvm)

@@ -12,6 +12,7 @@ backward: the explicit reverse; the gradient w.r.t. the image tokens (through bo
 backward's residual input and handed back to the caller, which adds the pooling gradient and continues into the encoder."""
 import torch
 
+from . import encoder_blocks as EB
 from . import ops
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -56,11 +57,7 @@ def forward(step, feat, pooled, pre, arena, n_img, save):
             # (dig_seq_attn_fwd / _bwd -- a thread per key -- took 257 / 426 us per launch here: 1.9 ms per step for 5 x 256 scores per head)
             kv = torch.empty((n_img * N, 3 * D), device=dev, dtype=BF16)
             ops.gemm(kn, _kv_view(M, sh, n["attn.linear_k.weight"]), n_img * N, 2 * D, D, out=kv[:, D:], ldc=3 * D)
-            fq = kv.view(n_img, N, 3 * D)[:, :, :D]
-            fq[:, nw:32].zero_()
-            fq[:, :nw] = (q * scale).view(n_img, nw, D)                 # (scale = 2^-3: exact in bf16)
-            ctx, lse = ops.attn_fwd(kv, n_img, H, D, q_rows=nw)
-            a = ctx.view(n_img, N, D)[:, :nw].reshape(n_img * nw, D)
+            a, ctx, lse = EB.cross_attn_fwd(kv, q, n_img, nw, H, D, scale)
             lse = (lse, ctx)
         else:
             kv = ops.linear_fwd(kn, _kv_view(M, sh, n["attn.linear_k.weight"]))
@@ -110,13 +107,7 @@ def backward(step, dout, pre, saved, n_img):
         da = ops.linear_dgrad(dy1, w16[n["attn.proj.weight"]])
         if isinstance(lse, tuple):                                       # MFMA path (see forward): kv = the fused q | k | v buffer
             lse_, ctx = lse
-            dctx = torch.empty((n_img * N, D), device=dev, dtype=BF16)
-            dv_ = dctx.view(n_img, N, D)
-            dv_[:, nw:32].zero_()
-            dv_[:, :nw] = da.view(n_img, nw, D)
-            dfused = ops.attn_bwd(kv, ctx, dctx, lse_, n_img, H, D, scale, q_rows=nw)
-            dq = dfused.view(n_img, N, 3 * D)[:, :nw, :D].reshape(n_img * nw, D)
-            dkv = dfused[:, D:]                                           # [n_img * N, 2 D] view, row stride 3 D
+            dq, dkv = EB.cross_attn_bwd(kv, ctx, lse_, da, n_img, nw, H, D, scale)
         else:
             dq = torch.empty_like(q)
             dkv = torch.empty_like(kv)

@@ -19,6 +19,7 @@ import types
 import torch
 
 from . import _lib as L
+from . import encoder_blocks as EB
 from . import ops
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -135,13 +136,13 @@ class RecModel(torch.nn.Module):
         sd = {k: v.to(dev) for k, v in self._sd.items()}
         D, d = self.D, self.d
         w = {}
+        blocks = w["enc_blocks"] = []                                   # per block, under the key names encoder_blocks reads
         for i in range(self.depth):
             b = f"encoder.blocks.{i}."
-            w[b] = dict(n1w=sd[b + "norm1.weight"], n1b=sd[b + "norm1.bias"], n2w=sd[b + "norm2.weight"], n2b=sd[b + "norm2.bias"],
-                        qkv=sd[b + "attn.qkv.weight"].to(BF16).contiguous(), proj=sd[b + "attn.proj.weight"].to(BF16).contiguous(),
-                        qkv_bias=torch.cat([sd[b + "attn.q_bias"], torch.zeros(D, device=dev), sd[b + "attn.v_bias"]]).contiguous(),
-                        proj_b=sd[b + "attn.proj.bias"], fc1=sd[b + "mlp.fc1.weight"].to(BF16).contiguous(), fc1_b=sd[b + "mlp.fc1.bias"],
-                        fc2=sd[b + "mlp.fc2.weight"].to(BF16).contiguous(), fc2_b=sd[b + "mlp.fc2.bias"])
+            blk = {k: sd[b + k] for k in ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")}
+            blk.update({k: sd[b + k].to(BF16).contiguous() for k in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")})
+            blk["qkv_bias"] = torch.cat([sd[b + "attn.q_bias"], torch.zeros(D, device=dev), sd[b + "attn.v_bias"]]).contiguous()
+            blocks.append(blk)
         w["pe_w"] = sd["encoder.patch_embed.proj.weight"].reshape(D, 48).contiguous()
         w["pe_b"] = sd["encoder.patch_embed.proj.bias"]
         w["mask_token"] = sd["encoder.mask_token"].reshape(D).contiguous()
@@ -175,16 +176,7 @@ class RecModel(torch.nn.Module):
         B = images.shape[0]
         zeros = torch.zeros((B, self.N), device=images.device, dtype=torch.uint8)
         x = ops.patch_embed_fwd(images.contiguous().float(), w["pe_w"], w["pe_b"], zeros, w["mask_token"], w["enc_pos"], D, self.gh, self.gw)
-        scale = (D // H) ** -0.5
-        for i in range(self.depth):
-            b = w[f"encoder.blocks.{i}."]
-            ln1, _, _ = ops.layernorm_fwd(x, b["n1w"], b["n1b"], 1e-6)
-            qkv = ops.linear_fwd(ln1, b["qkv"], bias=b["qkv_bias"], alpha=scale, alpha_cols=D)
-            ctx, _ = ops.attn_fwd(qkv, B, H, D)
-            x_mid = ops.linear_fwd(ctx, b["proj"], bias=b["proj_b"], resid=x)
-            ln2, _, _ = ops.layernorm_fwd(x_mid, b["n2w"], b["n2b"], 1e-6)
-            act = ops.linear_fwd(ln2, b["fc1"], bias=b["fc1_b"], act=1)
-            x = ops.linear_fwd(act, b["fc2"], bias=b["fc2_b"], resid=x_mid)
+        x, _, _ = EB.forward(EB.Plan(), w["enc_blocks"], x, B, H, 1e-6, False)              # the plain form, nothing kept
         y, _, _ = ops.layernorm_fwd(x, w["enc_nw"], w["enc_nb"], 1e-6)
         return y
 
