@@ -14,51 +14,14 @@ matrix -- round-off, as in the reference."""
 import torch
 
 from . import ops
+from .parallel import bn_backward, bn_forward
 
-BF16, F32 = torch.bfloat16, torch.float32
+BF16 = torch.bfloat16
 CONV_IDX = (0, 2, 4, 6)                 # positions of the conv3x3_blocks in ConvPatchNet.conv_layers (:217-225; max-pools at 1, 3, 5)
 
 
 def channels(D):
     return (D, D, int(D * 1.5), D * 2, D * 2)
-
-
-def _bn_fwd(step, h, key, arena_pre, relu, affine=True):
-    """BatchNorm (train) over the rows of h with this step's cross-rank statistics; running buffers updated.  Returns (y, mean, rstd)."""
-    M = step.m
-    f32 = M._f32
-    gamma = f32[f"{arena_pre}.{key}.weight"] if affine else None
-    beta = f32[f"{arena_pre}.{key}.bias"] if affine else None
-    rm, rv, i_bn = M._bn_views[f"{arena_pre}.{key}"]
-    rows, C = h.shape
-    from .engine_core import LOCAL
-    if step.comm is LOCAL and ops.bn_fused_supported(rows, C):
-        y, mean, rstd = ops.bn_fwd_fused(h, M.bn_eps, gamma, beta, relu=relu, running=(rm, rv, M.bn_momentum))
-    else:
-        sums = torch.empty((2, C), device=h.device, dtype=F32)
-        ops.bn_stats(h, sums)
-        step.comm.all_reduce_(sums)
-        y, mean, rstd = ops.bn_fwd_apply(h, sums, float(rows * step.comm.world), M.bn_eps, gamma, beta, relu=relu, running=(rm, rv, M.bn_momentum))
-    step._bn_touched.append(i_bn)
-    return y, mean, rstd
-
-
-def _bn_bwd(step, dy, h, mean, rstd, key, relu, affine=True):
-    M = step.m
-    f32, g32 = M._f32, M._g32
-    pre = "patch_extractor"
-    gamma = f32[f"{pre}.{key}.weight"] if affine else None
-    beta = f32[f"{pre}.{key}.bias"] if affine else None
-    dbeta = g32[f"{pre}.{key}.bias"] if affine else None
-    dgamma = g32[f"{pre}.{key}.weight"] if affine else None
-    rows, C = h.shape
-    from .engine_core import LOCAL
-    if step.comm is LOCAL and ops.bn_fused_supported(rows, C):
-        return ops.bn_bwd_fused(dy, h, mean, rstd, gamma, beta, relu, dbeta, dgamma)
-    sums = torch.empty((2, C), device=dy.device, dtype=F32)
-    ops.bn_bwd_stats(dy, h, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma)
-    step.comm.all_reduce_(sums)
-    return ops.bn_bwd_apply(dy, h, mean, rstd, gamma, beta, relu, sums, float(rows * step.comm.world))
 
 
 def _conv_gemm(a, w, rows, out_cols, bias=None):
@@ -83,7 +46,7 @@ def forward(step, feat, pre, arena, n_img, save):
         key = f"conv_layers.{i}"
         col = ops.im2col3x3(x, n_img, H, W, c[j])
         h = _conv_gemm(col, w16[f"{pre}.{key}.0.weight"], n_img * H * W, c[j + 1], bias=f32[f"{pre}.{key}.0.bias"])
-        a, mean, rstd = _bn_fwd(step, h, key + ".1", pre, relu=True)
+        a, mean, rstd = bn_forward(step, [h], [f"{pre}.{key}.1"], relu=True)[0]
         idx = None
         if j < 3:
             a, idx = ops.maxpool2x2_fwd(a, n_img, H, W, c[j + 1])
@@ -96,9 +59,9 @@ def forward(step, feat, pre, arena, n_img, save):
     ops.window_pool_fwd(x, g, n_img, H, W, nw, c[4])                       # adaptive_avg_pool2d((1, nw)) of the [1, 4] map, rows = (image, window)
     g = g.view(n_img, nw * c[4])
     z = ops.linear_fwd(g, w16[f"{pre}.patches2global.0.weight"], bias=f32[f"{pre}.patches2global.0.bias"])
-    a1, mean1, rstd1 = _bn_fwd(step, z, "patches2global.1", pre, relu=True)
+    a1, mean1, rstd1 = bn_forward(step, [z], [pre + ".patches2global.1"], relu=True)[0]
     z2 = ops.linear_fwd(a1, w16[f"{pre}.patches2global.3.weight"], bias=f32[f"{pre}.patches2global.3.bias"])
-    out, mean2, rstd2 = _bn_fwd(step, z2, "patches2global.4", pre, relu=False, affine=False)
+    out, mean2, rstd2 = bn_forward(step, [z2], [pre + ".patches2global.4"], relu=False, affine=False)[0]
     return out, ((layers, (H, W), g, z, mean1, rstd1, a1, z2, mean2, rstd2) if save else None)
 
 
@@ -112,10 +75,10 @@ def backward(step, dout, pre, saved, n_img):
     layers, (H, W), g, z, mean1, rstd1, a1, z2, mean2, rstd2 = saved
     side = lambda fn, *t: step._on_side(dev, fn, *t)                     # noqa: E731  (weight gradients / column sums: consumers only)
     p2g = f"{pre}.patches2global"
-    dz2 = _bn_bwd(step, dout, z2, mean2, rstd2, "patches2global.4", relu=False, affine=False)
+    dz2 = bn_backward(step, dout, z2, mean2, rstd2, p2g + ".4", relu=False, affine=False)
     side(lambda: (ops.linear_wgrad(dz2, a1, g32[p2g + ".3.weight"]), ops.colsum(dz2, g32[p2g + ".3.bias"])), dz2, a1)
     da1 = ops.linear_dgrad(dz2, w16[p2g + ".3.weight"])
-    dz = _bn_bwd(step, da1, z, mean1, rstd1, "patches2global.1", relu=True)
+    dz = bn_backward(step, da1, z, mean1, rstd1, p2g + ".1", relu=True)
     side(lambda: (ops.linear_wgrad(dz, g, g32[p2g + ".0.weight"]), ops.colsum(dz, g32[p2g + ".0.bias"])), dz, g)
     dg = ops.linear_dgrad(dz, w16[p2g + ".0.weight"])                    # [n_img, nw * 2 D]
     da = torch.empty((n_img * H * W, c[4]), device=dev, dtype=BF16)
@@ -126,7 +89,7 @@ def backward(step, dout, pre, saved, n_img):
         layers[j] = None
         if idx is not None:
             da = ops.maxpool2x2_bwd(da, idx, n_img, H, W, c[j + 1])
-        dh = _bn_bwd(step, da, h, mean, rstd, f"conv_layers.{CONV_IDX[j]}.1", relu=True)
+        dh = bn_backward(step, da, h, mean, rstd, key + ".1", relu=True)
         gw_ = g32[key + ".0.weight"].view(c[j + 1], c[j] * 9)
         side(lambda dh=dh, col=col, gw_=gw_, key=key, j=j: (ops.wgrad(dh, col, gw_, c[j + 1], c[j] * 9, dh.shape[0]),
                                                              ops.colsum(dh, g32[key + ".0.bias"])), dh, col)

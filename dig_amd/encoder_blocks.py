@@ -8,8 +8,9 @@ reverse -- for every caller: the pre-training step (engine_core._Step), the fine
   drops    per block (attention, proj-branch, MLP-branch) dropout.DropSpec, any of them None; None = no block drops anything
   on_side / block_done / grad_ready / mark   the caller's second-stream hand-over, keep-list release, bucket callback and phase marks
 
-The block-call path (one FFI crossing per block: engine_core._encoder_forward_calls / _encoder_backward_calls) is not here.  The two helpers
-at the end run a few-query cross-attention on the encoder's MFMA attention kernels (PatchNet, the recognition decoder)."""
+The block-call path (one FFI crossing per block, the pre-training step's default) is block_calls.forward / backward; its saved activations
+are read here as tensors.  The two helpers at the end run a few-query cross-attention on the encoder's MFMA attention kernels (PatchNet,
+the recognition decoder)."""
 from typing import NamedTuple
 
 import torch
@@ -43,7 +44,7 @@ class Plan(NamedTuple):
 
 
 def _tensors(s):
-    """A block's saved activations: the tuple forward() made, or the views of a block-call forward's buffers (engine_core._BlockSaved)."""
+    """A block's saved activations: the tuple forward() made, or the views of a block-call forward's buffers (block_calls._BlockSaved)."""
     return s if isinstance(s, tuple) else s.tensors()
 
 

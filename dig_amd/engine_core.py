@@ -8,6 +8,7 @@ fp32 gradient arena, per-stage callbacks so the data-parallel wrapper can start 
 parameter range while earlier layers are still in backward.
 """
 import ctypes
+import functools
 import itertools
 import os
 import weakref
@@ -15,8 +16,10 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import block_calls as BC
 from . import encoder_blocks as EB
 from . import ops
+from .parallel import LOCAL, LocalComm, bn_backward, bn_forward  # noqa: F401  (LocalComm: part of this module's interface)
 
 BF16, F32 = torch.bfloat16, torch.float32
 FWD_MODE = os.environ.get("DIG_FWD_MODE", "flip")                   # two-stream plan of the forward (single process): "flip" (default) or "side"
@@ -63,22 +66,6 @@ def _mark(name, dev):
         PHASE_MARKS.append((name, ev))
 
 
-class LocalComm:
-    world, rank = 1, 0
-
-    def all_reduce_(self, t):
-        return t
-
-    def all_gather_cat(self, t):
-        return t
-
-    def grad_ready(self, model, key):
-        pass
-
-
-LOCAL = LocalComm()
-
-
 class _EncWeights:
     """Per-encoder (online / momentum) accessors resolved once per arena binding."""
 
@@ -121,46 +108,6 @@ def _weights(model):
     return cache[1], cache[2]
 
 
-class _BlockSaved:
-    """What dig_encoder_block_fwd(save = 1) left for the backward of one block: two buffers (bf16 tensors, fp32 statistics) and the block's
-    input rows x / ln1 / mean / rstd, which live in the PREVIOUS block's buffers (or, for block 0, in tensors of their own).  The block-call
-    backward reads addresses (`ptr`); the per-entry-point backward asks for tensors()."""
-    __slots__ = ("b16", "b32", "off", "rows", "D", "F", "n_img", "heads", "inp", "inp_ptr")
-
-    def __init__(self, b16, b32, off, rows, D, F, n_img, heads, inp, inp_ptr):
-        self.b16, self.b32, self.off, self.rows, self.D, self.F, self.n_img, self.heads = b16, b32, off, rows, D, F, n_img, heads
-        self.inp = inp                   # keeps x, ln1, mu1, rs1 alive: 4 tensors (block 0) or the previous block's (b16, b32)
-        self.inp_ptr = inp_ptr           # their addresses: (x, ln1, mu1, rs1)
-
-    def ptr(self, name):
-        return (self.b32 if name in ("lse", "mu2", "rs2", "nmu", "nrs") else self.b16).data_ptr() + self.off[name]
-
-    def _v16(self, buf, base, byte_off, cols):
-        a = (byte_off - base) // 2
-        return buf[a:a + self.rows * cols].view(self.rows, cols)
-
-    def view(self, name):
-        R, D, F = self.rows, self.D, self.F
-        if name == "lse":
-            a = self.off["lse"] // 4
-            return self.b32[a:a + self.n_img * self.heads * 256].view(self.n_img * self.heads, 256)
-        if name in ("mu2", "rs2", "nmu", "nrs"):
-            a = self.off[name] // 4
-            return self.b32[a:a + R]
-        cols = {"qkv": 3 * D, "pre": F, "act": F}.get(name, D)
-        a = self.off[name] // 2
-        return self.b16[a:a + R * cols].view(R, cols)
-
-    def tensors(self):
-        """(x, ln1, mu1, rs1, qkv, ctx, lse, x_mid, ln2, mu2, rs2, pre, act) as tensors (views)."""
-        if len(self.inp) == 4:
-            x, ln1, mu1, rs1 = self.inp
-        else:
-            p = self.inp[2]
-            x, ln1, mu1, rs1 = p.view("out"), p.view("nln"), p.view("nmu"), p.view("nrs")
-        return (x, ln1, mu1, rs1) + tuple(self.view(k) for k in ("qkv", "ctx", "lse", "x_mid", "ln2", "mu2", "rs2", "pre", "act"))
-
-
 class _Step:
     def __init__(self, model):
         self._keep = []                             # tensors the side stream still reads (see _on_side)
@@ -197,209 +144,10 @@ class _Step:
         plan = EB.Plan(chain=chain, chain_ln=chain and ops.MLP_CHAIN_LN and M.F <= 2048,
                        attn_block=ops.attn_block_supported(H, D, B if views == 1 else None))
         if plan.chain_ln and ops.BLOCK_CALLS and D == H * 64 and path is None:
-            return self._encoder_forward_calls(ew, x, views * B, save, single_view=views == 1)
+            return BC.forward(ew.blocks, x, views * B, H, M.F, M.ln_eps, save, fuse_attn=plan.attn_block)
         drops = [ds and (None, ds[0], ds[1]) for ds in path] if path is not None else None
         x, saved, _ = EB.forward(plan, ew.blocks, x, views * B, H, M.ln_eps, save, drops=drops)
         return x, saved
-
-    def _encoder_forward_calls(self, ew, x, n_img, save, single_view=False):
-        """The block loop of encoder_forward with ONE FFI crossing per block (dig_encoder_block_fwd: qkv GEMM -> attention -> proj GEMM +
-        residual -> norm2 + MLP + residual + the next block's norm1) and two allocations per block (a bf16 buffer, an fp32 one) instead of
-        four crossings and thirteen allocations.  Same kernels, same arguments, same order: bit-identical to encoder_blocks.forward."""
-        M = self.m
-        D, Fh, H = M.D, M.F, M.H
-        R, dev = x.shape[0], x.device
-        off, n16, n32 = ops.block_fwd_layout(R, D, Fh, n_img, H, save)
-        blk0 = ew.blocks[0]
-        ln1, mu1, rs1 = ops.layernorm_fwd(x, blk0["norm1.weight"], blk0["norm1.bias"], M.ln_eps)
-        inp, inp_ptr = (x, ln1, mu1, rs1), (x.data_ptr(), ln1.data_ptr(), mu1.data_ptr(), rs1.data_ptr())
-        stream = ops.L.stream()
-        saved = []
-        nb_blocks = len(ew.blocks)
-        key = ("fwd_call", bool(save), R, n_img)
-        fuse_attn = int(ops.attn_block_supported(H, D, n_img if single_view else None))
-        prev = None
-        for i, blk in enumerate(ew.blocks):
-            st = blk.get(key)
-            if st is None:
-                nb = ew.blocks[i + 1] if i + 1 < nb_blocks else None
-                st = blk[key] = ops.BlockFwd(
-                    n_img=n_img, heads=H, D=D, F=Fh, rows=R, save=int(bool(save)),
-                    tile_qkv=ops.fwd_tile_code(R, 3 * D, D) or ops.GEMM_BK_FWD, tile_proj=ops.fwd_tile_code(R, D, D, has_resid=True) or ops.GEMM_BK_FWD,
-                    fuse_attn=fuse_attn, eps=M.ln_eps, scale=(D // H) ** -0.5,
-                    qkv_w=blk["attn.qkv.weight"].data_ptr(), qkv_b=blk["qkv_bias"].data_ptr(), proj_w=blk["attn.proj.weight"].data_ptr(),
-                    proj_b=blk["attn.proj.bias"].data_ptr(), n2_g=blk["norm2.weight"].data_ptr(), n2_b=blk["norm2.bias"].data_ptr(),
-                    fc1_w=blk["mlp.fc1.weight"].data_ptr(), fc1_b=blk["mlp.fc1.bias"].data_ptr(), fc2_w=blk["mlp.fc2.weight"].data_ptr(),
-                    fc2_b=blk["mlp.fc2.bias"].data_ptr(), next_n1_g=nb["norm1.weight"].data_ptr() if nb else None,
-                    next_n1_b=nb["norm1.bias"].data_ptr() if nb else None)
-            b16 = torch.empty(n16 // 2, device=dev, dtype=BF16)
-            b32 = torch.empty(n32 // 4, device=dev, dtype=F32)
-            p16, p32 = b16.data_ptr(), b32.data_ptr()
-            st.fuse_attn = fuse_attn                                  # (a switch, like fuse_ln2 / wg_defer of the backward: read on every call)
-            st.x, st.ln1 = inp_ptr[0], inp_ptr[1]
-            st.qkv, st.ctx, st.x_mid, st.out, st.nln = p16 + off["qkv"], p16 + off["ctx"], p16 + off["x_mid"], p16 + off["out"], p16 + off["nln"]
-            st.lse = p32 + off["lse"]
-            if save:
-                st.ln2, st.pre, st.act = p16 + off["ln2"], p16 + off["pre"], p16 + off["act"]
-                st.mu2, st.rs2, st.nmu, st.nrs = p32 + off["mu2"], p32 + off["rs2"], p32 + off["nmu"], p32 + off["nrs"]
-            ops.L.call("dig_encoder_block_fwd", ctypes.byref(st), stream)
-            cur = _BlockSaved(b16, b32, off, R, D, Fh, n_img, H, inp, inp_ptr)
-            if save:
-                saved.append(cur)
-                inp, inp_ptr = (b16, b32, cur), (p16 + off["out"], p16 + off["nln"], p32 + off["nmu"], p32 + off["nrs"])
-            else:
-                inp, inp_ptr = (b16, b32), (p16 + off["out"], p16 + off["nln"], 0, 0)     # (no chain of blocks: the previous buffers go back to the pool)
-            prev = cur
-        return prev.view("out"), saved
-
-    def _encoder_backward_calls(self, ew, saved, dx, wT, plan, n_img, R):
-        """The block loop of encoder_backward with ONE FFI crossing per block (dig_encoder_block_bwd: the data-gradient chain with the grouped
-        weight gradients in it on this stream, the five parameter-gradient reductions on the side stream behind one event) and two
-        allocations per block.  Same kernels, same arguments, same order as encoder_blocks.backward.  Returns the gradient w.r.t. the
-        patch embedding's output rows."""
-        M = self.m
-        D, Fh, H = M.D, M.F, M.H
-        dev = dx.device
-        main, side = self._streams(dev)
-        off, n16, n32 = ops.block_bwd_layout(R, D, Fh, n_img)
-        grp = plan["group"]
-        stream, side_h = ops.L.stream(), ctypes.c_void_p(side.cuda_stream)
-        probs = ((ops._WgProb * 4)(), (ops._WgProb * 4)())
-        wmap_ptr = plan["wmap"].data_ptr()
-        tile = ops.dgrad_tile_code(R, D) or ops.GEMM_BK_BWD
-        tile_direct = ops.dgrad_direct_tile_code(R, D)
-        key = ("bwd_call", R, n_img)
-        dy_ptr, dy_owner = dx.data_ptr(), dx
-        prev_block, n_launch, slabs_prev = None, 0, None
-        deferred = []                                                    # deferred plan: (problem table, temporaries kept alive) per block
-        defer = WGRAD_DEFER == "1" or (WGRAD_DEFER == "auto" and self.comm is LOCAL and self._defer_fits(dev, M.depth * n16))
-        red_defer = bool(RED_DEFER and defer and self.comm is LOCAL and ops.MLP_CHAIN_LNB and M.depth * 9 <= ops.COLSUM_MAX_SEGS)
-        red_segs, red_keep = [], []                                      # (partials address, destination, stride, partial rows, columns) of the held-back reductions
-        lib = ops.L.lib()
-        n_b, n_l2, n_l1 = lib.dig_mlp_chain_colsum_rows(R), lib.dig_mlp_chain_ln_parts(R), lib.dig_layernorm_bwd_parts(R)
-        for i in reversed(range(M.depth)):
-            blk, g, sv = ew.blocks[i], ew.blocks[i]["g"], saved[i]
-            saved[i] = None
-            st = blk.get(key)
-            if st is None:
-                gb = g["qkv_bias"]
-                for k in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"):
-                    assert g[k].is_contiguous()
-                st = blk[key] = ops.BlockBwd(
-                    n_img=n_img, heads=H, D=D, F=Fh, rows=R, tile_dgrad=tile, scale=(D // H) ** -0.5,
-                    qkv_w=blk["attn.qkv.weight"].data_ptr(), proj_w=blk["attn.proj.weight"].data_ptr(),
-                    n1_g=blk["norm1.weight"].data_ptr(), n1_b=blk["norm1.bias"].data_ptr(), n2_g=blk["norm2.weight"].data_ptr(),
-                    n2_b=blk["norm2.bias"].data_ptr(),
-                    g_n1_g=g["norm1.weight"].data_ptr(), g_n1_b=g["norm1.bias"].data_ptr(), g_qkv_w=g["attn.qkv.weight"].data_ptr(),
-                    g_q_b=gb.data_ptr(), g_v_b=gb[2 * D:].data_ptr(), g_proj_w=g["attn.proj.weight"].data_ptr(),
-                    g_proj_b=g["attn.proj.bias"].data_ptr(), g_n2_g=g["norm2.weight"].data_ptr(), g_n2_b=g["norm2.bias"].data_ptr(),
-                    g_fc1_w=g["mlp.fc1.weight"].data_ptr(), g_fc1_b=g["mlp.fc1.bias"].data_ptr(), g_fc2_w=g["mlp.fc2.weight"].data_ptr(),
-                    g_fc2_b=g["mlp.fc2.bias"].data_ptr(),
-                    wg_fn=plan["fn"], wg_wa=plan["wa"], wg_splits=plan["splits"], wg_n_wg=plan["n_wg"], wg_fold_splits=plan["splits"],
-                    wg_trans=(ctypes.c_int * 4)(*plan["trans"]))
-            w2t, w1t, projt, qkvt = wT[i]
-            st.w2t, st.w1t = w2t.data_ptr(), w1t.data_ptr()
-            st.projt = projt.data_ptr() if (ops.MLP_CHAIN_LNB and ops.MLP_CHAIN_PROJ) else None
-            st.tile_direct = tile_direct                              # (a switch: read on every call)
-            st.attn_proj = int(ops.ATTN_BWD_PROJ and ops.attn_bwd_proj_supported(D) and not ops.attn_bwd_mode())   # (a switch, read on every call)
-            st.proj_wt = projt.data_ptr() if (tile_direct or st.attn_proj) else None
-            st.qkv_wt = qkvt.data_ptr() if tile_direct else None
-            st.x, st.ln1, st.mu1, st.rs1 = sv.inp_ptr
-            for k in ("qkv", "ctx", "lse", "x_mid", "ln2", "mu2", "rs2", "pre", "act"):
-                setattr(st, k, sv.ptr(k))
-            t16 = torch.empty(n16 // 2, device=dev, dtype=BF16)
-            t32 = torch.empty(n32 // 4, device=dev, dtype=F32)
-            p16, p32 = t16.data_ptr(), t32.data_ptr()
-            st.dy = dy_ptr
-            st.dln2, st.dpre, st.dctx, st.dqkv = p16 + off["dln2"], p16 + off["dpre"], p16 + off["dctx"], p16 + off["dqkv"]
-            st.bparts, st.ws1, st.ws2, st.qs, st.vs = p32 + off["bparts"], p32 + off["ws1"], p32 + off["ws2"], p32 + off["qs"], p32 + off["vs"]
-            slabs = grp._slabs(plan["slab_bytes"])
-            grp.set ^= 1
-            st.wg_map, st.wg_slabs = wmap_ptr, slabs.data_ptr()
-            st.wg_defer = int(defer)
-            st.fuse_ln2 = int(ops.MLP_CHAIN_LNB)
-            st.defer_red = int(red_defer)
-            if red_defer:
-                # what dig_encoder_block_bwd would have launched on the second stream (csrc/encoder_block.inc), as segments of one launch
-                gb = g["qkv_bias"]
-                red_segs.append((st.bparts, g["mlp.fc1.bias"], Fh, n_b, Fh))
-                for k, dst in enumerate((g["norm2.weight"], g["norm2.bias"], g["mlp.fc2.bias"])):
-                    red_segs.append((st.ws2 + 4 * k * D, dst, 3 * D, n_l2, D))
-                red_segs.append((st.qs, gb[:D], D, n_img, D))
-                red_segs.append((st.vs, gb[2 * D:], D, n_img, D))
-                for k, dst in enumerate((g["norm1.weight"], g["norm1.bias"], g["attn.proj.bias"])):
-                    red_segs.append((st.ws1 + 4 * k * D, dst, 3 * D, n_l1, D))
-                red_keep.append(t32)
-            if defer:
-                own = (ops._WgProb * 4)()
-                deferred.append((own, t16, sv, i))
-                st.wg_probs = ctypes.addressof(own)
-                st.wg_fold_n = 0
-                st.wg_fold_probs = st.wg_fold_slabs = None
-                st.side = side_h
-                ops.L.call("dig_encoder_block_bwd", ctypes.byref(st), stream)
-                if side is not main and not red_defer:
-                    self._keep.append(t32)
-                dy_ptr, dy_owner = p16 + off["dctx"], t16
-                self._mark_kept(dev)
-                self._release_kept(dev)
-                continue
-            st.wg_probs = ctypes.addressof(probs[n_launch & 1])
-            st.wg_fold_n = 4 if n_launch else 0
-            st.wg_fold_probs = ctypes.addressof(probs[(n_launch & 1) ^ 1]) if n_launch else None
-            st.wg_fold_slabs = slabs_prev.data_ptr() if n_launch else None
-            st.side = side_h
-            ops.L.call("dig_encoder_block_bwd", ctypes.byref(st), stream)
-            n_launch += 1
-            slabs_prev = slabs
-            if side is not main:
-                self._keep.append(t32)                                   # the side stream's reductions read it
-            dy_ptr, dy_owner = p16 + off["dctx"], t16                    # the next block's incoming gradient lives in this block's buffer
-            del sv
-            self._mark_kept(dev)
-            self._release_kept(dev)
-            # (block i's slabs are folded by the NEXT launch, so the bucket that is final here is block i + 1's)
-            if prev_block is not None:
-                self._grad_ready(dev, f"encoder.blocks.{prev_block}")
-            prev_block = i
-        if red_segs:
-            # every block's bias / LayerNorm partial rows in one launch, on this stream, in front of the weight gradients (nothing runs beside it)
-            segs = (ops._ColsumSeg * len(red_segs))(*[ops._ColsumSeg(int(p_), d_.data_ptr(), st_, n_, c_) for p_, d_, st_, n_, c_ in red_segs])
-            ops.L.call("dig_colsum_partials_multi", segs, len(red_segs), stream)
-            del red_keep
-        if defer:
-            # the twelve launches now, in block order (each folds its predecessor's slabs), every bucket behind its fold
-            prev_probs = None
-            for own, _t16, _sv, i in deferred:
-                slabs = grp._slabs(plan["slab_bytes"])
-                grp.set ^= 1
-                ops.L.call("dig_wgrad_group", ctypes.addressof(own), 4, ctypes.addressof(prev_probs) if prev_probs is not None else None,
-                           4 if prev_probs is not None else 0, int(R), plan["splits"], wmap_ptr, plan["n_wg"], ops.L.ptr(slabs),
-                           ops.L.ptr(slabs_prev) if slabs_prev is not None else None, plan["splits"], plan["fn"], plan["wa"], stream)
-                if prev_block is not None:
-                    self._grad_ready(dev, f"encoder.blocks.{prev_block}")
-                prev_probs, slabs_prev, prev_block = own, slabs, i
-            probs = (prev_probs, prev_probs)
-            n_launch = 1
-        # fold of the last launch's slabs (a fold-only launch), then the last bucket
-        ops.L.call("dig_wgrad_group", None, 0, ctypes.addressof(probs[(n_launch & 1) ^ 1]), 4, int(R), 1, None, ops.WGRAD_GROUP_SLOTS, None,
-                   ops.L.ptr(slabs_prev), plan["splits"], plan["fn"], plan["wa"], stream)
-        if prev_block is not None:
-            self._grad_ready(dev, f"encoder.blocks.{prev_block}")
-        a = off["dctx"] // 2
-        return dy_owner[a:a + R * D].view(R, D)
-
-    def _defer_fits(self, dev, extra_bytes):
-        """The deferred weight-gradient plan keeps `extra_bytes` of gradient temporaries (and every block's saved activations) alive until
-        the end of the backward: taken only while that leaves three quarters of what the device (and torch's pool) has free.  The answer
-        is cached per size: one hipMemGetInfo per new shape, not per step."""
-        cache = self.m.__dict__.setdefault("_defer_fits_cache", {})
-        key = (dev.index, extra_bytes)
-        if key not in cache:
-            free, _ = torch.cuda.mem_get_info(dev)
-            pooled = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-            cache[key] = extra_bytes <= (free + pooled) // 4
-        return cache[key]
 
     def mlp_weight_transposes(self, ew, fresh=False):
         """K-contiguous copies of the MLP weights for the fused backward (W2^T [F, D], W1^T [D, F]; 1.2 MB each) and of the projection weight.
@@ -479,7 +227,7 @@ class _Step:
         """The per-entry-point backward's plan (encoder_blocks.Plan) from this module's and ops' switches as they stand NOW.
         Grouped weight gradients: shapes the grouped kernel does not take (tiny test models) keep the per-layer launches.  red_defer: single
         process (the 512-wide model, single-view encoders): the blocks' bias / LayerNorm column-sum launches held back as in
-        _encoder_backward_calls -- collected over ALL blocks and folded in one dig_colsum_partials_multi launch behind the walk."""
+        the block-call backward -- collected over ALL blocks and folded in one dig_colsum_partials_multi launch behind the walk."""
         D, Fh = self.m.D, self.m.F
         grouped = (ops.WGRAD_GROUP and WGRAD_GROUPING != "off" and
                    all(ops.wgrad_group_route(o, i_, rows) is not None for o, i_ in ((Fh, D), (D, Fh), (3 * D, D), (D, D))))
@@ -490,13 +238,24 @@ class _Step:
                        grouping=WGRAD_GROUPING if grouped else "off", inline=WGRAD_INLINE, batch_reduce=BATCH_REDUCE,
                        red_defer=bool(RED_DEFER and self.comm is LOCAL and path is None and not BATCH_REDUCE and PHASE_MARKS is None))
 
+    def _block_call_plan(self, dev, n_img, R):
+        """The block-call backward's plan (block_calls.Plan) from this module's and ops' switches as they stand NOW.  defer "auto": see
+        WGRAD_DEFER -- a single process, and the device has the memory for what the deferred plan keeps alive."""
+        M, local = self.m, self.comm is LOCAL
+        kept = M.depth * ops.block_bwd_layout(R, M.D, M.F, n_img)[1]
+        defer = WGRAD_DEFER == "1" or (WGRAD_DEFER == "auto" and local and BC.defer_fits(M.__dict__.setdefault("_defer_fits_cache", {}), dev, kept))
+        return BC.Plan(defer=defer, red_defer=bool(RED_DEFER and defer and local and ops.MLP_CHAIN_LNB and M.depth * 9 <= ops.COLSUM_MAX_SEGS),
+                       tile_direct=ops.dgrad_direct_tile_code(R, M.D),
+                       attn_proj=bool(ops.ATTN_BWD_PROJ and ops.attn_bwd_proj_supported(M.D) and not ops.attn_bwd_mode()),
+                       fuse_ln2=bool(ops.MLP_CHAIN_LNB), chain_proj=bool(ops.MLP_CHAIN_LNB and ops.MLP_CHAIN_PROJ))
+
     @staticmethod
     def _takes_block_calls(plan, path, saved, dx):
-        """Whether the block-call backward (_encoder_backward_calls) computes what `plan` asks for: it is the default plan -- one grouped launch
+        """Whether the block-call backward (block_calls.backward) computes what `plan` asks for: it is the default plan -- one grouped launch
         per block in the chain, the fused MLP backward in every block, fused q / v bias sums -- without stochastic depth, batched reductions
         or phase marks, behind a block-call forward."""
         return (ops.BLOCK_CALLS and plan.grouping == "block" and plan.inline and plan.chain_bwd and plan.chain_every == 1 and plan.fused_qv
-                and path is None and not plan.batch_reduce and PHASE_MARKS is None and all(isinstance(s_, _BlockSaved) for s_ in saved)
+                and path is None and not plan.batch_reduce and PHASE_MARKS is None and all(isinstance(s_, BC._BlockSaved) for s_ in saved)
                 and dx.is_contiguous())
 
     def encoder_backward(self, ew, saved, dx, images, aug, mask_u8, views=2):
@@ -519,24 +278,22 @@ class _Step:
                     t.record_stream(main)
         path = getattr(self, "path_on", None)
         plan = self._backward_plan(chain, wT is not None, R, path)
-        blocks_done = False
-        if self._takes_block_calls(plan, path, saved, dx):
-            wplan = ops.wgrad_block_plan(dev, R, D, M.F)
-            if wplan is not None:
-                dx = self._encoder_backward_calls(ew, saved, dx, wT, wplan, n_img, R)
-                blocks_done = True                                       # only the patch embedding is left
-        if not blocks_done:
-            def on_side(fn, *tensors):
-                self._on_side(dev, fn, *tensors)
+        grad_ready = functools.partial(self._grad_ready, dev)
 
-            def block_done():
-                self._mark_kept(dev)
-                self._release_kept(dev)
+        def block_done():
+            self._mark_kept(dev)
+            self._release_kept(dev)
+        wplan = ops.wgrad_block_plan(dev, R, D, M.F) if self._takes_block_calls(plan, path, saved, dx) else None
+        if wplan is not None:
+            dx = BC.backward(self._block_call_plan(dev, n_img, R), ew.blocks, saved, dx, wT, wplan, n_img, H, M.F,
+                             ctypes.c_void_p(side.cuda_stream), keep=self._keep.append if side is not main else None,
+                             block_done=block_done, grad_ready=grad_ready)
+        else:
             drops = [ds and (None, ds[0], ds[1]) for ds in path] if path is not None else None
             # views == 1: only view 0 carries a gradient (zero contrastive weight): rows [0, B*N) of everything.  A bucket's all-reduce is issued
             # from the side stream after it has waited for the main chain (_grad_ready), so the main chain never stalls on the collective
-            dx = EB.backward(plan, ew.blocks, saved, dx, wT, n_img, H, on_side, drops=drops, rows=R if views == 1 else None,
-                             block_done=block_done, grad_ready=lambda key: self._grad_ready(dev, key), mark=_mark)
+            dx = EB.backward(plan, ew.blocks, saved, dx, wT, n_img, H, functools.partial(self._on_side, dev), drops=drops, rows=R if views == 1 else None,
+                             block_done=block_done, grad_ready=grad_ready, mark=_mark)
         for half, im in enumerate((images, aug)[:views]):
             ops.patch_embed_bwd_mfma(dx[half * B * N:(half + 1) * B * N], im, mask_u8[half * B:(half + 1) * B], ew.g_pe_w, ew.g_pe_b,
                                      ew.g_mask_token, D, M.gh, M.gw)
@@ -549,25 +306,12 @@ class _Step:
         -> ReLU ... ; the last BN has no affine parameters."""
         M = self.m
         dims = M.mlps[pre]
-        w16, f32 = M._w(arena), M._f32
-        n_local = x.shape[0]
-        n_total = float(n_local * self.comm.world)
+        w16 = M._w(arena)
         saved = []
-        for l, (d1, d2) in enumerate(dims):
+        for l in range(len(dims)):
             last = l == len(dims) - 1
             h = ops.linear_fwd(x, w16[f"{pre}.{3 * l}.weight"])
-            gamma = None if last else f32[f"{pre}.{3 * l + 1}.weight"]
-            beta = None if last else f32[f"{pre}.{3 * l + 1}.bias"]
-            rm, rv, i_bn = M._bn_views[f"{pre}.{3 * l + 1}"]
-            if self.comm is LOCAL and ops.bn_fused_supported(n_local, d2):
-                # a single rank: nothing sits between statistics and apply -- a few-row layer (the heads on 8 B pooled rows) is one launch
-                y, mean, rstd = ops.bn_fwd_fused(h, M.bn_eps, gamma, beta, relu=not last, running=(rm, rv, M.bn_momentum))
-            else:
-                sums = torch.empty((2, d2), device=x.device, dtype=F32)
-                ops.bn_stats(h, sums)
-                self.comm.all_reduce_(sums)
-                y, mean, rstd = ops.bn_fwd_apply(h, sums, n_total, M.bn_eps, gamma, beta, relu=not last, running=(rm, rv, M.bn_momentum))
-            self._bn_touched.append(i_bn)
+            y, mean, rstd = bn_forward(self, [h], [f"{pre}.{3 * l + 1}"], relu=not last, affine=not last)[0]
             if save:
                 saved.append((x, h, mean, rstd))
             x = y
@@ -581,24 +325,13 @@ class _Step:
         M = self.m
         dims = M.mlps[pre_a]
         assert dims == M.mlps[pre_b]
-        f32 = M._f32
-        outs = []
         xs = [xa, xb]
         saved = [[], []]
-        for l, (d1, d2) in enumerate(dims):
+        for l in range(len(dims)):
             last = l == len(dims) - 1
             hs = [ops.linear_fwd(xs[k], M._w(ar)[f"{pre}.{3 * l}.weight"]) for k, (pre, ar) in enumerate(((pre_a, arena_a), (pre_b, arena_b)))]
-            sums = torch.empty((2, 2, d2), device=xa.device, dtype=F32)
-            for k in range(2):
-                ops.bn_stats(hs[k], sums[k])
-            self.comm.all_reduce_(sums)
-            for k, (pre, save) in enumerate(((pre_a, save_a), (pre_b, save_b))):
-                n_total = float(xs[k].shape[0] * self.comm.world)
-                gamma = None if last else f32[f"{pre}.{3 * l + 1}.weight"]
-                beta = None if last else f32[f"{pre}.{3 * l + 1}.bias"]
-                rm, rv, i_bn = M._bn_views[f"{pre}.{3 * l + 1}"]
-                y, mean, rstd = ops.bn_fwd_apply(hs[k], sums[k], n_total, M.bn_eps, gamma, beta, relu=not last, running=(rm, rv, M.bn_momentum))
-                self._bn_touched.append(i_bn)
+            outs = bn_forward(self, hs, [f"{pre}.{3 * l + 1}" for pre in (pre_a, pre_b)], relu=not last, affine=not last)
+            for k, (save, (y, mean, rstd)) in enumerate(zip((save_a, save_b), outs)):
                 if save:
                     saved[k].append((xs[k], hs[k], mean, rstd))
                 xs[k] = y
@@ -607,24 +340,11 @@ class _Step:
     def mlp_backward(self, dy, pre, saved, need_dx=True, dx_out=None):
         M = self.m
         dims = M.mlps[pre]
-        w16, f32, g32 = M._w("online"), M._f32, M._g32
-        n_total = float(saved[0][0].shape[0] * self.comm.world)
+        w16, g32 = M._w("online"), M._g32
         for l in reversed(range(len(dims))):
-            d1, d2 = dims[l]
             last = l == len(dims) - 1
             x, h, mean, rstd = saved[l]
-            gamma = None if last else f32[f"{pre}.{3 * l + 1}.weight"]
-            beta = None if last else f32[f"{pre}.{3 * l + 1}.bias"]
-            if self.comm is LOCAL and ops.bn_fused_supported(h.shape[0], d2):
-                dh = ops.bn_bwd_fused(dy, h, mean, rstd, gamma, beta, not last, None if last else g32[f"{pre}.{3 * l + 1}.bias"],
-                                      None if last else g32[f"{pre}.{3 * l + 1}.weight"])
-            else:
-                sums = torch.empty((2, d2), device=dy.device, dtype=F32)
-                # (the LOCAL sums are the affine gradients: accumulated by the statistics launch itself)
-                ops.bn_bwd_stats(dy, h, mean, rstd, gamma, beta, not last, sums, None if last else g32[f"{pre}.{3 * l + 1}.bias"],
-                                 None if last else g32[f"{pre}.{3 * l + 1}.weight"])
-                self.comm.all_reduce_(sums)
-                dh = ops.bn_bwd_apply(dy, h, mean, rstd, gamma, beta, not last, sums, n_total)
+            dh = bn_backward(self, dy, h, mean, rstd, f"{pre}.{3 * l + 1}", relu=not last, affine=not last)
             # (every head weight is used once per forward: right after zero_grad() its gradient can be written instead of added)
             asg = getattr(self, "_assign", False)
             self._on_side(dy.device, lambda: ops.linear_wgrad(dh, x, g32[f"{pre}.{3 * l}.weight"], assign=asg), dh, x)

@@ -2,6 +2,7 @@
 kernels on the caller's current stream; nothing here computes on the host or falls back to ATen."""
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
@@ -559,27 +560,40 @@ class WgradGroup:
                              A.stride(0) if A is not None else 0, B.stride(0) if B is not None else 0, dw.stride(0), I, J, trans)
         return arr
 
+    def next_slabs(self, nbytes):
+        """The slab set the next launch writes.  The two sets alternate: a launch fills one while it folds the other."""
+        slabs = self._slabs(nbytes)
+        self.set ^= 1
+        return slabs
+
+    def call(self, probs, n, fold_probs, fold_n, splits, wmap, n_wg, slabs, fold_slabs, fold_splits):
+        """One dig_wgrad_group call on problem tables (_WgProb arrays or their addresses): the partial products of `probs` into `slabs` and
+        the fold of `fold_slabs`, which the launch of `fold_probs` left.  Either half may be empty (None, 0)."""
+        L.call("dig_wgrad_group", probs, n, fold_probs, fold_n, int(self.rows), splits, L.ptr(wmap), n_wg, L.ptr(slabs), L.ptr(fold_slabs), fold_splits,
+               self.fn, WGRAD_GROUP_WA, L.stream())
+
+    def fold(self, probs, n, slabs, splits):
+        """The fold-only launch that ends a backward: `slabs` of the last launch (its table `probs`) summed into the gradient tensors."""
+        self.call(None, 0, probs, n, 1, None, WGRAD_GROUP_SLOTS, None, slabs, splits)
+
     def launch(self):
         """Partial products of everything add()ed since the last launch + the fold of the previous launch's slabs."""
         if not self.cur and self.pending is None:
             return
-        fn = self.fn
-        tj = 128 * fn
-        wa = WGRAD_GROUP_WA
+        fn, wa = self.fn, WGRAD_GROUP_WA
         tiles = [L.lib().dig_wgrad_group_tiles(int(dw.shape[1] if t else dw.shape[0]), int(dw.shape[0] if t else dw.shape[1]), fn, wa)
                  for _, _, dw, t in self.cur]
         if self.cur:
             splits, n_wg, wmap = self._plan(tiles)
-            slabs = self._slabs(sum(tiles) * splits * 128 * wa * tj * 4)
+            slabs = self.next_slabs(sum(tiles) * splits * 128 * wa * 128 * fn * 4)
         else:
             splits, n_wg, wmap, slabs = 1, WGRAD_GROUP_SLOTS, None, None
-        pend = self.pending
-        L.call("dig_wgrad_group", self._structs(self.cur), len(self.cur), self._structs(pend[0]) if pend else None, len(pend[0]) if pend else 0,
-               int(self.rows), splits, L.ptr(wmap), n_wg, L.ptr(slabs), L.ptr(pend[1]) if pend else None, pend[2] if pend else 1, fn, wa, L.stream())
+        items, fold_slabs, fold_splits = self.pending or ([], None, 1)
+        self.call(self._structs(self.cur), len(self.cur), self._structs(items) if items else None, len(items), splits, wmap, n_wg, slabs,
+                  fold_slabs, fold_splits)
         # the fold list keeps the gradient tensors only (operands are dead once this launch has run)
         self.pending = ([(None, None, dw, t) for _, _, dw, t in self.cur], slabs, splits) if self.cur else None
         self.cur = []
-        self.set ^= 1
 
     def flush(self):
         """Fold what the last launch left (a fold-only launch); afterwards every gradient add()ed so far is final on this stream."""
@@ -655,10 +669,13 @@ def block_bwd_layout(rows, D, Fh, n_img):
     return lay
 
 
+# (wmap: on the device; trans: one flag per problem; group: the WgradGroup whose slab sets the launches alternate between)
+WgradBlockPlan = namedtuple("WgradBlockPlan", "fn wa splits n_wg wmap trans group slab_bytes")
+
+
 def wgrad_block_plan(dev, rows, D, Fh):
-    """The grouped weight-gradient launch of one encoder block (fc2, fc1, proj, qkv) for dig_encoder_block_bwd: None when a shape cannot
-    join, else a dict with fn, wa, splits, n_wg, wmap (device tensor), slab_bytes, trans (one flag per problem) and `group` (the WgradGroup
-    whose slab sets the launches alternate between)."""
+    """The grouped weight-gradient launch of one encoder block (fc2, fc1, proj, qkv) for dig_encoder_block_bwd: a WgradBlockPlan, or None when
+    a shape cannot join."""
     grp = WgradGroup(dev)
     grp.rows = rows
     trans, tiles = [], []
@@ -670,8 +687,7 @@ def wgrad_block_plan(dev, rows, D, Fh):
         trans.append(t)
         tiles.append(L.lib().dig_wgrad_group_tiles(int(in_dim if t else out_dim), int(out_dim if t else in_dim), grp.fn, WGRAD_GROUP_WA))
     splits, n_wg, wmap = grp._plan(tiles)
-    return {"fn": grp.fn, "wa": WGRAD_GROUP_WA, "splits": splits, "n_wg": n_wg, "wmap": wmap, "trans": trans, "group": grp,
-            "slab_bytes": sum(tiles) * splits * 128 * WGRAD_GROUP_WA * 128 * grp.fn * 4}
+    return WgradBlockPlan(grp.fn, WGRAD_GROUP_WA, splits, n_wg, wmap, trans, grp, sum(tiles) * splits * 128 * WGRAD_GROUP_WA * 128 * grp.fn * 4)
 
 
 _ws2 = {}

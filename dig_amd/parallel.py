@@ -15,6 +15,64 @@ Replaces the reference's SyncBatchNorm.convert + DistributedDataParallel pair (r
 import torch
 import torch.distributed as dist
 
+from . import ops
+
+
+class LocalComm:
+    world, rank = 1, 0
+
+    def all_reduce_(self, t):
+        return t
+
+    def all_gather_cat(self, t):
+        return t
+
+    def grad_ready(self, model, key):
+        pass
+
+
+LOCAL = LocalComm()
+
+
+# ---- a train-mode BatchNorm layer (SyncBatchNorm semantics) for a step object: .m (the model), .comm, ._bn_touched (running buffers written)
+def bn_forward(step, hs, names, relu, affine=True):
+    """BatchNorm (train) over the rows of every matrix in hs with this step's cross-rank statistics; running buffers updated.  names: the
+    layers' parameter prefixes.  Several matrices (the lock-step stacks of mlp_forward_pair) share ONE all-reduce: [len(hs), 2, C].
+    Returns [(y, mean, rstd)]."""
+    M = step.m
+    rows, C = hs[0].shape
+    # a single rank: nothing sits between statistics and apply -- a few-row layer (the heads on 8 B pooled rows) is one launch
+    fused = step.comm is LOCAL and len(hs) == 1 and ops.bn_fused_supported(rows, C)
+    if not fused:
+        sums = torch.empty((len(hs), 2, C), device=hs[0].device, dtype=torch.float32)
+        for h, s in zip(hs, sums):
+            ops.bn_stats(h, s)
+        step.comm.all_reduce_(sums)
+    out = []
+    for k, (h, name) in enumerate(zip(hs, names)):
+        gamma, beta = (M._f32[name + ".weight"], M._f32[name + ".bias"]) if affine else (None, None)
+        rm, rv, i_bn = M._bn_views[name]
+        running = (rm, rv, M.bn_momentum)
+        out.append(ops.bn_fwd_fused(h, M.bn_eps, gamma, beta, relu=relu, running=running) if fused else
+                   ops.bn_fwd_apply(h, sums[k], float(h.shape[0] * step.comm.world), M.bn_eps, gamma, beta, relu=relu, running=running))
+        step._bn_touched.append(i_bn)
+    return out
+
+
+def bn_backward(step, dy, h, mean, rstd, name, relu, affine=True):
+    """The reverse of one bn_forward layer: returns d h; the affine gradients are accumulated into the gradient arena."""
+    M = step.m
+    gamma, dgamma = (M._f32[name + ".weight"], M._g32[name + ".weight"]) if affine else (None, None)
+    beta, dbeta = (M._f32[name + ".bias"], M._g32[name + ".bias"]) if affine else (None, None)
+    rows, C = h.shape
+    if step.comm is LOCAL and ops.bn_fused_supported(rows, C):
+        return ops.bn_bwd_fused(dy, h, mean, rstd, gamma, beta, relu, dbeta, dgamma)
+    sums = torch.empty((2, C), device=dy.device, dtype=torch.float32)
+    # (the LOCAL sums are the affine gradients: accumulated by the statistics launch itself)
+    ops.bn_bwd_stats(dy, h, mean, rstd, gamma, beta, relu, sums, dbeta, dgamma)
+    step.comm.all_reduce_(sums)
+    return ops.bn_bwd_apply(dy, h, mean, rstd, gamma, beta, relu, sums, float(rows * step.comm.world))
+
 
 class DistComm:
     def __init__(self, process_group=None):

@@ -1263,8 +1263,7 @@ def test_encoder_block_calls_equal_the_entry_point_sequence(dev, n_img):
             t16, t32 = torch.empty(n16 // 2, device=dev, dtype=torch.bfloat16), torch.empty(n32 // 4, device=dev)
             keep += [t16, t32]
             p16, p32 = t16.data_ptr(), t32.data_ptr()
-            slabs = plan["group"]._slabs(plan["slab_bytes"])
-            plan["group"].set ^= 1
+            slabs = plan.group.next_slabs(plan.slab_bytes)
             st = ops.BlockBwd(n_img=n_img, heads=H, D=D, F=Fh, rows=R, tile_dgrad=ops.dgrad_tile_code(R, D) or ops.GEMM_BK_BWD, scale=scale,
                               qkv_w=P["qkv_w"].data_ptr(), proj_w=P["proj_w"].data_ptr(), w2t=w2t.data_ptr(), w1t=w1t.data_ptr(),
                               n1_g=P["n1_g"].data_ptr(), n1_b=P["n1_b"].data_ptr(), n2_g=P["n2_g"].data_ptr(), n2_b=P["n2_b"].data_ptr(),
@@ -1275,8 +1274,8 @@ def test_encoder_block_calls_equal_the_entry_point_sequence(dev, n_img):
                               x=x.data_ptr(), ln1=ln1.data_ptr(), mu1=mu1.data_ptr(), rs1=rs1.data_ptr(), qkv=sv["qkv"].data_ptr(), ctx=sv["ctx"].data_ptr(),
                               lse=sv["lse"].data_ptr(), x_mid=sv["x_mid"].data_ptr(), ln2=sv["ln"].data_ptr(), mu2=sv["ln_mean"].data_ptr(),
                               rs2=sv["ln_rstd"].data_ptr(), pre=sv["pre"].data_ptr(), act=sv["act"].data_ptr(), dy=dy.data_ptr(),
-                              wg_fn=plan["fn"], wg_wa=plan["wa"], wg_splits=plan["splits"], wg_n_wg=plan["n_wg"], wg_fold_n=4 if n else 0,
-                              wg_fold_splits=plan["splits"], wg_trans=(ctypes.c_int * 4)(*plan["trans"]), wg_map=plan["wmap"].data_ptr(),
+                              wg_fn=plan.fn, wg_wa=plan.wa, wg_splits=plan.splits, wg_n_wg=plan.n_wg, wg_fold_n=4 if n else 0,
+                              wg_fold_splits=plan.splits, wg_trans=(ctypes.c_int * 4)(*plan.trans), wg_map=plan.wmap.data_ptr(),
                               wg_slabs=slabs.data_ptr(), wg_fold_slabs=slabs_prev.data_ptr() if n else None,
                               wg_probs=ctypes.addressof(probs[n & 1]), wg_fold_probs=ctypes.addressof(probs[(n & 1) ^ 1]) if n else None,
                               side=ops.L.stream(), fuse_ln2=int(bool(fuse_ln2)), projt=projt.data_ptr() if fuse_ln2 == 2 else None)
@@ -1287,8 +1286,7 @@ def test_encoder_block_calls_equal_the_entry_point_sequence(dev, n_img):
             ops.L.call("dig_encoder_block_bwd", ctypes.byref(st), ops.L.stream())
             slabs_prev = slabs
             outs.append(t16[off["dctx"] // 2:][:R * D].view(R, D).clone())
-        ops.L.call("dig_wgrad_group", None, 0, ctypes.addressof(probs[(len(dys) & 1) ^ 1]), 4, R, 1, None, ops.WGRAD_GROUP_SLOTS, None,
-                   ops.L.ptr(slabs_prev), plan["splits"], plan["fn"], plan["wa"], ops.L.stream())
+        plan.group.fold(ctypes.addressof(probs[(len(dys) & 1) ^ 1]), 4, slabs_prev, plan.splits)
         return outs
 
     projt = ops.transpose_bf16(P["proj_w"])
