@@ -10,7 +10,6 @@ pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head's steps ru
 `dig_gru_cell_*` (csrc/gru_attn.hip), weight gradients as ONE GEMM per weight over the stacked steps.  Beam search is not built."""
 import ctypes
 import math
-from collections import OrderedDict
 
 import torch
 
@@ -70,10 +69,7 @@ class _AttnTrainStep(_TrainStep):
             L.call("dig_gru_cell_fwd", L.ptr(gi), L.ptr(gh), L.ptr(s_all[t - 1]) if t else None, L.ptr(s_all[t]), L.ptr(sbf_all[t + 1]),
                    L.ptr(gates_all[t]), B, S, L.stream())
         # classifier for all steps at once (rows (t, b))
-        self.cls_w = torch.zeros((CLS_PAD, S), device=dev, dtype=BF16)
-        self.cls_w[:C] = w(PRE + "fc.weight")
-        cb = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        cb[:C] = p(PRE + "fc.bias")
+        self.cls_w, cb = M.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
         out = torch.empty((steps * B, CLS_PAD), device=dev, dtype=F32)
         ops.gemm(sbf_all[1:].reshape(steps * B, S), self.cls_w, steps * B, CLS_PAD, S, out=out, out_kind=ops.OUT_F32, bias=cb)
         logits[:, :steps] = out.view(steps, B, CLS_PAD)[:, :, :C].transpose(0, 1)
@@ -177,19 +173,8 @@ class AttnRecModelTrain(RecModelTrain):
                          drop_path_rate=drop_path_rate or 0.0, decoder_dropout=0.0, drop_seed=drop_seed)
 
     def param_shapes(self):
-        D, F, A, S, C = self.D, self.F, self.attDim, self.sDim, self.nb_classes
-        o = OrderedDict()
-        e = "encoder."
-        o[e + "mask_token"] = (1, 1, D)
-        o[e + "patch_embed.proj.weight"] = (D, 3, 4, 4); o[e + "patch_embed.proj.bias"] = (D,)
-        for i in range(self.depth):
-            b = f"{e}blocks.{i}."
-            o[b + "norm1.weight"] = (D,); o[b + "norm1.bias"] = (D,)
-            o[b + "attn.q_bias"] = (D,); o[b + "attn.v_bias"] = (D,)
-            o[b + "attn.qkv.weight"] = (3 * D, D); o[b + "attn.proj.weight"] = (D, D); o[b + "attn.proj.bias"] = (D,)
-            o[b + "norm2.weight"] = (D,); o[b + "norm2.bias"] = (D,)
-            o[b + "mlp.fc1.weight"] = (F, D); o[b + "mlp.fc1.bias"] = (F,); o[b + "mlp.fc2.weight"] = (D, F); o[b + "mlp.fc2.bias"] = (D,)
-        o[e + "norm.weight"] = (D,); o[e + "norm.bias"] = (D,)
+        D, A, S, C = self.D, self.attDim, self.sDim, self.nb_classes
+        o = self._encoder_shapes()
         o[PRE + "attention_unit.sEmbed.weight"] = (A, S); o[PRE + "attention_unit.sEmbed.bias"] = (A,)
         o[PRE + "attention_unit.xEmbed.weight"] = (A, D); o[PRE + "attention_unit.xEmbed.bias"] = (A,)
         o[PRE + "attention_unit.wEmbed.weight"] = (1, A); o[PRE + "attention_unit.wEmbed.bias"] = (1,)
@@ -211,15 +196,12 @@ class AttnRecModelTrain(RecModelTrain):
         fan_in = self.param_shapes()[k.rsplit(".", 1)[0] + ".weight"][1]
         return (torch.rand(shp) * 2 - 1) / math.sqrt(fan_in)
 
-    def no_weight_decay(self):
-        return {"encoder.pos_embed", "encoder.cls_token"}
-
     # ------------------------------------------------------------------ eval: greedy sample (attn_decoder.py:58-78)
     @torch.no_grad()
     def sample(self, images):
         dev = images.device
         if self._dev != dev or self._shadow is None:
-            self._prepare_train(dev)
+            self._bind(dev)
         step = _AttnTrainStep(self)
         saved = (self.drop_rate, self.attn_drop_rate, self.dpr, self.drop_step)
         self.drop_rate, self.attn_drop_rate, self.dpr = 0.0, 0.0, [0.0] * self.depth    # eval mode: no dropout
@@ -232,10 +214,7 @@ class AttnRecModelTrain(RecModelTrain):
         p, w = step.p, step.w
         xproj = ops.linear_fwd(x, w(PRE + "attention_unit.xEmbed.weight"), bias=p(PRE + "attention_unit.xEmbed.bias"))
         wv = p(PRE + "attention_unit.wEmbed.weight").reshape(A).contiguous()
-        cls_w = torch.zeros((CLS_PAD, S), device=dev, dtype=BF16)
-        cls_w[:C] = w(PRE + "fc.weight")
-        cb = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        cb[:C] = p(PRE + "fc.bias")
+        cls_w, cb = self.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
         probs = torch.empty((B, self.max_len, C), device=dev, dtype=F32)
         s = torch.zeros((B, S), device=dev, dtype=F32)
         sbf = torch.zeros((B, S), device=dev, dtype=BF16)

@@ -23,7 +23,7 @@ from . import _lib as L
 from . import dropout as DR
 from . import encoder_blocks as EB
 from . import ops
-from .recognizer import RecModel, _encoder_pos, _sinusoid
+from .recognizer import RecModel
 
 BF16, F32 = torch.bfloat16, torch.float32
 cf = ctypes.c_float
@@ -39,12 +39,9 @@ def _ref(spec):
     return ctypes.byref(spec) if spec is not None else None
 
 
-def _pad256(n):
-    return (n + 255) // 256 * 256
-
-
 class RecModelTrain(RecModel):
-    """`RecModel` with trainable flat arenas.  `.train()` forward = teacher-forced logits with autograd; `.eval()` = greedy decode."""
+    """`RecModel` with a gradient arena beside its parameter arena.  `.train()` forward = teacher-forced logits with autograd; `.eval()`
+    = greedy decode on the same weights."""
     _step_cls = None                                    # set below (the forward / backward of one step)
 
     def __init__(self, args=None, *, drop_rate=None, attn_drop_rate=None, drop_path_rate=None, decoder_dropout=0.1, drop_seed=None, **kw):
@@ -65,31 +62,6 @@ class RecModelTrain(RecModel):
         self.drop_step = 0                              # training forwards so far: every step draws fresh keys
         self.frozen = set()                             # names with requires_grad = False (`fix_encoder_layers`)
         self.frozen_blocks = 0                          # encoder blocks 0 .. frozen_blocks-1 (and patch_embed) take no gradient
-        self.comm = None
-        self._dev = None
-        self._offsets = OrderedDict()
-        off = 0
-        shapes = self.param_shapes()
-        for k, s in shapes.items():
-            n = 1
-            for d_ in s:
-                n *= d_
-            if k.endswith("attn.q_bias") and k[:-6] + "v_bias" in shapes:
-                # q_bias | zeros (K has no bias, modeling_finetune.py:91) | v_bias laid out as ONE [3D] vector: the fused qkv GEMM takes it as
-                # its bias without a per-step concatenation (the gap belongs to no optimizer granule and stays zero)
-                self._offsets[k] = (off, n, tuple(s))
-                self._offsets[k[:-6] + "v_bias"] = (off + 2 * n, n, tuple(s))
-                off += _pad256(3 * n)
-                continue
-            if k in self._offsets:
-                continue                                                    # (v_bias: placed with its q_bias)
-            self._offsets[k] = (off, n, tuple(s))
-            off += _pad256(n)
-        self._offsets = OrderedDict((k, self._offsets[k]) for k in shapes)      # registration order (state_dict / optimizer indices)
-        self.n_flat = off
-        self.flat_params = torch.zeros(off, dtype=F32)
-        self.flat_grads = torch.zeros(off, dtype=F32)
-        self._shadow = None
         self.init_weights()
 
     def init_weights(self):
@@ -139,21 +111,6 @@ class RecModelTrain(RecModel):
         return load_state_dict(self, new, prefix=prefix)
 
     # ------------------------------------------------------------------ state
-    def _view(self, flat, k, dtype_shape=True):
-        o, n, s = self._offsets[k]
-        return flat[o:o + n].view(s)
-
-    def load_state_dict(self, state_dict, strict=True):
-        super().load_state_dict(state_dict, strict)
-        for k in self._offsets:
-            if k in state_dict:
-                self._view(self.flat_params, k).copy_(self._sd[k])
-        self._ready = False
-        self.weights_changed()
-
-    def state_dict(self, *a, **k):
-        return OrderedDict((n, self._view(self.flat_params, n).detach().cpu().clone()) for n in self._offsets)
-
     def fix_encoder_layers(self, fixed_encoder_layers):
         """`--fixed_encoder_layers k` (run_class_finetuning.py:500-518): k >= 1 freezes `encoder.patch_embed`, k > 1 also the encoder
         blocks with index < k - 1 (k capped at depth + 1).  Call BEFORE `create_optimizer` (frozen parameters are not listed there, as
@@ -187,88 +144,39 @@ class RecModelTrain(RecModel):
     def no_weight_decay(self):
         return {"encoder.pos_embed", "encoder.cls_token"}
 
-    def to(self, device=None, *a, **k):
-        if device is not None:
-            dev = torch.device(device)
-            self.flat_params = self.flat_params.to(dev)
-            self.flat_grads = self.flat_grads.to(dev)
-            self._ready = False
-            self.weights_changed()
-        return self
+    _ARENAS = ("flat_params", "flat_grads")
 
-    def _prepare_train(self, dev):
-        if self.flat_params.device != dev:
-            self.to(dev)
-        if self._shadow is None or self._shadow.device != dev:
-            self._shadow = torch.empty(self.n_flat, device=dev, dtype=BF16)
-        self._enc_pos = _encoder_pos(self.N, self.D).to(dev).contiguous()
-        self._pos = _sinusoid(self.n_position, self.d).to(dev).contiguous()
-        self._dev = dev
+    def _own_arenas(self, flat_params):
+        super()._own_arenas(flat_params)
+        self.flat_grads = torch.zeros_like(flat_params)
+        self._side = self.comm = None
 
     def _side_stream(self, dev):
-        st = getattr(self, "_side", None)
+        st = self._side
         if st is None or st.device != dev:
             st = self._side = torch.cuda.Stream(device=dev, priority=-1)   # (as the pre-training side stream)
         return st
 
+    def _build_views(self):
+        w = super()._build_views()
+        grads = self._enc_block_views(self.flat_grads, self.flat_grads)
+        self._train_blocks = [{**blk, "g": g} for blk, g in zip(w["enc_blocks"], grads)]
+        return w
+
     def enc_blocks(self):
-        """The encoder blocks' accessors as encoder_blocks reads them (engine_core._EncWeights' key names: fp32 parameters, bf16 GEMM operands
-        from the shadow, "qkv_bias" = q_bias | 0 | v_bias of the arena layout, "g": the same names in the gradient arena), rebuilt when an
-        arena has been re-made (.to(), _prepare_train, a copy of the model with arenas of its own)."""
-        c = getattr(self, "_enc_blocks", None)
-        if c is None or c[0] is not self.flat_params or c[1] is not self.flat_grads or c[2] is not self._shadow:
-            blocks = []
-            for i in range(self.depth):
-                b = f"encoder.blocks.{i}."
-                qo = self._offsets[b + "attn.q_bias"][0]
-                f32 = ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")
-                w16 = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
-                d = {k: self._view(self.flat_params, b + k) for k in f32}
-                d.update({k: self._view(self._shadow, b + k) for k in w16})
-                d["qkv_bias"] = self.flat_params[qo:qo + 3 * self.D]
-                d["g"] = {k: self._view(self.flat_grads, b + k) for k in f32 + w16}
-                d["g"]["qkv_bias"] = self.flat_grads[qo:qo + 3 * self.D]
-                blocks.append(d)
-            c = self._enc_blocks = (self.flat_params, self.flat_grads, self._shadow, blocks)
-        return c[3]
-
-    def refresh_shadow(self):
-        ops.cast_f32_to_bf16(self.flat_params, self._shadow)
-
-    # fused views
-    def _fused(self, flat, first, count):
-        o, n, s = self._offsets[first]
-        return flat[o:o + count * n].view(count * s[0], s[1])
-
-    def weights_changed(self):
-        """Whoever writes the flat parameter arena (FineTuneAdamW.step, load_state_dict, ModelEma.update, .to) bumps this counter;
-        the eval forward re-syncs its tensors, re-packs the bf16 operands and re-captures the decode HIP graph only when it moved."""
-        self._weights_version = getattr(self, "_weights_version", 0) + 1
-
-    def sync_eval_weights(self, force=False):
-        """Copy the arena back into the inference path's tensors (used by `.eval()` forward / checkpoints) -- once per weight
-        version: `evaluate()` calls the eval forward for every batch, and a sync per call meant a full weight copy, a repack and a
-        HIP-graph capture per batch."""
-        # writers that go through the parameter views (an in-place op on model.parameters()) do not call weights_changed(): torch's own
-        # version counter of the arena catches those
-        ver = (getattr(self, "_weights_version", 0), self.flat_params._version)
-        if not force and getattr(self, "_synced_version", None) == ver:
-            return
-        for k in self._offsets:
-            self._sd[k] = self._view(self.flat_params, k).detach().clone()
-        self._ready = False
-        self._synced_version = ver
+        """The eval forward's per-block accessors plus "g": the same names in the gradient arena."""
+        self._views()
+        return self._train_blocks
 
     # ------------------------------------------------------------------ forward
     def forward(self, x):
         if not self.training:
-            self.sync_eval_weights()
             return super().forward(x)
         images, targets, lens = x
         if not images.is_cuda:
             raise RuntimeError("dig_amd.RecModelTrain runs on an MI355X (cuda device) only; there is no CPU fallback")
         if self._dev != images.device or self._shadow is None:
-            self._prepare_train(images.device)
+            self._bind(images.device)
         anchor = getattr(self, "_anchor", None)
         if anchor is None or anchor.device != images.device:
             anchor = self._anchor = torch.zeros(1, device=images.device, requires_grad=True)
@@ -288,15 +196,7 @@ class ModelEma:
             raise NotImplementedError("ModelEma(resume=...) is not built: load the checkpoint's 'model_ema' into .ema.load_state_dict")
         self.decay = float(decay)
         self.ema = copy.copy(model)                                            # shares configuration, owns its arenas
-        self.ema.flat_params = model.flat_params.detach().clone()
-        self.ema.flat_grads = torch.zeros_like(model.flat_grads)
-        self.ema._shadow = None
-        self.ema._side = None
-        self.ema.comm = None
-        self.ema._ready = False
-        self.ema._graphs = {}                                                  # (its own HIP-graph cache: the copy above is shallow)
-        self.ema._sd = OrderedDict((k, v.clone()) for k, v in model._sd.items())
-        self.ema._weights_version, self.ema._synced_version = 0, None
+        self.ema._own_arenas(model.flat_params.detach().clone())
         self.ema.train(False)
 
     def update(self, model):
@@ -320,7 +220,7 @@ class FlatGradComm:
         self.dist, self.group = dist, process_group
         self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
         dist.broadcast(model.flat_params, src=0, group=process_group)
-        model.weights_changed()              # the arena was just overwritten: an eval forward must re-sync (and re-capture its HIP graph)
+        model.weights_changed()              # the arena was just overwritten behind torch's back
         # every rank draws its own dropout masks (the reference seeds each rank with args.seed + rank, run_class_finetuning.py:262-264)
         model.drop_seed = (int(model.drop_seed) + 0x9E3779B97F4A7C15 * self.rank) & ((1 << 64) - 1)
 
@@ -351,18 +251,18 @@ class _TrainStep:
         (dy, saved activation) pairs and run on a second stream, joined before the optimizer."""
         M = self.m
         self._main = torch.cuda.current_stream(dev)
-        self._sd = M._side_stream(dev) if getattr(M, "overlap_streams", True) else self._main
-        return self._main, self._sd
+        self._side_st = M._side_stream(dev) if getattr(M, "overlap_streams", True) else self._main
+        return self._main, self._side_st
 
     def side(self, fn, *tensors):
-        if self._sd is self._main:
+        if self._side_st is self._main:
             fn()
             return
-        self._sd.wait_stream(self._main)
-        with torch.cuda.stream(self._sd):
+        self._side_st.wait_stream(self._main)
+        with torch.cuda.stream(self._side_st):
             fn()
         for t in tensors:
-            t.record_stream(self._sd)
+            t.record_stream(self._side_st)
 
     def encoder_forward(self, images):
         """PretrainVisionTransformerEncoder.forward (modeling_pretrain_vit.py:89-112, mask=None) on the pre-training hot-path kernels;
@@ -376,7 +276,7 @@ class _TrainStep:
         self.zmask = torch.zeros((B, N), device=dev, dtype=torch.uint8)
         # ---- encoder (PretrainVisionTransformerEncoder.forward_features, mask=None) -- the pre-training hot-path kernels
         x = ops.patch_embed_fwd(self.images, self.p("encoder.patch_embed.proj.weight").view(D, 48), self.p("encoder.patch_embed.proj.bias"),
-                                self.zmask, self.p("encoder.mask_token").view(D), M._enc_pos, D, M.gh, M.gw)
+                                self.zmask, self.p("encoder.mask_token").view(D), M._w["enc_pos"], D, M.gh, M.gw)
         # dropout / drop-path keys of this step (dig_amd/dropout.py); every spec is None when its rate is 0
         plan = self.plan = DR.DropPlan(M.drop_seed, M.drop_step)
         M.drop_step += 1
@@ -427,7 +327,7 @@ class _TrainStep:
         query = torch.cat([bos, targets.long()], dim=-1)[:, :-1].contiguous()
         self.query, self.targets, self.lens = query, targets.long().contiguous(), lens.long().contiguous()
         x = torch.empty((B * T, d), device=dev, dtype=BF16)
-        L.call("dig_seq_embed_fwd", L.ptr(query), L.ptr(self.p("decoder.trg_word_emb.weight")), L.ptr(M._pos), L.ptr(x), B, T, d,
+        L.call("dig_seq_embed_fwd", L.ptr(query), L.ptr(self.p("decoder.trg_word_emb.weight")), L.ptr(M._w["pos"]), L.ptr(x), B, T, d,
                M.nb_classes + 1, L.stream())
         x = ops.dropout_apply(x, self.ds_tgt, out=x)                            # decoder.py:180
         sc = dk ** -0.5
@@ -442,9 +342,8 @@ class _TrainStep:
             sd.wait_stream(main)
             with torch.cuda.stream(sd):
                 for i in range(M.n_layers):
-                    o2, n2, _ = M._offsets[f"decoder.layer_stack.{i}.enc_attn.linear_k.weight"]
                     fused = torch.empty((B * N, 3 * hk), device=dev, dtype=BF16)
-                    ops.gemm(mem, M._shadow[o2:o2 + 2 * n2].view(2 * hk, hk), B * N, 2 * hk, d, out=fused[:, hk:], ldc=3 * hk)
+                    ops.gemm(mem, M._fused(M._shadow, f"decoder.layer_stack.{i}.enc_attn.linear_k.weight", 2), B * N, 2 * hk, d, out=fused[:, hk:], ldc=3 * hk)
                     ev = torch.cuda.Event()
                     ev.record(sd)
                     fused.record_stream(main)
@@ -462,8 +361,6 @@ class _TrainStep:
             x1 = ops.linear_fwd(a, self.w(p + "self_attn.fc.weight"), resid=x, drop=ds["sproj"])
             h2, m2, r2 = ops.layernorm_fwd(x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), 1e-5)
             q2 = ops.linear_fwd(h2, self.w(p + "enc_attn.linear_q.weight"))
-            o2, n2, s2 = M._offsets[p + "enc_attn.linear_k.weight"]
-            wkv = M._shadow[o2:o2 + 2 * n2].view(2 * hk, hk)
             if mfma_cross:
                 # cross-attention on the MFMA kernel of the encoder (256 keys, head dim 64): the T queries of a sample sit in rows
                 # [0, T) of a fused q|k|v buffer of 256 rows per sample, and the kernels are told to compute the first
@@ -473,7 +370,7 @@ class _TrainStep:
                 a2, ctx2, lse2 = EB.cross_attn_fwd(fused, q2, B, T, nh, hk, sc, drop=ds["cattn"])
                 kvm, lse2 = fused, (lse2, ctx2)
             else:
-                kvm = ops.linear_fwd(mem, wkv)
+                kvm = ops.linear_fwd(mem, M._fused(M._shadow, p + "enc_attn.linear_k.weight", 2))
                 a2 = torch.empty((B * T, hk), device=dev, dtype=BF16)
                 lse2 = torch.empty((B, nh, T), device=dev, dtype=F32)
                 L.call("dig_seq_attn_fwd_dropout", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(a2), hk, L.ptr(lse2), B, nh,
@@ -488,10 +385,7 @@ class _TrainStep:
         o, fm, fr = ops.layernorm_fwd(x, self.p("decoder.layer_norm.weight"), self.p("decoder.layer_norm.bias"), 1e-6)
         self.fin_saved = (x, fm, fr, o)
         C = M.nb_classes
-        self.cls_w = torch.zeros((CLS_PAD, d), device=dev, dtype=BF16)
-        self.cls_w[:C] = self.w("decoder.classifier.weight")
-        cb = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        cb[:C] = self.p("decoder.classifier.bias")
+        self.cls_w, cb = M.padded_classifier("decoder.classifier.weight", "decoder.classifier.bias", CLS_PAD)
         logits = torch.empty((B * T, CLS_PAD), device=dev, dtype=F32)
         ops.gemm(o, self.cls_w, B * T, CLS_PAD, d, out=logits, out_kind=ops.OUT_F32, bias=cb)
         return logits[:, :C].reshape(B, T, C)
@@ -567,7 +461,6 @@ class _TrainStep:
             dz = ops.dropout_apply(dx2, ds["cproj"])
             side(lambda: ops.linear_wgrad(dz, a2, self.g(p + "enc_attn.fc.weight")), dz, a2)
             da2 = ops.linear_dgrad(dz, self.w(p + "enc_attn.fc.weight"))
-            o2, n2, _ = M._offsets[p + "enc_attn.linear_k.weight"]
             if isinstance(lse2, tuple):                                           # MFMA path (see forward)
                 lse2, ctx2 = lse2                                                 # padded rows: finite outputs, zero dO -> delta = 0
                 dq2, dkvm = EB.cross_attn_bwd(kvm, ctx2, lse2, da2, B, T, nh, hk, sc, drop=ds["cattn"])   # kvm = the fused q|k|v buffer
@@ -579,10 +472,10 @@ class _TrainStep:
                        L.stream())
             side(lambda: ops.linear_wgrad(dq2, h2, self.g(p + "enc_attn.linear_q.weight")), dq2, h2)
             dh2 = ops.linear_dgrad(dq2, self.w(p + "enc_attn.linear_q.weight"))
-            side(lambda: ops.wgrad(dkvm, mem, M.flat_grads[o2:o2 + 2 * n2].view(2 * hk, hk), 2 * hk, hk, B * N), dkvm, mem)
+            side(lambda: ops.wgrad(dkvm, mem, M._fused(M.flat_grads, p + "enc_attn.linear_k.weight", 2), 2 * hk, hk, B * N), dkvm, mem)
             # the gradient w.r.t. the encoder memory is needed only after the decoder loop: its GEMMs run on the second stream too
-            def mem_grad(dkvm=dkvm, o2=o2, n2=n2):
-                dm = ops.gemm(dkvm, M._shadow[o2:o2 + 2 * n2].view(2 * hk, hk), B * N, hk, 2 * hk, tb=True)
+            def mem_grad(dkvm=dkvm, wkv=M._fused(M._shadow, p + "enc_attn.linear_k.weight", 2)):
+                dm = ops.gemm(dkvm, wkv, B * N, hk, 2 * hk, tb=True)
                 if self._dmem is None:
                     self._dmem = dm
                 else:

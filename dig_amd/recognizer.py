@@ -11,6 +11,7 @@ times -- same result, position t only depends on tokens <= t) and the cross-atte
 projected once per layer.  Inference only (the fine-tune *training* step is row N1, not built yet): there is no CPU fallback
 and no autograd through this module."""
 import ctypes
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -25,9 +26,16 @@ from . import ops
 BF16, F32 = torch.bfloat16, torch.float32
 cf = ctypes.c_float
 
+# per encoder block, under the key names encoder_blocks reads: fp32 parameters and bf16 GEMM operands
+ENC_F32 = ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")
+ENC_W16 = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
 ENCODERS = {"simmim_vit_tiny_patch4_32x128": (192, 3), "simmim_vit_small_patch4_32x128": (384, 6), "simmim_vit_base_patch4_32x128": (512, 8)}
 DECODERS = {"tf_decoder": dict(n_layers=6, d_model=512, n_head=8, d_k=64, d_inner=256),
             "small_tf_decoder": dict(n_layers=2, d_model=384, n_head=6, d_k=64, d_inner=192)}
+
+
+def _pad256(n):
+    return (n + 255) // 256 * 256
 
 
 def _sinusoid(n_position, d_hid):
@@ -71,16 +79,34 @@ class RecModel(torch.nn.Module):
         self.n_layers, self.d, self.nh, self.dk, self.d_inner = n_layers, d_model, n_head, d_k, d_inner
         self.nb_classes, self.max_len, self.n_position = nb_classes, max_len, n_position
         self.start_idx = nb_classes                                         # decoder.py:149
-        self._sd = OrderedDict()
-        self._ready = False
-        self._graphs = {}
         self.use_hip_graph = True
         self.beam_width = int(getattr(args, "beam_width", 0) or 0) if args is not None else 0      # model_builder.py:110
         self.eos = 94                                                       # TFDecoder.beam_search's default (decoder.py:254)
+        # ONE weight store: an fp32 arena (each tensor padded to 256 elements, q|k|v and k|v projection weights adjacent, so the fused
+        # projections are views) and its bf16 shadow, the GEMM operands; everything the kernels read is a view of the two
+        self._offsets = OrderedDict()
+        off = 0
+        shapes = self.param_shapes()
+        for k, s in shapes.items():
+            n = math.prod(s)
+            if k.endswith("attn.q_bias") and k[:-6] + "v_bias" in shapes:
+                # q_bias | zeros (K has no bias, modeling_finetune.py:91) | v_bias laid out as ONE [3D] vector: the fused qkv GEMM takes it as
+                # its bias without a per-step concatenation (the gap belongs to no optimizer granule and stays zero)
+                self._offsets[k] = (off, n, tuple(s))
+                self._offsets[k[:-6] + "v_bias"] = (off + 2 * n, n, tuple(s))
+                off += _pad256(3 * n)
+            elif k not in self._offsets:                                    # (v_bias: placed with its q_bias)
+                self._offsets[k] = (off, n, tuple(s))
+                off += _pad256(n)
+        self._offsets = OrderedDict((k, self._offsets[k]) for k in shapes)      # registration order (state_dict / optimizer indices)
+        self.n_flat = off
+        self._loaded = False
+        self._dev = None
+        self._own_arenas(torch.zeros(off, dtype=F32))
 
     # ------------------------------------------------------------------ state
-    def param_shapes(self):
-        D, F, d, hk = self.D, self.F, self.d, self.nh * self.dk
+    def _encoder_shapes(self):
+        D, F = self.D, self.F
         o = OrderedDict()
         e = "encoder."
         o[e + "mask_token"] = (1, 1, D)
@@ -93,6 +119,11 @@ class RecModel(torch.nn.Module):
             o[b + "norm2.weight"] = (D,); o[b + "norm2.bias"] = (D,)
             o[b + "mlp.fc1.weight"] = (F, D); o[b + "mlp.fc1.bias"] = (F,); o[b + "mlp.fc2.weight"] = (D, F); o[b + "mlp.fc2.bias"] = (D,)
         o[e + "norm.weight"] = (D,); o[e + "norm.bias"] = (D,)
+        return o
+
+    def param_shapes(self):
+        D, d, hk = self.D, self.d, self.nh * self.dk
+        o = self._encoder_shapes()
         o["decoder.trg_word_emb.weight"] = (self.nb_classes + 1, d)
         for i in range(self.n_layers):
             p = f"decoder.layer_stack.{i}."
@@ -110,64 +141,142 @@ class RecModel(torch.nn.Module):
         o["linear_norm.1.weight"] = (d,); o["linear_norm.1.bias"] = (d,)
         return o
 
+    def _view(self, flat, k):
+        o, n, s = self._offsets[k]
+        return flat[o:o + n].view(s)
+
+    def _fused(self, flat, first, count):
+        """`count` adjacent [out, in] weights starting at `first` as one [count * out, in] matrix (q|k|v, k|v)."""
+        o, n, s = self._offsets[first]
+        return flat[o:o + count * n].view(count * s[0], s[1])
+
     def load_state_dict(self, state_dict, strict=True):
         """Accepts the reference RecModel's state_dict: buffers (`decoder.position_enc.position_table`) and the aliases RecModel
         registers (`patch_embed.*` = `encoder.patch_embed.*`, model_builder.py:92-93) are ignored."""
-        shapes = self.param_shapes()
+        shapes = self._offsets
         missing = [k for k in shapes if k not in state_dict]
         if missing and strict:
             raise KeyError(f"missing keys in state_dict: {missing[:5]}{'...' if len(missing) > 5 else ''}")
         extra = [k for k in state_dict if k not in shapes and not k.endswith("position_table") and not k.startswith("patch_embed.")]
         if extra and strict:
             raise KeyError(f"unexpected keys in state_dict: {extra[:5]}")
-        for k, s in shapes.items():
+        for k, (_, _, s) in shapes.items():
+            if k in state_dict and tuple(state_dict[k].shape) != s:
+                raise ValueError(f"{k}: shape {tuple(state_dict[k].shape)} != {s}")
+        for k in shapes:
             if k in state_dict:
-                if tuple(state_dict[k].shape) != tuple(s):
-                    raise ValueError(f"{k}: shape {tuple(state_dict[k].shape)} != {s}")
-                self._sd[k] = state_dict[k].detach().to(F32).clone()
-        self._ready = False
-        self._graphs = {}
+                self._view(self.flat_params, k).copy_(state_dict[k].detach())
+        self._loaded = True
+        self.weights_changed()
 
     def state_dict(self, *a, **k):
-        return OrderedDict((k_, v.cpu()) for k_, v in self._sd.items())
+        return OrderedDict((n, self._view(self.flat_params, n).detach().to("cpu", copy=True)) for n in self._offsets)
 
-    def _prepare(self, dev):
-        """bf16 GEMM operands (fused q|k|v and k|v weights, classifier padded to a multiple of 8 rows) + fp32 vectors."""
-        sd = {k: v.to(dev) for k, v in self._sd.items()}
-        D, d = self.D, self.d
-        w = {}
-        blocks = w["enc_blocks"] = []                                   # per block, under the key names encoder_blocks reads
+    _ARENAS = ("flat_params",)
+
+    def to(self, device=None, *a, **k):
+        if device is not None:
+            for name in self._ARENAS:
+                setattr(self, name, getattr(self, name).to(torch.device(device)))
+        return self
+
+    def _own_arenas(self, flat_params):
+        """Make `flat_params` this object's weight store: no shadow, unbound views, an empty HIP-graph cache (a shallow copy of a model
+        becomes a model of its own with this)."""
+        self.flat_params, self._shadow = flat_params, None
+        self._bound = self._w = self._fresh = None
+        self._weights_version = 0
+        self._graphs = {}
+
+    def weights_changed(self):
+        """Whoever writes the parameter arena through a kernel (FineTuneAdamW.step, ModelEma.update, a broadcast) calls this; the next eval
+        forward then refreshes what is derived from it.  (torch in-place writes are seen through the arena's own version counter.)"""
+        self._weights_version += 1
+
+    def refresh_shadow(self):
+        ops.cast_f32_to_bf16(self.flat_params, self._shadow)
+
+    def padded_classifier(self, weight, bias, rows, out=None):
+        """The classifier zero-padded to `rows` rows (bf16 weight from the shadow, fp32 bias), written into `out` = (weight, bias) if given."""
+        w, b = self._view(self._shadow, weight), self._view(self.flat_params, bias)
+        cw = torch.zeros((rows, w.shape[1]), device=w.device, dtype=BF16) if out is None else out[0]
+        cb = torch.zeros(rows, device=w.device, dtype=F32) if out is None else out[1]
+        cw[:w.shape[0]].copy_(w)
+        cb[:w.shape[0]].copy_(b)
+        return cw, cb
+
+    def _enc_block_views(self, f32, w16):
+        """Per block: ENC_F32 names and "qkv_bias" (q_bias | 0 | v_bias of the arena layout) as views of `f32`, ENC_W16 names of `w16`."""
+        blocks = []
         for i in range(self.depth):
             b = f"encoder.blocks.{i}."
-            blk = {k: sd[b + k] for k in ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")}
-            blk.update({k: sd[b + k].to(BF16).contiguous() for k in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")})
-            blk["qkv_bias"] = torch.cat([sd[b + "attn.q_bias"], torch.zeros(D, device=dev), sd[b + "attn.v_bias"]]).contiguous()
+            qo = self._offsets[b + "attn.q_bias"][0]
+            blk = {k: self._view(f32, b + k) for k in ENC_F32}
+            blk.update({k: self._view(w16, b + k) for k in ENC_W16})
+            blk["qkv_bias"] = f32[qo:qo + 3 * self.D]
             blocks.append(blk)
-        w["pe_w"] = sd["encoder.patch_embed.proj.weight"].reshape(D, 48).contiguous()
-        w["pe_b"] = sd["encoder.patch_embed.proj.bias"]
-        w["mask_token"] = sd["encoder.mask_token"].reshape(D).contiguous()
-        w["enc_pos"] = _encoder_pos(self.N, D).to(dev).contiguous()
-        w["enc_nw"], w["enc_nb"] = sd["encoder.norm.weight"], sd["encoder.norm.bias"]
-        w["ln_w"] = sd["linear_norm.0.weight"].to(BF16).contiguous(); w["ln_b"] = sd["linear_norm.0.bias"]
-        w["ln_nw"], w["ln_nb"] = sd["linear_norm.1.weight"], sd["linear_norm.1.bias"]
-        w["emb"] = sd["decoder.trg_word_emb.weight"].contiguous()
-        w["pos"] = _sinusoid(self.n_position, d).to(dev).contiguous()
-        for i in range(self.n_layers):
-            p = f"decoder.layer_stack.{i}."
-            cat = lambda a, names: torch.cat([sd[p + a + "." + n + ".weight"] for n in names]).to(BF16).contiguous()
-            w[p] = dict(n1w=sd[p + "norm1.weight"], n1b=sd[p + "norm1.bias"], n2w=sd[p + "norm2.weight"], n2b=sd[p + "norm2.bias"],
-                        n3w=sd[p + "norm3.weight"], n3b=sd[p + "norm3.bias"], qkv=cat("self_attn", ("linear_q", "linear_k", "linear_v")),
-                        fc=sd[p + "self_attn.fc.weight"].to(BF16).contiguous(), q2=sd[p + "enc_attn.linear_q.weight"].to(BF16).contiguous(),
-                        kv2=cat("enc_attn", ("linear_k", "linear_v")), fc2=sd[p + "enc_attn.fc.weight"].to(BF16).contiguous(),
-                        w1=sd[p + "mlp.w_1.weight"].to(BF16).contiguous(), b1=sd[p + "mlp.w_1.bias"],
-                        w2=sd[p + "mlp.w_2.weight"].to(BF16).contiguous(), b2=sd[p + "mlp.w_2.bias"])
-        w["fnw"], w["fnb"] = sd["decoder.layer_norm.weight"], sd["decoder.layer_norm.bias"]
-        C, Cp = self.nb_classes, (self.nb_classes + 7) // 8 * 8
-        cw = torch.zeros((Cp, d), device=dev); cw[:C] = sd["decoder.classifier.weight"]
-        cb = torch.zeros(Cp, device=dev); cb[:C] = sd["decoder.classifier.bias"]
-        w["cls_w"], w["cls_b"], w["Cp"] = cw.to(BF16).contiguous(), cb, Cp
-        self._w, self._dev, self._ready = w, dev, True
-        self._graphs = {}
+        return blocks
+
+    def _build_views(self):
+        """Everything the forward reads, as views of the fp32 arena (vectors, embeddings) and of the bf16 shadow (GEMM operands); own
+        storage only for the position tables and the classifier padded to a multiple of 8 rows."""
+        P, S, D, has = self.flat_params, self._shadow, self.D, self._offsets.__contains__
+        p, s = (lambda k: self._view(P, k)), (lambda k: self._view(S, k))
+        dev = P.device
+        w = {"enc_blocks": self._enc_block_views(P, S)}
+        w["pe_w"], w["pe_b"] = p("encoder.patch_embed.proj.weight").view(D, 48), p("encoder.patch_embed.proj.bias")
+        w["mask_token"] = p("encoder.mask_token").view(D)
+        tabs = getattr(self, "_tables", None)
+        if tabs is None or tabs[0] != dev:                                  # once per device
+            tabs = self._tables = (dev, _encoder_pos(self.N, D).to(dev).contiguous(), _sinusoid(self.n_position, self.d).to(dev).contiguous())
+        _, w["enc_pos"], w["pos"] = tabs
+        w["enc_nw"], w["enc_nb"] = p("encoder.norm.weight"), p("encoder.norm.bias")
+        if has("linear_norm.0.weight"):
+            w["ln_w"], w["ln_b"] = s("linear_norm.0.weight"), p("linear_norm.0.bias")
+            w["ln_nw"], w["ln_nb"] = p("linear_norm.1.weight"), p("linear_norm.1.bias")
+        if has("decoder.classifier.weight"):
+            w["emb"] = p("decoder.trg_word_emb.weight")
+            for i in range(self.n_layers):
+                l = f"decoder.layer_stack.{i}."
+                w[l] = dict(n1w=p(l + "norm1.weight"), n1b=p(l + "norm1.bias"), n2w=p(l + "norm2.weight"), n2b=p(l + "norm2.bias"),
+                            n3w=p(l + "norm3.weight"), n3b=p(l + "norm3.bias"), qkv=self._fused(S, l + "self_attn.linear_q.weight", 3),
+                            fc=s(l + "self_attn.fc.weight"), q2=s(l + "enc_attn.linear_q.weight"),
+                            kv2=self._fused(S, l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
+                            w1=s(l + "mlp.w_1.weight"), b1=p(l + "mlp.w_1.bias"), w2=s(l + "mlp.w_2.weight"), b2=p(l + "mlp.w_2.bias"))
+            w["fnw"], w["fnb"] = p("decoder.layer_norm.weight"), p("decoder.layer_norm.bias")
+            w["Cp"] = (self.nb_classes + 7) // 8 * 8
+            w["cls_w"], w["cls_b"] = torch.zeros((w["Cp"], self.d), device=dev, dtype=BF16), torch.zeros(w["Cp"], device=dev, dtype=F32)
+        return w
+
+    def _views(self):
+        """self._w, rebuilt when an arena has been re-made (.to(), another device, a copy of the model with arenas of its own): the one
+        place where addresses change, so the captured decode graphs go with it."""
+        arenas = (self.flat_params, getattr(self, "flat_grads", None), self._shadow)
+        if self._bound is None or any(a is not b for a, b in zip(self._bound, arenas)):
+            self._bound, self._w = arenas, self._build_views()
+            self._fresh, self._graphs = None, {}
+        return self._w
+
+    def _bind(self, dev):
+        """Arenas and shadow on `dev`, views bound."""
+        if self.flat_params.device != dev:
+            self.to(dev)
+        if self._shadow is None or self._shadow.device != dev:
+            self._shadow = torch.empty(self.n_flat, device=dev, dtype=BF16)
+        self._dev = dev
+        return self._views()
+
+    def _prepare(self, dev):
+        """Ready for the eval forward on `dev`: views bound, and what is derived from the fp32 arena -- the bf16 shadow (one cast launch) and
+        the padded classifier -- refreshed IN PLACE if the arena was written since.  No address changes, so a captured decode graph stays
+        valid across weight updates: the refresh is ordered before the replay on the caller's stream."""
+        w = self._bind(dev)
+        ver = (self._weights_version, self.flat_params._version)
+        if self._fresh != ver:
+            self.refresh_shadow()
+            if "cls_w" in w:
+                self.padded_classifier("decoder.classifier.weight", "decoder.classifier.bias", w["Cp"], out=(w["cls_w"], w["cls_b"]))
+            self._fresh = ver
 
     # ------------------------------------------------------------------ forward pieces
     def encoder_features(self, images):
@@ -301,10 +410,9 @@ class RecModel(torch.nn.Module):
         images = x[0] if isinstance(x, (tuple, list)) else x
         if not images.is_cuda:
             raise RuntimeError("dig_amd.RecModel runs on an MI355X (cuda device) only; there is no CPU fallback")
-        if not self._sd:
+        if not self._loaded:
             raise RuntimeError("load_state_dict() first")
-        if not self._ready or self._dev != images.device:
-            self._prepare(images.device)
+        self._prepare(images.device)
         with torch.no_grad():
             if self.beam_width > 0:
                 # RecModel.forward -> TFDecoder.forward(..., beam_width) (model_builder.py:151-158, decoder.py:101-102): token ids

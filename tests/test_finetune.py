@@ -1085,3 +1085,100 @@ def test_model_ema_tracks_the_parameters():
     assert not torch.equal(ema.ema.flat_params, m.flat_params)
     probs = ema.ema((images.to("cuda:0"), None, None))[0]                      # the averaged model decodes (eval mode)
     assert probs.shape[0] == images.shape[0] and torch.isfinite(probs).all()
+    assert all(torch.equal(a, b) for a, b in zip(_eval_outputs(ema.ema, images), _eval_outputs(_fresh_eval_model(ema.ema), images)))
+
+
+# ---------------------------------------------------------------------------------------------- one weight store for training and evaluation
+def _fresh_eval_model(m):
+    """A new RecModel holding m.state_dict(): what a checkpoint of `m` evaluates to."""
+    from dig_amd.recognizer import RecModel
+    r = RecModel(embed_dim=m.D, depth=m.depth, num_heads=m.H, n_layers=m.n_layers, d_model=m.d, n_head=m.nh, d_k=m.dk, d_inner=m.d_inner,
+                 nb_classes=m.nb_classes, max_len=m.max_len, use_1d_attdec=m.use_1d_attdec).eval()
+    r.load_state_dict(m.state_dict())
+    return r
+
+
+def _eval_outputs(m, images, graph=True):
+    m.use_hip_graph = graph
+    probs, _, _, maps = m((images.to("cuda:0"), None, None))
+    return probs, maps
+
+
+def _tiny_trainer():
+    import types
+    from dig_amd.finetune import SeqCrossEntropyLoss, LayerDecayValueAssigner, create_optimizer
+    from dig_amd.utils import NativeScalerWithGradNormCount
+    _, c, ecfg, P, images, targets, lens = _fixture()
+    m = _device_model(c, ecfg, P)
+    nl = m.get_num_layers()
+    asg = LayerDecayValueAssigner([0.75 ** (nl + 1 - i) for i in range(nl + 2)])
+    args = types.SimpleNamespace(opt="adamw", lr=1e-2, weight_decay=0.05, opt_eps=1e-8, opt_betas=None)
+    opt = create_optimizer(args, m, get_num_layer=asg.get_layer_id, get_layer_scale=asg.get_scale)
+    for grp in opt.param_groups:
+        grp["lr"] = args.lr * grp["lr_scale"]
+
+    def step():
+        m.train()
+        opt.zero_grad()
+        loss = SeqCrossEntropyLoss()(m((images.to("cuda:0"), targets, lens))[0], targets, lens)
+        NativeScalerWithGradNormCount()(loss, opt, clip_grad=None, parameters=None)
+        m.eval()
+    return m, step, images
+
+
+@pytest.mark.gpu
+def test_eval_reads_the_weights_training_wrote():
+    """The eval forward of a RecModelTrain reads the arena the optimizer writes: after every kind of write -- optimizer steps, one more
+    step behind an already captured decode graph, a torch in-place op on a parameter that tells nobody -- its outputs are bit-equal to
+    those of a fresh RecModel loaded from m.state_dict(), with the HIP graph off and on; and the bf16 operands (dig_cast_f32_to_bf16)
+    are what Tensor.to(bfloat16) gives for every tensor."""
+    m, step, images = _tiny_trainer()
+
+    def check():
+        fresh = _fresh_eval_model(m)
+        outs = None
+        for graph in (False, True):
+            outs = _eval_outputs(m, images, graph)
+            want = _eval_outputs(fresh, images, graph)
+            assert torch.equal(outs[0], want[0]) and torch.equal(outs[1], want[1]), graph
+        return outs
+
+    step(); step()
+    first = check()
+    step()                                                                     # the captured graph is replayed on the new weights
+    second = check()
+    assert not torch.equal(first[0], second[0])
+    with torch.no_grad():
+        next(p for n, p in m.named_parameters() if n == "decoder.classifier.weight").mul_(0.5)
+    third = check()
+    assert not torch.equal(second[0], third[0])
+    bad = [k for k in m._offsets if not torch.equal(m._view(m._shadow, k), m._view(m.flat_params, k).to(torch.bfloat16))]
+    assert not bad, bad
+
+
+@pytest.mark.gpu
+def test_model_keeps_one_copy_of_its_weights():
+    """After a train step and an eval forward every floating tensor the eval forward reads (m._w, through the per-block and per-layer
+    dicts) is a view of the parameter arena or of its bf16 shadow; storage of their own have only the zero-padded classifier pair and the
+    two position tables."""
+    m, step, images = _tiny_trainer()
+    step()
+    _eval_outputs(m, images)
+    arenas = {m.flat_params.untyped_storage().data_ptr(), m._shadow.untyped_storage().data_ptr()}
+    own, seen = [], 0
+
+    def walk(name, v):
+        nonlocal seen
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}[{i}]", x)
+        elif torch.is_tensor(v) and v.is_floating_point():
+            seen += 1
+            if v.untyped_storage().data_ptr() not in arenas:
+                own.append(name)
+    walk("", m._w)
+    assert sorted(own) == ["cls_b", "cls_w", "enc_pos", "pos"], own
+    assert seen > 4 + 12 * m.depth + 15 * m.n_layers

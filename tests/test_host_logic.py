@@ -386,3 +386,40 @@ def test_tensorboard_logger_surface(tmp_path):
         rows = [json.loads(l) for l in open(tmp_path / "scalars.jsonl")]
         assert [(r["tag"], r["step"]) for r in rows] == [("loss/loss", 40), ("opt/lr", 40), ("opt/grad_norm", 41)]
         assert rows[0]["value"] == 1.5 and abs(rows[1]["value"] - 2e-4) < 1e-9
+
+
+def test_recognizer_state_dict_round_trip_on_cpu():
+    """RecModel / RecModelTrain keep their weights in one fp32 arena: state_dict() -> load_state_dict() is bit-exact on the CPU and keeps the
+    registration order; strict loading still refuses a missing key, an unexpected key and a wrong shape (and ignores the reference's buffer
+    and `patch_embed.*` aliases)."""
+    import decode_oracle as D
+    from dig_amd.recognizer import RecModel
+    from dig_amd.finetune import RecModelTrain
+    c, ecfg = D.DecoderConfig(**D.TINY), O.DiGConfig(**O.TINY)
+    P = {**D.det_encoder_state(ecfg, 3), **D.det_decoder_state(c, 4)}
+    kw = dict(embed_dim=ecfg.embed_dim, depth=ecfg.depth, num_heads=ecfg.heads, n_layers=c.n_layers, d_model=c.d_model, n_head=c.n_head,
+              d_k=c.d_k, d_inner=c.d_inner, nb_classes=c.num_classes, max_len=c.max_seq_len)
+    for cls in (RecModel, RecModelTrain):
+        m = cls(**kw)
+        m.load_state_dict({**P, "decoder.position_enc.position_table": torch.zeros(1, 200, c.d_model),
+                           "patch_embed.proj.bias": P["encoder.patch_embed.proj.bias"]})
+        sd = m.state_dict()
+        assert list(sd) == list(m.param_shapes()) and set(sd) == set(P)
+        assert all(v.dtype == torch.float32 and v.device.type == "cpu" and torch.equal(v, P[k]) for k, v in sd.items())
+        m2 = cls(**kw)
+        m2.load_state_dict(sd)
+        sd2 = m2.state_dict()
+        assert list(sd2) == list(sd) and all(torch.equal(sd2[k], sd[k]) for k in sd)
+        sd["encoder.norm.weight"].add_(1.0)                                    # clones: the model is not written through them
+        assert torch.equal(m.state_dict()["encoder.norm.weight"], P["encoder.norm.weight"])
+        first = next(iter(P))
+        with pytest.raises(KeyError, match="missing"):
+            m2.load_state_dict({k: v for k, v in P.items() if k != first})
+        with pytest.raises(KeyError, match="unexpected"):
+            m2.load_state_dict({**P, "decoder.no_such.weight": torch.zeros(1)})
+        with pytest.raises(ValueError, match="shape"):
+            m2.load_state_dict({**P, "decoder.classifier.bias": torch.zeros(c.num_classes + 1)})
+        m2.load_state_dict({"encoder.norm.bias": torch.full_like(P["encoder.norm.bias"], 2.0)}, strict=False)
+        assert float(m2.state_dict()["encoder.norm.bias"].min()) == 2.0
+    with pytest.raises(RuntimeError, match="cuda"):
+        RecModel(**kw).eval()(torch.zeros(1, 3, 32, 128))
