@@ -15,6 +15,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .arena import encoder_shapes
 from .finetune import RecModelTrain, _TrainStep, CLS_PAD
 from .recognizer import ENCODERS
 
@@ -174,7 +175,7 @@ class AttnRecModelTrain(RecModelTrain):
 
     def param_shapes(self):
         D, A, S, C = self.D, self.attDim, self.sDim, self.nb_classes
-        o = self._encoder_shapes()
+        o = encoder_shapes("encoder.", D, self.F, self.depth, True)
         o[PRE + "attention_unit.sEmbed.weight"] = (A, S); o[PRE + "attention_unit.sEmbed.bias"] = (A,)
         o[PRE + "attention_unit.xEmbed.weight"] = (A, D); o[PRE + "attention_unit.xEmbed.bias"] = (A,)
         o[PRE + "attention_unit.wEmbed.weight"] = (1, A); o[PRE + "attention_unit.wEmbed.bias"] = (1,)

@@ -19,6 +19,7 @@ import torch
 from . import block_calls as BC
 from . import encoder_blocks as EB
 from . import ops
+from .arena import enc_block_views
 from .parallel import LOCAL, LocalComm, bn_backward, bn_forward  # noqa: F401  (LocalComm: part of this module's interface)
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -70,21 +71,9 @@ class _EncWeights:
     """Per-encoder (online / momentum) accessors resolved once per arena binding."""
 
     def __init__(self, model, prefix, arena):
-        self.blocks = []
-        w16, f32 = model._w(arena), model._f32
-        g32 = model._g32 if arena == "online" else {}
-        for i in range(model.depth):
-            b = f"{prefix}blocks.{i}."
-            d = {k: f32[b + k] for k in ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias",
-                                         "mlp.fc1.bias", "mlp.fc2.bias")}
-            d.update({k: w16[b + k] for k in ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")})
-            d["qkv_bias"] = model._qkv_bias[b + "attn."]
-            if g32:
-                d["g"] = {k: g32[b + k] for k in ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.proj.weight",
-                                                   "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight",
-                                                   "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")}
-                d["g"]["qkv_bias"] = model._qkv_bias_grad[b + "attn."]
-            self.blocks.append(d)
+        f32, g32 = model._f32, model._g32 if arena == "online" else {}
+        self.blocks = enc_block_views(model.specs, prefix, model.depth, model.D, model._flat[arena], model.shadow(arena),
+                                      model._flat["grad"] if g32 else None)
         self.pe_w = f32[prefix + "patch_embed.proj.weight"].view(model.D, 48)
         self.pe_b = f32[prefix + "patch_embed.proj.bias"]
         self.mask_token = f32[prefix + "mask_token"].view(model.D)

@@ -22,32 +22,16 @@ import math
 from collections import OrderedDict
 from functools import partial
 
-import numpy as np
 import os
 
 import torch
 import torch.nn as nn
 
 from . import ops
+from .arena import ALIGN, Slot, encoder_pos_table, encoder_shapes, place, round_up, view
 from .registry import register_model
 
 BF16, F32 = torch.bfloat16, torch.float32
-ALIGN = 256  # arena granule (elements): every parameter starts on a 1 KiB boundary
-
-
-def _round_up(x, a):
-    return (x + a - 1) // a * a
-
-
-def get_sinusoid_encoding_table(n_position, d_hid):
-    """Same values as modeling_finetune.py:200-210 (float64 math, cast to fp32), vectorised."""
-    pos = np.arange(n_position, dtype=np.float64)[:, None]
-    j = np.arange(d_hid)
-    ang = pos / np.power(10000.0, 2.0 * (j // 2) / d_hid)[None, :]
-    tab = np.empty_like(ang)
-    tab[:, 0::2] = np.sin(ang[:, 0::2])
-    tab[:, 1::2] = np.cos(ang[:, 1::2])
-    return torch.from_numpy(tab).to(torch.float32).unsqueeze(0)
 
 
 class _Node(nn.Module):
@@ -68,13 +52,9 @@ def _mlp_dims(n_layers, din, dmid, dout):
     return [(din if l == 0 else dmid, dout if l == n_layers - 1 else dmid) for l in range(n_layers)]
 
 
-class ParamSpec:
-    __slots__ = ("name", "shape", "numel", "offset", "group", "arena", "bundle_off")
-
-    def __init__(self, name, shape, group, arena):
-        self.name, self.shape, self.group, self.arena = name, tuple(shape), group, arena
-        self.numel = int(np.prod(shape))
-        self.offset = -1
+def _slots(shapes, arena):
+    """Unplaced slots of one arena; granule group 0 = decays (matrices, convolutions, mask_token), 1 = does not (vectors)."""
+    return OrderedDict((n, Slot(None, math.prod(s), tuple(s), 0 if len(s) >= 2 else 1, arena)) for n, s in shapes.items())
 
 
 class MoCo_ViT(nn.Module):
@@ -149,53 +129,35 @@ class MoCo_ViT(nn.Module):
         pe.patch_size, pe.patch_shape, pe.num_patches, pe.img_size = (patch_size, patch_size), (self.gh, self.gw), self.N, tuple(img_size)
 
     # ------------------------------------------------------------------ layout
-    def _encoder_specs(self, pre, arena):
-        D, Fh = self.D, self.F
-        s = [ParamSpec(pre + "mask_token", (1, 1, D), 0, arena),
-             ParamSpec(pre + "patch_embed.proj.weight", (D, 3, 4, 4), 0, arena),
-             ParamSpec(pre + "patch_embed.proj.bias", (D,), 1, arena)]
-        for i in range(self.depth):
-            b = f"{pre}blocks.{i}."
-            s += [ParamSpec(b + "norm1.weight", (D,), 1, arena), ParamSpec(b + "norm1.bias", (D,), 1, arena),
-                  ParamSpec(b + "attn.q_bias", (D,), 1, arena), ParamSpec(b + "attn.v_bias", (D,), 1, arena),
-                  ParamSpec(b + "attn.qkv.weight", (3 * D, D), 0, arena), ParamSpec(b + "attn.proj.weight", (D, D), 0, arena),
-                  ParamSpec(b + "attn.proj.bias", (D,), 1, arena), ParamSpec(b + "norm2.weight", (D,), 1, arena),
-                  ParamSpec(b + "norm2.bias", (D,), 1, arena), ParamSpec(b + "mlp.fc1.weight", (Fh, D), 0, arena),
-                  ParamSpec(b + "mlp.fc1.bias", (Fh,), 1, arena), ParamSpec(b + "mlp.fc2.weight", (D, Fh), 0, arena),
-                  ParamSpec(b + "mlp.fc2.bias", (D,), 1, arena)]
-        if self.has_final_norm:                                          # modeling_pretrain_vit.py:59,104 (Gen-only)
-            s += [ParamSpec(pre + "norm.weight", (D,), 1, arena), ParamSpec(pre + "norm.bias", (D,), 1, arena)]
-        return s
-
-    def _patchnet_specs(self, pre, arena):
+    def _patchnet_shapes(self, pre):
         """PatchNet(use_patch_transformer=True): modeling_pretrain_moco_mim_ori.py:144-154 (blocks of :88-135, q / k / v without bias)."""
         D, Fh = self.D, self.F
-        s = []
+        o = OrderedDict()
         for i in range(self.patchnet_depth):
             b = f"{pre}.blocks.{i}."
-            s += [ParamSpec(b + "norm1.weight", (D,), 1, arena), ParamSpec(b + "norm1.bias", (D,), 1, arena),
-                  ParamSpec(b + "attn.linear_q.weight", (D, D), 0, arena), ParamSpec(b + "attn.linear_k.weight", (D, D), 0, arena),
-                  ParamSpec(b + "attn.linear_v.weight", (D, D), 0, arena), ParamSpec(b + "attn.proj.weight", (D, D), 0, arena),
-                  ParamSpec(b + "attn.proj.bias", (D,), 1, arena), ParamSpec(b + "norm2.weight", (D,), 1, arena),
-                  ParamSpec(b + "norm2.bias", (D,), 1, arena), ParamSpec(b + "mlp.fc1.weight", (Fh, D), 0, arena),
-                  ParamSpec(b + "mlp.fc1.bias", (Fh,), 1, arena), ParamSpec(b + "mlp.fc2.weight", (D, Fh), 0, arena),
-                  ParamSpec(b + "mlp.fc2.bias", (D,), 1, arena)]
-        return s + [ParamSpec(pre + ".norm.weight", (D,), 1, arena), ParamSpec(pre + ".norm.bias", (D,), 1, arena)]
+            o[b + "norm1.weight"] = (D,); o[b + "norm1.bias"] = (D,)
+            o[b + "attn.linear_q.weight"] = (D, D); o[b + "attn.linear_k.weight"] = (D, D); o[b + "attn.linear_v.weight"] = (D, D)
+            o[b + "attn.proj.weight"] = (D, D); o[b + "attn.proj.bias"] = (D,)
+            o[b + "norm2.weight"] = (D,); o[b + "norm2.bias"] = (D,)
+            o[b + "mlp.fc1.weight"] = (Fh, D); o[b + "mlp.fc1.bias"] = (Fh,); o[b + "mlp.fc2.weight"] = (D, Fh); o[b + "mlp.fc2.bias"] = (D,)
+        o[pre + ".norm.weight"] = (D,); o[pre + ".norm.bias"] = (D,)
+        return o
 
-    def _convnet_specs(self, pre, arena):
+    def _convnet_shapes(self, pre):
         """ConvPatchNet: modeling_pretrain_moco_mim_ori.py:216-232 (conv_layers.{0,2,4,6} = Conv2d 3x3 with bias + BatchNorm2d; patches2global =
         Linear, BatchNorm1d, ReLU, Linear, BatchNorm1d(affine=False))."""
         from .convpatchnet import CONV_IDX, channels
         c, D = channels(self.D), self.D
-        s = []
+        o = OrderedDict()
         for j, i in enumerate(CONV_IDX):
             b = f"{pre}.conv_layers.{i}."
-            s += [ParamSpec(b + "0.weight", (c[j + 1], c[j], 3, 3), 0, arena), ParamSpec(b + "0.bias", (c[j + 1],), 1, arena),
-                  ParamSpec(b + "1.weight", (c[j + 1],), 1, arena), ParamSpec(b + "1.bias", (c[j + 1],), 1, arena)]
+            o[b + "0.weight"] = (c[j + 1], c[j], 3, 3); o[b + "0.bias"] = (c[j + 1],)
+            o[b + "1.weight"] = (c[j + 1],); o[b + "1.bias"] = (c[j + 1],)
         g = pre + ".patches2global."
-        return s + [ParamSpec(g + "0.weight", (D, c[4] * self.num_windows), 0, arena), ParamSpec(g + "0.bias", (D,), 1, arena),
-                    ParamSpec(g + "1.weight", (D,), 1, arena), ParamSpec(g + "1.bias", (D,), 1, arena),
-                    ParamSpec(g + "3.weight", (D, D), 0, arena), ParamSpec(g + "3.bias", (D,), 1, arena)]
+        o[g + "0.weight"] = (D, c[4] * self.num_windows); o[g + "0.bias"] = (D,)
+        o[g + "1.weight"] = (D,); o[g + "1.bias"] = (D,)
+        o[g + "3.weight"] = (D, D); o[g + "3.bias"] = (D,)
+        return o
 
     def _bn_layers(self):
         """(state_dict prefix, channels) of every BatchNorm layer, in the reference's registration order: the BN-MLP heads, then ConvPatchNet's."""
@@ -209,80 +171,57 @@ class MoCo_ViT(nn.Module):
         return out
 
     @staticmethod
-    def _mlp_specs(pre, dims, arena):
-        s, n = [], len(dims)
+    def _mlp_shapes(pre, dims):
+        o, n = OrderedDict(), len(dims)
         for l, (d1, d2) in enumerate(dims):
-            s.append(ParamSpec(f"{pre}.{3 * l}.weight", (d2, d1), 0, arena))
+            o[f"{pre}.{3 * l}.weight"] = (d2, d1)
             if l < n - 1:
-                s.append(ParamSpec(f"{pre}.{3 * l + 1}.weight", (d2,), 1, arena))
-                s.append(ParamSpec(f"{pre}.{3 * l + 1}.bias", (d2,), 1, arena))
-        return s
+                o[f"{pre}.{3 * l + 1}.weight"] = (d2,); o[f"{pre}.{3 * l + 1}.bias"] = (d2,)
+        return o
 
     def _build_layout(self):
-        """Reference order of named_parameters() (this is also the registration order), then arena offsets.
+        """Reference order of named_parameters() (this is also the registration order), then arena offsets (arena.place).
         Online arena: [encoder | encoder_projection_layer | pix_projector | predictor | pix_decoder]; the momentum
-        arena mirrors the first three groups offset-for-offset so the EMA is one flat kernel.  q_bias and v_bias of
-        a block share one 3*D bundle [q_bias | zeros | v_bias] = the bias vector of the fused QKV GEMM
-        (modeling_finetune.py:91: K has no bias)."""
+        arena mirrors the first three groups offset-for-offset so the EMA is one flat kernel."""
         D, Dd = self.D, self.dec_dim
-        specs = []
-        specs += self._encoder_specs("encoder.", "online")
+        specs = self.specs = OrderedDict()
+        mlp = lambda pre: self._mlp_shapes(pre, self.mlps[pre])
+        # (online prefix, its momentum copy's prefix or None, shapes of a prefix)
+        families = [("encoder.", "momentum_encoder." if self.use_moco_target else None,
+                     lambda pre: encoder_shapes(pre, D, self.F, self.depth, self.has_final_norm))]
         if self.use_moco_target:
-            specs += self._encoder_specs("momentum_encoder.", "momentum")
-            specs += self._mlp_specs("encoder_projection_layer", self.mlps["encoder_projection_layer"], "online")
-            specs += self._mlp_specs("momentum_projection_layer", self.mlps["momentum_projection_layer"], "momentum")
-            specs += self._mlp_specs("predictor", self.mlps["predictor"], "online")
-            if self.patchnet == 'regular':
-                specs += self._patchnet_specs("patch_extractor", "online")
-                specs += self._patchnet_specs("momentum_patch_extractor", "momentum")
-            elif self.patchnet == 'conv':
-                specs += self._convnet_specs("patch_extractor", "online")
-                specs += self._convnet_specs("momentum_patch_extractor", "momentum")
+            families += [("encoder_projection_layer", "momentum_projection_layer", mlp), ("predictor", None, mlp)]
+            if self.patchnet != 'no_patchtrans':
+                families.append(("patch_extractor", "momentum_patch_extractor",
+                                 self._patchnet_shapes if self.patchnet == 'regular' else self._convnet_shapes))
         if self.has_pix_projector:
-            specs += self._mlp_specs("pix_projector", self.mlps["pix_projector"], "online")
-            specs += self._mlp_specs("pix_projector_m", self.mlps["pix_projector_m"], "momentum")
+            families.append(("pix_projector", "pix_projector_m", mlp))
+        for on, mom, shapes in families:
+            specs.update(_slots(shapes(on), "online"))
+            if mom is not None:
+                specs.update(_slots(shapes(mom), "momentum"))
         if self.use_pixel_target:
-            specs += [ParamSpec("pix_decoder.0.weight", (Dd, D), 0, "online"), ParamSpec("pix_decoder.1.weight", (Dd, Dd), 0, "online"),
-                      ParamSpec("pix_decoder.2.weight", (Dd,), 1, "online"), ParamSpec("pix_decoder.2.bias", (Dd,), 1, "online"),
-                      ParamSpec("pix_decoder.4.weight", (self.dec_classes, Dd), 0, "online"),
-                      ParamSpec("pix_decoder.4.bias", (self.dec_classes,), 1, "online")]
-        self.specs = OrderedDict((s.name, s) for s in specs)
-        if not self.use_pixel_target:
+            specs.update(_slots(OrderedDict([("pix_decoder.0.weight", (Dd, D)), ("pix_decoder.1.weight", (Dd, Dd)), ("pix_decoder.2.weight", (Dd,)),
+                                             ("pix_decoder.2.bias", (Dd,)), ("pix_decoder.4.weight", (self.dec_classes, Dd)),
+                                             ("pix_decoder.4.bias", (self.dec_classes,))]), "online"))
+        else:
             # Dis-only: the encoder runs without a mask (`vis_mask_pos = None`, :493-494), mask_token is never read, its .grad stays None
             # and the reference's AdamW skips it altogether (custom_optim/adamw.py:78-79: no decay, no state): granule group 2 = untouched
-            self.specs["encoder.mask_token"].group = 2
+            specs["encoder.mask_token"] = specs["encoder.mask_token"]._replace(group=2)
 
-        def place(names, arena_groups):
-            off = 0
-            for n in names:
-                s = self.specs[n]
-                if n.endswith("attn.v_bias"):
-                    continue                                            # placed with its q_bias
-                s.offset = off
-                if n.endswith("attn.q_bias"):
-                    self.specs[n[:-len("q_bias")] + "v_bias"].offset = off + 2 * D
-                    size = 3 * D
-                else:
-                    size = s.numel
-                padded = _round_up(size, ALIGN)
-                arena_groups.extend([s.group] * (padded // ALIGN))
-                off += padded
-            return off
+        def segment(names, start, groups):
+            part = OrderedDict((n, specs[n]) for n in names)
+            end = place(part, start, groups)
+            specs.update(part)                                              # (existing keys: the registration order stays)
+            return end
 
-        ema_src = [n for n in self.specs if n.startswith(("encoder.", "encoder_projection_layer.", "patch_extractor.", "pix_projector."))]
-        rest = [n for n in self.specs if n.startswith(("predictor.", "pix_decoder."))]
+        ema_src = [n for n in specs if n.startswith(("encoder.", "encoder_projection_layer.", "patch_extractor.", "pix_projector."))]
+        rest = [n for n in specs if n.startswith(("predictor.", "pix_decoder."))]
+        mom = [n for n in specs if specs[n].arena == "momentum"]
         self._online_groups = []
-        self.n_ema = place(ema_src, self._online_groups)                    # elements covered by the EMA
-        rest_groups = []
-        n_rest = place(rest, rest_groups)
-        for n in rest:
-            if self.specs[n].offset >= 0:
-                self.specs[n].offset += self.n_ema
-        self._online_groups += rest_groups
-        self.n_online = self.n_ema + n_rest
-        mom = [n for n in self.specs if self.specs[n].arena == "momentum"]
-        tmp = []
-        n_mom = place(mom, tmp)
+        self.n_ema = segment(ema_src, 0, self._online_groups)               # elements covered by the EMA
+        self.n_online = segment(rest, self.n_ema, self._online_groups)
+        n_mom = segment(mom, 0, None)
         if not self.use_moco_target:
             self.n_ema = 0                                                  # Gen-only: no momentum arena, nothing for the EMA kernel
         assert n_mom == self.n_ema
@@ -290,7 +229,7 @@ class MoCo_ViT(nn.Module):
         for n in mom:
             src = (n.replace("momentum_encoder.", "encoder.").replace("momentum_projection_layer.", "encoder_projection_layer.")
                    .replace("momentum_patch_extractor.", "patch_extractor.").replace("pix_projector_m.", "pix_projector."))
-            assert self.specs[src].offset == self.specs[n].offset, (n, src)
+            assert specs[src].offset == specs[n].offset, (n, src)
         # gradient-bucket boundaries (element ranges of the online arena), in backward-completion order
         heads = [k for k, on in (("pix_decoder", self.use_pixel_target), ("predictor", self.use_moco_target),
                                  ("encoder_projection_layer", self.use_moco_target), ("patch_extractor", self.patchnet != 'no_patchtrans'),
@@ -323,7 +262,7 @@ class MoCo_ViT(nn.Module):
         else:
             names = [n for n in self.specs if n.startswith(key + ".") and self.specs[n].arena == "online"]
         lo = min(self.specs[n].offset for n in names)
-        hi = max(_round_up(self.specs[n].offset + self.specs[n].numel, ALIGN) for n in names)
+        hi = max(round_up(self.specs[n].offset + self.specs[n].numel) for n in names)
         return lo, hi
 
     # ------------------------------------------------------------------ storage
@@ -342,7 +281,7 @@ class MoCo_ViT(nn.Module):
         self._views_version = 0
 
     def _view(self, arena, spec):
-        return self._flat[arena][spec.offset:spec.offset + spec.numel].view(spec.shape)
+        return view(self._flat[arena], spec)
 
     def _register_tree(self):
         """Create the reference's module tree with Parameters/buffers that are views into the arenas."""
@@ -363,7 +302,7 @@ class MoCo_ViT(nn.Module):
             mod.register_buffer("num_batches_tracked", None)
             c_off += d2
             i_bn += 1
-        self.encoder.pos_embed = get_sinusoid_encoding_table(self.N, self.D)     # plain attribute (not in state_dict)
+        self.encoder.pos_embed = encoder_pos_table(self.N, self.D).unsqueeze(0)     # plain attribute (not in state_dict)
         if self.use_moco_target:
             self.momentum_encoder.pos_embed = self.encoder.pos_embed
         self._rebind()
@@ -388,13 +327,6 @@ class MoCo_ViT(nn.Module):
         self._shadow = {}
         self._f32 = {n: self._view(s.arena, s) for n, s in self.specs.items()}
         self._g32 = {n: self._view("grad", s) for n, s in self.specs.items() if s.arena == "online"}
-        self._qkv_bias, self._qkv_bias_grad = {}, {}
-        for n, s in self.specs.items():
-            if n.endswith("attn.q_bias"):
-                key = n[:-len("q_bias")]
-                self._qkv_bias[key] = self._flat[s.arena][s.offset:s.offset + 3 * self.D]
-                if s.arena == "online":
-                    self._qkv_bias_grad[key] = self._flat["grad"][s.offset:s.offset + 3 * self.D]
         self._views_version += 1
         self._fresh = None
 
@@ -502,7 +434,7 @@ class MoCo_ViT(nn.Module):
             cache = self._w16 = {}
         if arena not in cache:
             sh = self.shadow(arena)
-            cache[arena] = {n: sh[s.offset:s.offset + s.numel].view(s.shape[0], -1) for n, s in self.specs.items()
+            cache[arena] = {n: view(sh, s).view(s.shape[0], -1) for n, s in self.specs.items()
                             if s.arena == arena and len(s.shape) >= 2 and not n.endswith("mask_token")}
         return cache[arena]
 

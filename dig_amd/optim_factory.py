@@ -13,6 +13,7 @@ import torch
 import os
 
 from . import ops
+from .arena import join, split
 
 # the optimizer launch also writes the bf16 operand shadow and the transposed weight copies the next forward needs (dig_adamw_step_tr);
 # "0": the plain launch, the forward re-casts and re-transposes every step (the round-5 plan)
@@ -113,14 +114,10 @@ class FusedAdamW(torch.optim.Optimizer):
         return out
 
     def state_dict(self):
-        names = self._named_specs()
-        state = {}
-        if self._step > 0:
-            for i, n in enumerate(names):
-                sp = self.model.specs[n]
-                state[i] = {"step": self._step,
-                            "exp_avg": self.exp_avg[sp.offset:sp.offset + sp.numel].view(sp.shape),
-                            "exp_avg_sq": self.exp_avg_sq[sp.offset:sp.offset + sp.numel].view(sp.shape)}
+        moments = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        state = split(moments, self.model.specs, self._named_specs()) if self._step > 0 else {}
+        for st in state.values():
+            st["step"] = self._step
         groups, k = [], 0
         for g in self.param_groups:
             d = {key: v for key, v in g.items() if key not in ("params", "names")}
@@ -141,16 +138,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if len(sd["param_groups"]) != len(self.param_groups) or \
                 [len(g["params"]) for g in sd["param_groups"]] != [len(g["names"]) for g in self.param_groups]:
             raise ValueError("loaded state dict has different parameter groups")
-        steps = set()
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        for i, st in sd["state"].items():
-            sp = self.model.specs[names[int(i)]]
-            if tuple(st["exp_avg"].shape) != sp.shape:
-                raise ValueError(f"optimizer state {i} ({names[int(i)]}): shape {tuple(st['exp_avg'].shape)} != {sp.shape}")
-            self.exp_avg[sp.offset:sp.offset + sp.numel].view(sp.shape).copy_(st["exp_avg"])
-            self.exp_avg_sq[sp.offset:sp.offset + sp.numel].view(sp.shape).copy_(st["exp_avg_sq"])
-            steps.add(int(st["step"]))
+        join({"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}, self.model.specs, names, sd["state"])
+        steps = {int(st["step"]) for st in sd["state"].values()}
         if len(steps) > 1:
             raise ValueError("per-parameter step counts differ; the fused optimizer keeps one step counter")
         self._step = steps.pop() if steps else 0

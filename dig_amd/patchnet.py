@@ -14,6 +14,7 @@ import torch
 
 from . import encoder_blocks as EB
 from . import ops
+from .arena import fused
 
 BF16, F32 = torch.bfloat16, torch.float32
 L, cf = ops.L, ops.cf
@@ -27,12 +28,9 @@ def _names(pre, i):
                                "mlp.fc2.weight", "mlp.fc2.bias")}
 
 
-def _kv_view(model, flat, name_k, dtype_numel=1):
-    """[2 D, D] view over linear_k.weight | linear_v.weight (consecutive parameters of the arena, D * D a multiple of the 256-element granule)."""
-    sp = model.specs[name_k]
-    D = sp.shape[0]
-    assert model.specs[name_k.replace("linear_k", "linear_v")].offset == sp.offset + D * D
-    return flat[sp.offset:sp.offset + 2 * D * D].view(2 * D, D)
+def _kv_view(model, flat, name_k):
+    """[2 D, D] view over linear_k.weight | linear_v.weight (consecutive parameters of the arena, D * D a multiple of the granule)."""
+    return fused(flat, model.specs, name_k, 2)
 
 
 def forward(step, feat, pooled, pre, arena, n_img, save):

@@ -11,7 +11,6 @@ times -- same result, position t only depends on tokens <= t) and the cross-atte
 projected once per layer.  Inference only (the fine-tune *training* step is row N1, not built yet): there is no CPU fallback
 and no autograd through this module."""
 import ctypes
-import math
 from collections import OrderedDict
 
 import numpy as np
@@ -20,22 +19,16 @@ import types
 import torch
 
 from . import _lib as L
+from . import arena
 from . import encoder_blocks as EB
 from . import ops
 
 BF16, F32 = torch.bfloat16, torch.float32
 cf = ctypes.c_float
 
-# per encoder block, under the key names encoder_blocks reads: fp32 parameters and bf16 GEMM operands
-ENC_F32 = ("norm1.weight", "norm1.bias", "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias")
-ENC_W16 = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
 ENCODERS = {"simmim_vit_tiny_patch4_32x128": (192, 3), "simmim_vit_small_patch4_32x128": (384, 6), "simmim_vit_base_patch4_32x128": (512, 8)}
 DECODERS = {"tf_decoder": dict(n_layers=6, d_model=512, n_head=8, d_k=64, d_inner=256),
             "small_tf_decoder": dict(n_layers=2, d_model=384, n_head=6, d_k=64, d_inner=192)}
-
-
-def _pad256(n):
-    return (n + 255) // 256 * 256
 
 
 def _sinusoid(n_position, d_hid):
@@ -45,14 +38,6 @@ def _sinusoid(n_position, d_hid):
     tab[:, 0::2] = torch.sin(tab[:, 0::2])
     tab[:, 1::2] = torch.cos(tab[:, 1::2])
     return tab
-
-
-def _encoder_pos(n_pos, d):
-    """get_sinusoid_encoding_table (modeling_finetune.py / modeling_pretrain_vit.py: the encoder's fixed position table)."""
-    pos = np.arange(n_pos)[:, None] / np.power(10000, 2 * (np.arange(d)[None, :] // 2) / d)
-    pos[:, 0::2] = np.sin(pos[:, 0::2])
-    pos[:, 1::2] = np.cos(pos[:, 1::2])
-    return torch.FloatTensor(pos)
 
 
 class RecModel(torch.nn.Module):
@@ -82,48 +67,18 @@ class RecModel(torch.nn.Module):
         self.use_hip_graph = True
         self.beam_width = int(getattr(args, "beam_width", 0) or 0) if args is not None else 0      # model_builder.py:110
         self.eos = 94                                                       # TFDecoder.beam_search's default (decoder.py:254)
-        # ONE weight store: an fp32 arena (each tensor padded to 256 elements, q|k|v and k|v projection weights adjacent, so the fused
-        # projections are views) and its bf16 shadow, the GEMM operands; everything the kernels read is a view of the two
-        self._offsets = OrderedDict()
-        off = 0
-        shapes = self.param_shapes()
-        for k, s in shapes.items():
-            n = math.prod(s)
-            if k.endswith("attn.q_bias") and k[:-6] + "v_bias" in shapes:
-                # q_bias | zeros (K has no bias, modeling_finetune.py:91) | v_bias laid out as ONE [3D] vector: the fused qkv GEMM takes it as
-                # its bias without a per-step concatenation (the gap belongs to no optimizer granule and stays zero)
-                self._offsets[k] = (off, n, tuple(s))
-                self._offsets[k[:-6] + "v_bias"] = (off + 2 * n, n, tuple(s))
-                off += _pad256(3 * n)
-            elif k not in self._offsets:                                    # (v_bias: placed with its q_bias)
-                self._offsets[k] = (off, n, tuple(s))
-                off += _pad256(n)
-        self._offsets = OrderedDict((k, self._offsets[k]) for k in shapes)      # registration order (state_dict / optimizer indices)
-        self.n_flat = off
+        # ONE weight store: an fp32 arena laid out by arena.place (each tensor padded to the granule, q|k|v and k|v projection weights
+        # adjacent, so the fused projections are views) and its bf16 shadow, the GEMM operands; everything the kernels read is a view of the two
+        self._offsets = OrderedDict(self.param_shapes())
+        self.n_flat = arena.place(self._offsets)
         self._loaded = False
         self._dev = None
-        self._own_arenas(torch.zeros(off, dtype=F32))
+        self._own_arenas(torch.zeros(self.n_flat, dtype=F32))
 
     # ------------------------------------------------------------------ state
-    def _encoder_shapes(self):
-        D, F = self.D, self.F
-        o = OrderedDict()
-        e = "encoder."
-        o[e + "mask_token"] = (1, 1, D)
-        o[e + "patch_embed.proj.weight"] = (D, 3, 4, 4); o[e + "patch_embed.proj.bias"] = (D,)
-        for i in range(self.depth):
-            b = f"{e}blocks.{i}."
-            o[b + "norm1.weight"] = (D,); o[b + "norm1.bias"] = (D,)
-            o[b + "attn.q_bias"] = (D,); o[b + "attn.v_bias"] = (D,)
-            o[b + "attn.qkv.weight"] = (3 * D, D); o[b + "attn.proj.weight"] = (D, D); o[b + "attn.proj.bias"] = (D,)
-            o[b + "norm2.weight"] = (D,); o[b + "norm2.bias"] = (D,)
-            o[b + "mlp.fc1.weight"] = (F, D); o[b + "mlp.fc1.bias"] = (F,); o[b + "mlp.fc2.weight"] = (D, F); o[b + "mlp.fc2.bias"] = (D,)
-        o[e + "norm.weight"] = (D,); o[e + "norm.bias"] = (D,)
-        return o
-
     def param_shapes(self):
         D, d, hk = self.D, self.d, self.nh * self.dk
-        o = self._encoder_shapes()
+        o = arena.encoder_shapes("encoder.", D, self.F, self.depth, True)
         o["decoder.trg_word_emb.weight"] = (self.nb_classes + 1, d)
         for i in range(self.n_layers):
             p = f"decoder.layer_stack.{i}."
@@ -142,13 +97,7 @@ class RecModel(torch.nn.Module):
         return o
 
     def _view(self, flat, k):
-        o, n, s = self._offsets[k]
-        return flat[o:o + n].view(s)
-
-    def _fused(self, flat, first, count):
-        """`count` adjacent [out, in] weights starting at `first` as one [count * out, in] matrix (q|k|v, k|v)."""
-        o, n, s = self._offsets[first]
-        return flat[o:o + count * n].view(count * s[0], s[1])
+        return arena.view(flat, self._offsets[k])
 
     def load_state_dict(self, state_dict, strict=True):
         """Accepts the reference RecModel's state_dict: buffers (`decoder.position_enc.position_table`) and the aliases RecModel
@@ -160,9 +109,9 @@ class RecModel(torch.nn.Module):
         extra = [k for k in state_dict if k not in shapes and not k.endswith("position_table") and not k.startswith("patch_embed.")]
         if extra and strict:
             raise KeyError(f"unexpected keys in state_dict: {extra[:5]}")
-        for k, (_, _, s) in shapes.items():
-            if k in state_dict and tuple(state_dict[k].shape) != s:
-                raise ValueError(f"{k}: shape {tuple(state_dict[k].shape)} != {s}")
+        for k, slot in shapes.items():
+            if k in state_dict and tuple(state_dict[k].shape) != slot.shape:
+                raise ValueError(f"{k}: shape {tuple(state_dict[k].shape)} != {slot.shape}")
         for k in shapes:
             if k in state_dict:
                 self._view(self.flat_params, k).copy_(state_dict[k].detach())
@@ -205,30 +154,19 @@ class RecModel(torch.nn.Module):
         cb[:w.shape[0]].copy_(b)
         return cw, cb
 
-    def _enc_block_views(self, f32, w16):
-        """Per block: ENC_F32 names and "qkv_bias" (q_bias | 0 | v_bias of the arena layout) as views of `f32`, ENC_W16 names of `w16`."""
-        blocks = []
-        for i in range(self.depth):
-            b = f"encoder.blocks.{i}."
-            qo = self._offsets[b + "attn.q_bias"][0]
-            blk = {k: self._view(f32, b + k) for k in ENC_F32}
-            blk.update({k: self._view(w16, b + k) for k in ENC_W16})
-            blk["qkv_bias"] = f32[qo:qo + 3 * self.D]
-            blocks.append(blk)
-        return blocks
-
     def _build_views(self):
         """Everything the forward reads, as views of the fp32 arena (vectors, embeddings) and of the bf16 shadow (GEMM operands); own
         storage only for the position tables and the classifier padded to a multiple of 8 rows."""
         P, S, D, has = self.flat_params, self._shadow, self.D, self._offsets.__contains__
+        fused = lambda flat, first, count: arena.fused(flat, self._offsets, first, count)
         p, s = (lambda k: self._view(P, k)), (lambda k: self._view(S, k))
         dev = P.device
-        w = {"enc_blocks": self._enc_block_views(P, S)}
+        w = {"enc_blocks": arena.enc_block_views(self._offsets, "encoder.", self.depth, D, P, S)}
         w["pe_w"], w["pe_b"] = p("encoder.patch_embed.proj.weight").view(D, 48), p("encoder.patch_embed.proj.bias")
         w["mask_token"] = p("encoder.mask_token").view(D)
         tabs = getattr(self, "_tables", None)
         if tabs is None or tabs[0] != dev:                                  # once per device
-            tabs = self._tables = (dev, _encoder_pos(self.N, D).to(dev).contiguous(), _sinusoid(self.n_position, self.d).to(dev).contiguous())
+            tabs = self._tables = (dev, arena.encoder_pos_table(self.N, D).to(dev).contiguous(), _sinusoid(self.n_position, self.d).to(dev).contiguous())
         _, w["enc_pos"], w["pos"] = tabs
         w["enc_nw"], w["enc_nb"] = p("encoder.norm.weight"), p("encoder.norm.bias")
         if has("linear_norm.0.weight"):
@@ -239,9 +177,9 @@ class RecModel(torch.nn.Module):
             for i in range(self.n_layers):
                 l = f"decoder.layer_stack.{i}."
                 w[l] = dict(n1w=p(l + "norm1.weight"), n1b=p(l + "norm1.bias"), n2w=p(l + "norm2.weight"), n2b=p(l + "norm2.bias"),
-                            n3w=p(l + "norm3.weight"), n3b=p(l + "norm3.bias"), qkv=self._fused(S, l + "self_attn.linear_q.weight", 3),
+                            n3w=p(l + "norm3.weight"), n3b=p(l + "norm3.bias"), qkv=fused(S, l + "self_attn.linear_q.weight", 3),
                             fc=s(l + "self_attn.fc.weight"), q2=s(l + "enc_attn.linear_q.weight"),
-                            kv2=self._fused(S, l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
+                            kv2=fused(S, l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
                             w1=s(l + "mlp.w_1.weight"), b1=p(l + "mlp.w_1.bias"), w2=s(l + "mlp.w_2.weight"), b2=p(l + "mlp.w_2.bias"))
             w["fnw"], w["fnb"] = p("decoder.layer_norm.weight"), p("decoder.layer_norm.bias")
             w["Cp"] = (self.nb_classes + 7) // 8 * 8

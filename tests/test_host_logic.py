@@ -9,7 +9,9 @@ import torch
 
 import dig_oracle as O
 from dig_amd import utils as U
-from dig_amd.modeling_pretrain_moco_mim_ori import MoCo_ViT, ALIGN
+from dig_amd import arena
+from dig_amd.arena import ALIGN
+from dig_amd.modeling_pretrain_moco_mim_ori import MoCo_ViT
 from dig_amd.optim_factory import create_optimizer, get_parameter_groups
 from dig_amd.registry import create_model
 
@@ -423,3 +425,114 @@ def test_recognizer_state_dict_round_trip_on_cpu():
         assert float(m2.state_dict()["encoder.norm.bias"].min()) == 2.0
     with pytest.raises(RuntimeError, match="cuda"):
         RecModel(**kw).eval()(torch.zeros(1, 3, 32, 128))
+
+
+@pytest.mark.parametrize("D", [192, 64])
+def test_place_bundles_q_and_v_bias(D):
+    """arena.place at the smallest shapes where the q_bias | zeros | v_bias bundle can go wrong: D = 192 (576 elements padded to 768, v_bias at
+    +384 inside a granule, not on a boundary) and D = 64 (the whole bundle inside one granule)."""
+    def shapes():
+        return arena.encoder_shapes("encoder.", D, 4 * D, 1, True)
+
+    def check(slots, end, start, groups):
+        q, v = slots["encoder.blocks.0.attn.q_bias"], slots["encoder.blocks.0.attn.v_bias"]
+        assert list(slots) == list(shapes())                                   # registration order kept
+        assert q.offset % ALIGN == 0 and v.offset == q.offset + 2 * D
+        spans = sorted((s.offset, s.offset + s.numel) for s in slots.values())
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:]))            # no two slots overlap
+        assert all(hi <= q.offset + D or lo >= q.offset + 2 * D for lo, hi in spans)      # the gap belongs to no slot
+        assert all(s.offset % ALIGN == 0 for n, s in slots.items() if not n.endswith("attn.v_bias"))
+        assert spans[0][0] == start and end % ALIGN == 0 and end >= spans[-1][1]
+        assert len(groups) == (end - start) // ALIGN                           # one entry per granule
+        assert all(s.numel == int(np.prod(s.shape)) and s.shape == tuple(shapes()[n]) for n, s in slots.items())
+    a, ga = shapes(), []
+    end_a = arena.place(a, groups=ga)
+    check(a, end_a, 0, ga)
+    b, gb = shapes(), []
+    start = 5 * ALIGN
+    end_b = arena.place(b, start, gb)
+    check(b, end_b, start, gb)
+    assert end_b == end_a + start and ga == gb
+    assert all(b[n].offset == a[n].offset + start and b[n][1:] == a[n][1:] for n in a)     # every offset shifts by exactly `start`
+    # the group of a slot fills its granules: a bundle's are its q_bias's
+    g, gs = {n: arena.Slot(None, int(np.prod(s)), tuple(s), 0 if len(s) >= 2 else 1, "x") for n, s in shapes().items()}, []
+    arena.place(g, groups=gs)
+    for n, s in g.items():
+        if not n.endswith("attn.v_bias"):
+            assert gs[s.offset // ALIGN] == s.group and s.arena == "x", n
+    assert [s.offset for s in g.values()] == [s.offset for s in a.values()]
+    # without its sibling a q_bias is an ordinary tensor
+    alone = {"blocks.0.attn.q_bias": (D,), "w": (D, D)}
+    arena.place(alone)
+    assert alone["w"].offset == ALIGN * ((D + ALIGN - 1) // ALIGN)
+
+
+def test_fused_needs_adjacent_weights():
+    slots = {"a.linear_q.weight": (16, 16), "a.linear_k.weight": (16, 16), "a.linear_v.weight": (16, 16), "a.bias": (16,), "b.weight": (16, 16),
+             "c.weight": (8, 8), "d.weight": (8, 8)}
+    n = arena.place(slots)
+    flat = torch.arange(n, dtype=torch.float32)
+    kv = arena.fused(flat, slots, "a.linear_k.weight", 2)
+    assert kv.shape == (32, 16) and kv.data_ptr() == arena.view(flat, slots["a.linear_k.weight"]).data_ptr()
+    assert torch.equal(kv[16:], arena.view(flat, slots["a.linear_v.weight"]))
+    kv[16, 0] = -1.0                                                           # shares storage with the arena
+    assert float(flat[slots["a.linear_v.weight"].offset]) == -1.0
+    assert arena.fused(flat, slots, "a.linear_q.weight", 3).shape == (48, 16)
+    for first, count in (("a.linear_v.weight", 2),        # another shape follows
+                         ("a.bias", 2),
+                         ("c.weight", 2),                  # same shape, but 64 elements are padded to a granule: not back to back
+                         ("d.weight", 2)):                 # nothing follows
+        with pytest.raises(AssertionError):
+            arena.fused(flat, slots, first, count)
+
+
+def test_encoder_names_agree_between_pretraining_and_recognition():
+    """What lets a pre-training checkpoint load into the recognizer: a Gen-only MoCo_ViT (it keeps encoder.norm) and a RecModel of the same
+    width and depth have the same encoder.* names, shapes and relative offsets."""
+    from dig_amd.recognizer import RecModel
+    m = MoCo_ViT(encoder_embed_dim=192, encoder_depth=2, encoder_num_heads=3, use_pixel_target=True, use_moco_target=False)
+    r = RecModel(embed_dim=192, depth=2, num_heads=3, n_layers=1, d_model=64, n_head=1, d_inner=64)
+    enc_m = [(n, s.shape, s.offset - m.specs["encoder.mask_token"].offset) for n, s in m.specs.items() if n.startswith("encoder.")]
+    enc_r = [(n, s.shape, s.offset - r._offsets["encoder.mask_token"].offset) for n, s in r._offsets.items() if n.startswith("encoder.")]
+    assert enc_m == enc_r and len(enc_m) == 3 + 13 * 2 + 2
+    assert torch.equal(m.encoder.pos_embed[0], arena.encoder_pos_table(256, 192))
+
+
+def test_enc_block_views_point_at_their_slots():
+    D, depth = 64, 2
+    slots = arena.encoder_shapes("encoder.", D, 4 * D, depth, False)
+    n = arena.place(slots)
+    f32, grads, w16 = torch.zeros(n), torch.zeros(n), torch.zeros(n, dtype=torch.bfloat16)
+    plain = arena.enc_block_views(slots, "encoder.", depth, D, f32, w16)
+    train = arena.enc_block_views(slots, "encoder.", depth, D, f32, w16, grads)
+    assert len(plain) == len(train) == depth
+    for i in range(depth):
+        b = f"encoder.blocks.{i}."
+        assert "g" not in plain[i] and set(plain[i]) == set(arena.ENC_F32 + arena.ENC_W16 + ("qkv_bias",)) == set(train[i]) - {"g"}
+        assert set(train[i]["g"]) == set(arena.ENC_GRAD + ("qkv_bias",))
+        for blk in (plain[i], train[i]):
+            for k in arena.ENC_F32:
+                assert blk[k].data_ptr() == arena.view(f32, slots[b + k]).data_ptr() and blk[k].shape == slots[b + k].shape
+            for k in arena.ENC_W16:
+                assert blk[k].data_ptr() == arena.view(w16, slots[b + k]).data_ptr() and blk[k].dtype == torch.bfloat16
+            assert blk["qkv_bias"].data_ptr() == arena.qkv_bias(f32, slots, b, D).data_ptr() and blk["qkv_bias"].shape == (3 * D,)
+        for k in arena.ENC_GRAD:
+            assert train[i]["g"][k].data_ptr() == arena.view(grads, slots[b + k]).data_ptr() and train[i]["g"][k].shape == slots[b + k].shape
+        assert train[i]["g"]["qkv_bias"].data_ptr() == arena.qkv_bias(grads, slots, b, D).data_ptr()
+        assert arena.qkv_bias(f32, slots, b, D).data_ptr() == f32.data_ptr() + 4 * slots[b + "attn.q_bias"].offset
+
+
+def test_split_and_join_round_trip_moment_arenas():
+    slots = {"a.weight": (4, 8), "a.bias": (8,), "b.weight": (3, 3)}
+    n = arena.place(slots)
+    flats = {"exp_avg": torch.arange(n, dtype=torch.float32), "exp_avg_sq": -torch.arange(n, dtype=torch.float32)}
+    names = ["b.weight", "a.weight", "a.bias"]                                  # the optimizer's order, not the arena's
+    state = arena.split(flats, slots, names, skip={"a.bias"})
+    assert sorted(state) == [0, 1] and state[0]["exp_avg"].shape == (3, 3)
+    assert state[1]["exp_avg_sq"].data_ptr() == arena.view(flats["exp_avg_sq"], slots["a.weight"]).data_ptr()
+    saved = {i: {k: v.clone() for k, v in st.items()} for i, st in state.items()}
+    arena.join(flats, slots, names, {str(i): st for i, st in saved.items()})    # (keys may come back as strings)
+    assert all(torch.equal(arena.view(flats[k], slots[names[i]]), saved[i][k]) for i in saved for k in flats)
+    assert float(arena.view(flats["exp_avg"], slots["a.bias"]).abs().sum()) == 0.0       # what is not listed is zero
+    with pytest.raises(ValueError, match="shape"):
+        arena.join(flats, slots, names, {0: {"exp_avg": torch.zeros(9), "exp_avg_sq": torch.zeros(3, 3)}})
