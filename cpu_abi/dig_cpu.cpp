@@ -347,8 +347,10 @@ int dig_attn_bwd_dropout(const void* qkv_, const void* ctx_, const void* dctx_, 
         for (int j = 0; j < N_TOK; ++j) {
           float keep = 1.f;
           if (dropping) keep = drop_keep(drop->k0, drop->k1, ((unsigned)i << 16) | (unsigned)j, (unsigned)(b * heads + h), drop->thr) ? drop->scale : 0.f;
-          const float pd = p[j] * keep;                   // the probability that multiplied V in the forward
-          const float ds = p[j] * (dp[j] * keep - delta); // d(score): softmax backward through the (dropped) probabilities
+          // (both rounded to bf16, as the HIP kernels pack them for the matrix unit: with fp32 values here a sum whose terms cancel exactly
+          //  in the kernel came out as round-off, 1e-6 where the kernel writes 0)
+          const float pd = bf2f(f2bf(p[j] * keep));                   // the probability that multiplied V in the forward
+          const float ds = bf2f(f2bf(p[j] * (dp[j] * keep - delta))); // d(score): softmax backward through the (dropped) probabilities
           const bf16_t* k = qkv + ((size_t)b * N_TOK + j) * ld + D + h * DH;
           for (int c = 0; c < DH; ++c) {
             dq[c] += ds * bf2f(k[c]);

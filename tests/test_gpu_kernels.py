@@ -1057,6 +1057,204 @@ def test_attention_exact_arithmetic(dev):
     assert (lse.cpu().view(Bn, H, 256) - (256.0 + math.log(4.0))).abs().max().item() < 1e-3
 
 
+def _attention_bwd_exact_case(Bn, H, seed):
+    """Operands and the float64 gradients of the exact-arithmetic backward case.  Returns (qkv, dctx, ctx, dqkv) as [Bn * 256, ..] CPU tensors
+    (bf16 operands, float64 expectations) and m, the number of keys a query attends to."""
+    m, nh, scale = 8, 32, 0.125                                           # 256 keys / 32 hot channels: every channel hot in m = 8 keys
+    g = torch.Generator().manual_seed(seed)
+
+    def balanced():                                                       # every hot channel in exactly 8 of the 256 rows of an (image, head)
+        return torch.stack([torch.arange(256).remainder(nh)[torch.randperm(256, generator=g)] for _ in range(Bn * H)]).view(Bn, H, 256)
+    qh, kh = balanced(), balanced()
+    side = lambda: torch.randint(-1, 2, (Bn, H, 256, 32), generator=g).double()
+    q = torch.zeros(Bn, H, 256, 64, dtype=torch.float64)                  # as stored (pre-scaled): 16 in the hot channel, {-1, 0, 1} where no key has anything
+    q[..., 32:] = side()
+    q.scatter_(3, qh.unsqueeze(-1), 16.0)
+    k = torch.zeros(Bn, H, 256, 64, dtype=torch.float64)                  # 16 in the hot channel, {-1, 0, 1} in the other channels a query can be hot in
+    k[..., :32] = side()
+    k.scatter_(3, kh.unsqueeze(-1), 16.0)
+    v = torch.randint(-1, 2, (Bn, H, 256, 64), generator=g).double() * m  # multiples of m: the mean of m rows is an integer
+    do = torch.zeros(Bn, H, 256, 64, dtype=torch.float64)                 # one +-1 per row, a second one in about half the rows
+    c1 = torch.randint(0, 64, (Bn, H, 256, 1), generator=g)
+    c2 = (c1 + torch.randint(1, 64, (Bn, H, 256, 1), generator=g)).remainder(64)
+    do.scatter_(3, c2, torch.randint(-1, 2, (Bn, H, 256, 1), generator=g).double())
+    do.scatter_(3, c1, torch.randint(0, 2, (Bn, H, 256, 1), generator=g).double() * 2 - 1)
+    match = qh.unsqueeze(-1) == kh.unsqueeze(-2)                          # [Bn, H, query, key]
+    s = q @ k.transpose(-1, -2)
+    assert bool((s[match] == 256.0).all()) and s[~match].abs().max().item() <= 16.0 and bool((match.sum(-1) == m).all())
+    # the definition
+    P = match.double() / m
+    ctx = P @ v
+    dV = P.transpose(-1, -2) @ do
+    dP = do @ v.transpose(-1, -2)
+    delta = (do * ctx).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    assert bool((dS.bfloat16().double() == dS).all())                     # survives the rounding of the matrix unit's operands
+    dQ = scale * (dS @ k)                                                 # gradient w.r.t. the UNSCALED query
+    dK = dS.transpose(-1, -2) @ q
+    pack = lambda *t: torch.stack(t, 0).permute(1, 3, 0, 2, 4).reshape(Bn * 256, len(t) * H * 64)      # [image, token, (q|k|v), head, 64]
+    for name, t in (("dQ", dQ), ("dK", dK), ("dV", dV)):
+        assert bool((t.bfloat16().double() == t).all()), name             # representable: no rounding left to disagree about
+        nz = t.abs().amax(-1) > 0                                         # [Bn, H, 256] rows that carry something
+        assert nz.double().mean().item() >= 0.5 and bool(nz.view(Bn, H, 8, 32).any(-1).all()), name
+    return pack(q, k, v).bfloat16(), pack(do).bfloat16(), pack(ctx), pack(dQ, dK, dV), m
+
+
+@pytest.mark.parametrize("Bn,H", [(2, 6), (3, 2)])
+def test_attention_bwd_exact_arithmetic(dev, Bn, H):
+    """The backward on operands whose gradients are exact: hot channels of value 16 make a score 256 where query and key match and at most 16
+    elsewhere, so the probabilities are exactly 1/8 over the eight matching keys and exactly 0 (exp(-240) in fp32) over the rest; V in multiples
+    of 8, one or two +-1 per d(ctx) row and side entries in {-1, 0, 1} (the keys' where a query can be hot, the queries' where every key is
+    zero) keep dP, delta, dS = P (dP - delta) and every partial sum of dQ, dK, dV small integers over a power of two.  The expected values are
+    computed in float64 from the definition, are representable in bf16 and dense; every form of the backward must return exactly them, and
+    with them the exact per-image column sums of dQ and dV: the two-phase kernel in its three store forms, the single-pass kernel and the form
+    with the projection's data gradient inside (hip), the one form of the CPU build."""
+    from dig_amd import ops
+    D, scale = H * 64, 0.125
+    qkv_c, dctx_c, rctx, ref, m = _attention_bwd_exact_case(Bn, H, 40 + H)
+    qkv, dctx = qkv_c.to(dev), dctx_c.to(dev)
+    ctx, lse = ops.attn_fwd(qkv, Bn, H, D)
+    assert torch.equal(ctx.double().cpu(), rctx)
+    assert (lse.cpu() - (256.0 + math.log(m))).abs().max().item() < 1e-3
+    ref_q = ref[:, :D].view(Bn, 256, D).sum(1)                            # exact sums of exact summands: the same in any order, fp32 or float64
+    ref_v = ref[:, 2 * D:].view(Bn, 256, D).sum(1)
+
+    def check(form, bwd):
+        got = bwd(False)
+        for name, lo in (("dq", 0), ("dk", D), ("dv", 2 * D)):
+            assert torch.equal(got[:, lo:lo + D].double().cpu(), ref[:, lo:lo + D]), (form, name)
+        got, qs, vs = bwd(True)
+        assert torch.equal(got.double().cpu(), ref), (form, "with bias sums")
+        assert torch.equal(qs.double().cpu(), ref_q) and torch.equal(vs.double().cpu(), ref_v), (form, "bias sums")
+
+    plain = lambda sums: ops.attn_bwd(qkv, ctx, dctx, lse, Bn, H, D, scale, bias_sums=sums)
+    if dev.type == "cpu":
+        check("cpu", plain)
+        return
+    prev_mode, prev_store = ops.attn_bwd_mode(False), ops.attn_bwd_store()
+    try:
+        for store in (0, 1, 3):
+            ops.attn_bwd_store(store)
+            check(f"two-phase, store {store}", plain)
+        ops.attn_bwd_mode(True)
+        check("single pass", plain)
+    finally:
+        ops.attn_bwd_mode(prev_mode)
+        ops.attn_bwd_store(prev_store)
+    # the projection's data gradient inside: proj.weight a signed permutation, dy the matching permutation of d(ctx): dy @ proj.weight = d(ctx)
+    g = torch.Generator().manual_seed(D)
+    perm, sign = torch.randperm(D, generator=g), torch.randint(0, 2, (D,), generator=g).float() * 2 - 1
+    Wp = torch.zeros(D, D)
+    Wp[torch.arange(D), perm] = sign                                      # [out, in]
+    dy = (dctx_c.float()[:, perm] * sign).bfloat16()
+    assert torch.equal((dy.float() @ Wp).bfloat16(), dctx_c)
+    dy, projt = dy.to(dev), Wp.t().contiguous().bfloat16().to(dev)
+    check("projection inside", lambda sums: ops.attn_bwd_proj(qkv, ctx, dy, projt, lse, Bn, H, D, scale, bias_sums=sums))
+
+
+def _local_errors(got, ref, n):
+    """got / ref: [Bn, rows, H, 64] float64.  Relative Frobenius error and max-abs error over max |ref|, the largest over the (image, head)
+    pairs; n given: the largest relative Frobenius error over the (image, head, 32-row block) cells of rows [0, n) as well."""
+    fro = lambda a, b: ((a - b).norm(dim=(1, 3)) / b.norm(dim=(1, 3))).max().item()
+    out = [fro(got, ref), ((got - ref).abs().amax(dim=(1, 3)) / ref.abs().amax(dim=(1, 3))).max().item()]
+    if n is not None:
+        out.append(max(fro(got[:, r:min(r + 32, n)], ref[:, r:min(r + 32, n)]) for r in range(0, n, 32)))
+    return out
+
+
+@pytest.mark.parametrize("Bn,H,n", [(3, 6, 1), (3, 6, 5), (3, 6, 32), (3, 6, 33), (3, 6, 100), (3, 6, 224), (3, 6, 255), (2, 8, 33), (2, 8, 255)])
+def test_attention_few_query_rows(dev, Bn, H, n):
+    """attn_fwd / attn_bwd with q_rows = n and no dropout, driven as cross_attn_fwd / cross_attn_bwd drive them: n pre-scaled queries in rows
+    [0, n) of every image, zero queries with a zero d(ctx) up to the end of the last 32-row block, all 256 keys / values.  1, 2, 4, 7 and 8
+    query blocks, full and ragged last blocks: the guarded forward and the two-phase backward with waves that own no query block; n = 255
+    has all eight blocks (unguarded forward and, on hip, both backward kernels).
+      * against float64 softmax attention + autograd on the same bf16 operands, LOCALLY: per (image, head), and for ctx / dq per 32-row
+        block too, relative Frobenius error < 1e-2 (ctx) / 2e-2 (dq, dk, dv), max-abs error < 3e-2 / 4e-2 of max |ref|; lse to 2e-2;
+      * against the call with q_rows = 256 on the same zero-padded operands: ctx, lse, dq of the computed blocks and (same backward kernel
+        in both calls) dk, dv bit for bit -- the extra blocks add exact zeros;
+      * with NaN in every row past the last computed block (the queries, d(ctx), and for the backward ctx and lse): the same bits, all
+        finite.  cross_attn_bwd hands the kernels torch.empty buffers there;
+      * bias sums with fewer than eight query blocks are refused and nothing is written.
+    (The bands are the ones test_attention_fwd_bwd and test_attention_dropout_kernels_vs_torch_with_oracle_masks hold the same kernels to over
+    whole tensors; none had to be widened for a cell.  Largest values seen over all cases, hip | cpu: block Frobenius ctx 2.8e-3 | 2.1e-3,
+    dq 3.5e-3 | 3.5e-3; per (image, head) dk, dv 2.9e-3 | 2.9e-3; max-abs over max |ref| 7.1e-3 | 7.1e-3; lse 1e-6 | 1.4e-6.)"""
+    from dig_amd import ops
+    D, scale, nc = H * 64, 0.125, (n + 31) // 32 * 32
+    g = torch.Generator().manual_seed(100 * H + n)
+    fused = torch.zeros(Bn, 256, 3 * D)
+    fused[:, :n, :D] = (torch.randn(Bn, n, D, generator=g).bfloat16().float() * scale)     # (a power of two: exact)
+    fused[:, :, D:] = torch.randn(Bn, 256, 2 * D, generator=g)
+    fused = fused.bfloat16()
+    dctx = torch.zeros(Bn, 256, D)
+    dctx[:, :n] = torch.randn(Bn, n, D, generator=g)
+    dctx = dctx.bfloat16()
+    # float64 reference: the n queries of an image against its 256 keys
+    heads = lambda t, r: t.double().view(Bn, r, H, 64).transpose(1, 2)                     # [Bn, H, rows, 64]
+    q, k, v = (heads(t, r).clone().requires_grad_(True) for t, r in ((fused[:, :n, :D], n), (fused[:, :, D:2 * D], 256), (fused[:, :, 2 * D:], 256)))
+    s = q @ k.transpose(-1, -2)
+    o = s.softmax(-1) @ v
+    o.backward(heads(dctx[:, :n], n))
+    r_ctx, r_lse = o.detach().transpose(1, 2), torch.logsumexp(s.detach(), -1)             # [Bn, n, H, 64], [Bn, H, n]
+    r_dq, r_dk, r_dv = (q.grad * scale).transpose(1, 2), k.grad.transpose(1, 2), v.grad.transpose(1, 2)
+
+    f2, d2 = fused.view(Bn * 256, 3 * D).to(dev), dctx.view(Bn * 256, D).to(dev)
+    rows = lambda t, lo, r: t.double().cpu().view(Bn, 256, -1)[:, :r, lo:lo + D].reshape(Bn, r, H, 64)
+    hip = dev.type != "cpu"
+    prev = ops.attn_bwd_mode(False) if hip else False
+    try:
+        for single_pass in ((False, True) if hip and nc == 256 else (False,)):
+            if hip:
+                ops.attn_bwd_mode(single_pass)
+            ctx, lse = ops.attn_fwd(f2, Bn, H, D, q_rows=n)
+            dqkv = ops.attn_bwd(f2, ctx, d2, lse, Bn, H, D, scale, q_rows=n)
+            e_ctx = _local_errors(rows(ctx, 0, n), r_ctx, n)
+            e_lse = (lse.double().cpu().view(Bn, H, 256)[:, :, :n] - r_lse).abs().max().item()
+            e_dq = _local_errors(rows(dqkv, 0, n), r_dq, n)
+            e_dk = _local_errors(rows(dqkv, D, 256), r_dk, None)
+            e_dv = _local_errors(rows(dqkv, 2 * D, 256), r_dv, None)
+            print(f"few_query_rows {dev.type} Bn={Bn} H={H} n={n} sp={single_pass}: [fro, maxabs, block fro] ctx {e_ctx} dq {e_dq} dk {e_dk} dv {e_dv} lse {e_lse:.2e}")
+            assert e_ctx[0] < 1e-2 and e_ctx[2] < 1e-2 and e_ctx[1] < 3e-2 and e_lse < 2e-2
+            assert e_dq[0] < 2e-2 and e_dq[2] < 2e-2 and e_dq[1] < 4e-2
+            for e in (e_dk, e_dv):
+                assert e[0] < 2e-2 and e[1] < 4e-2
+            assert not rows(dqkv, 0, nc)[:, n:].any()                                      # a zero query with a zero d(ctx): no gradient
+            # the full-size call on the same operands
+            ctx_f, lse_f = ops.attn_fwd(f2, Bn, H, D)
+            dqkv_f = ops.attn_bwd(f2, ctx_f, d2, lse_f, Bn, H, D, scale)
+            img = lambda t: t.view(Bn, 256, -1)
+            assert torch.equal(img(ctx)[:, :nc], img(ctx_f)[:, :nc]) and torch.equal(lse[:, :nc], lse_f[:, :nc])
+            assert torch.equal(img(dqkv)[:, :nc, :D], img(dqkv_f)[:, :nc, :D]), "dq"
+            assert torch.equal(dqkv[:, D:], dqkv_f[:, D:]), "dk | dv"
+            # garbage past the last computed block
+            if nc < 256:
+                nan = float("nan")
+                f3, d3 = f2.clone(), d2.clone()
+                img(f3)[:, nc:, :D] = nan
+                img(d3)[:, nc:] = nan
+                ctx_n, lse_n = ops.attn_fwd(f3, Bn, H, D, q_rows=n)
+                assert torch.equal(img(ctx_n)[:, :nc], img(ctx)[:, :nc]) and torch.equal(lse_n[:, :nc], lse[:, :nc])
+                img(ctx_n)[:, nc:] = nan
+                lse_n[:, nc:] = nan
+                dqkv_n = ops.attn_bwd(f3, ctx_n, d3, lse_n, Bn, H, D, scale, q_rows=n)
+                assert torch.equal(img(dqkv_n)[:, :nc, :D], img(dqkv)[:, :nc, :D]), "dq with NaN rows behind"
+                assert torch.equal(dqkv_n[:, D:], dqkv[:, D:]), "dk | dv with NaN rows behind"
+                assert bool(torch.isfinite(img(ctx)[:, :nc].float()).all() and torch.isfinite(lse[:, :nc]).all()
+                            and torch.isfinite(img(dqkv)[:, :nc, :D].float()).all() and torch.isfinite(dqkv[:, D:].float()).all())
+            # the fused bias sums assume all eight query blocks: refused, nothing written
+            if nc < 256:
+                with pytest.raises(RuntimeError, match="unsupported"):
+                    ops.attn_bwd(f2, ctx, d2, lse, Bn, H, D, scale, bias_sums=True, q_rows=n)
+                keep = torch.full_like(f2, 3.0)
+                sums = torch.full((2, Bn, D), 3.0, device=dev)
+                with pytest.raises(RuntimeError, match="unsupported"):
+                    ops.L.call("dig_attn_bwd_dropout", ops.L.ptr(f2), ops.L.ptr(ctx), ops.L.ptr(d2), ops.L.ptr(lse), ops.L.ptr(keep), Bn, H, D, cf(scale),
+                               ops.L.ptr(sums[0]), ops.L.ptr(sums[1]), None, n, ops.L.stream())
+                assert bool((keep == 3.0).all() and (sums == 3.0).all())
+    finally:
+        if hip:
+            ops.attn_bwd_mode(prev)
+
+
 def _attn_block_reference(ln1, x, wq, bq, wp, bp, n_img, H, D, scale):
     """Attention.forward + the residual add (modeling_finetune.py:87-120, :156) in fp32 torch on the bf16 operands."""
     qkv = ln1.float() @ wq.float().t() + bq
