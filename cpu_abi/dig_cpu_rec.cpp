@@ -120,6 +120,21 @@ inline void row_max_sum(const float* x, int C, float& m, float& s) {
 }
 
 inline unsigned char canon_of(long long v, const unsigned char* canon, int n_classes) { return (v >= 0 && v < n_classes) ? canon[v] : 0; }
+// Levenshtein distance with unit costs, one row of the table at a time
+inline int levenshtein(const int* x, int xlen, const int* y, int ylen) {
+  std::vector<int> row(ylen + 1);
+  for (int j = 0; j <= ylen; ++j) row[j] = j;
+  for (int i = 0; i < xlen; ++i) {
+    int diag = row[0];
+    row[0] = i + 1;
+    for (int j = 1; j <= ylen; ++j) {
+      const int old = row[j];
+      row[j] = std::min(std::min(old, row[j - 1]) + 1, diag + (x[i] != y[j - 1] ? 1 : 0));
+      diag = old;
+    }
+  }
+  return row[ylen];
+}
 
 }  // namespace
 
@@ -353,6 +368,75 @@ int dig_char_fmeasure(const long long* pred, const long long* target, const unsi
     const double n = (double)__builtin_popcountll(ps & ts);
     const double p = n / ((double)__builtin_popcountll(ps) + 1e-5), r = n / ((double)__builtin_popcountll(ts) + 1e-5);
     f_per_sample[b] = 2 * p * r / (p + r + 1e-5);
+  }
+  return DIG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- strings (csrc/metrics.hip)
+int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text, int* len,
+                       hipStream_t) {
+  if (!tokens || !canon || !text || !len || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  for (int b = 0; b < B; ++b) {
+    int n = 0;
+    for (int i = 0; i < T && tokens[(size_t)b * T + i] != eos; ++i) {
+      const int c = canon_of(tokens[(size_t)b * T + i], canon, n_classes);
+      if (c) text[(size_t)b * T + n++] = c <= 10 ? '0' + (c - 1) : 'a' + (c - 11);
+    }
+    len[b] = n;
+    for (int i = n; i < T; ++i) text[(size_t)b * T + i] = 0;
+  }
+  return DIG_OK;
+}
+
+int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const int* a_index, const int* b, const int* b_len, int ldb,
+                      int n, int* dist, hipStream_t) {
+  if (!a || !a_len || !b || !b_len || !dist || lda <= 0 || ldb <= 0 || n <= 0 || a_rows <= 0) return DIG_ERR_ARG;
+  if (!a_index && a_rows < n) return DIG_ERR_ARG;
+  if (lda > 128 || ldb > 128) return DIG_ERR_UNSUPPORTED;
+  for (int i = 0; i < n; ++i) {
+    const int r = a_index ? a_index[i] : i;
+    const bool have = r >= 0 && r < a_rows;
+    dist[i] = levenshtein(a + (size_t)(have ? r : 0) * lda, have ? std::clamp(a_len[r], 0, lda) : 0, b + (size_t)i * ldb,
+                          std::clamp(b_len[i], 0, ldb));
+  }
+  return DIG_OK;
+}
+
+long long dig_lexicon_search_workspace_bytes(int B, int max_count) {
+  if (B <= 0 || max_count < 0) return 0;
+  return (long long)B * std::max(1LL, ((long long)max_count + 63) / 64) * 8;
+}
+
+int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, const int* words, const int* word_len, int ldw, int W,
+                       const int* lex_begin, const int* lex_count, int max_count, int* best_index, int* best_dist, void* workspace,
+                       long long workspace_bytes, hipStream_t) {
+  if (!query || !query_len || !words || !word_len || !lex_begin || !lex_count || !best_index || !best_dist || !workspace) return DIG_ERR_ARG;
+  if (ldq <= 0 || ldw <= 0 || B <= 0 || W <= 0 || max_count < 0) return DIG_ERR_ARG;
+  if (ldq > 128 || ldw > 128 || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
+  if (workspace_bytes < dig_lexicon_search_workspace_bytes(B, max_count)) return DIG_ERR_ARG;
+  for (int q = 0; q < B; ++q) {
+    const int begin = std::clamp(lex_begin[q], 0, W);
+    const int count = std::clamp(lex_count[q], 0, std::min(W - begin, max_count));
+    int bi = -1, bd = -1;
+    for (int w = begin; w < begin + count; ++w) {
+      const int d = levenshtein(words + (size_t)w * ldw, std::clamp(word_len[w], 0, ldw), query + (size_t)q * ldq,
+                                std::clamp(query_len[q], 0, ldq));
+      if (bi < 0 || d < bd) { bi = w; bd = d; }
+    }
+    best_index[q] = bi;
+    best_dist[q] = bd;
+  }
+  return DIG_OK;
+}
+
+int dig_seq_confidence(const float* score, const int* text_len, int B, int T, double* conf, hipStream_t) {
+  if (!score || !text_len || !conf || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  for (int b = 0; b < B; ++b) {
+    const int n = text_len[b] < 0 ? 0 : (text_len[b] >= T ? T : text_len[b] + 1);
+    double s = 0.0;
+    for (int j = 0; j < n; ++j) s += std::log((double)score[(size_t)b * T + j]);
+    conf[b] = std::exp(s);
   }
   return DIG_OK;
 }

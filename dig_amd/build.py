@@ -92,7 +92,9 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                # the key-view augmentation of the input path (keyview.hip): the sampler's and the stages' per-thread state stays in registers
                "keyview_sample_kernel", "keyview_stage_a_kernel", "keyview_stage_b_kernel",
                # the ABINet augmentation of fine-tuning (abiaug.hip): the same
-               "abiaug_sample_kernel", "abiaug_warp_kernel", "abiaug_det_kernel", "abiaug_tail_kernel")
+               "abiaug_sample_kernel", "abiaug_warp_kernel", "abiaug_det_kernel", "abiaug_tail_kernel",
+               # the lexicon search of the evaluation metrics (metrics.hip): its DP row is in LDS, the rest in registers
+               "lexicon_search_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

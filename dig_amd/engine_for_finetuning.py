@@ -14,6 +14,7 @@ from typing import Iterable, Optional
 import torch
 
 from . import utils
+from .evaluation_metric import edit_distances
 from .recognizer import SeqCrossEntropyLoss, accuracy, recognition_f_measure
 
 
@@ -147,6 +148,7 @@ def evaluate(data_loader, model, device, args=None):
     header = 'Test:'
     model.eval()
     voc = _vocabulary(data_loader.dataset)
+    with_ed = bool(getattr(args, "eval_edit_distance", False))                      # EditDistance (evaluation_metric/metrics.py:142-147) per image
     for batch in metric_logger.log_every(data_loader, 10, header):
         images, target, lens = batch[0], batch[1], batch[-1]
         images = images.to(device, non_blocking=True)
@@ -159,12 +161,18 @@ def evaluate(data_loader, model, device, args=None):
         else:
             loss = criterion(output, target, lens)                               # (on probabilities, as the reference does: :249)
             pred_ids = output.argmax(-1)
-        vals = torch.stack([loss.double(), accuracy(pred_ids, target, voc).double(), recognition_f_measure(pred_ids, target, voc)]).tolist()
+        vals = [loss.double(), accuracy(pred_ids, target, voc).double(), recognition_f_measure(pred_ids, target, voc)]
+        if with_ed:
+            vals.append(edit_distances(pred_ids, target, voc).double().mean())
+        vals = torch.stack(vals).tolist()                                        # the one host read of the batch
         batch_size = images.shape[0]
         metric_logger.update(loss=vals[0])
         metric_logger.meters['acc'].update(vals[1], n=batch_size)
         metric_logger.meters['recognition_fmeasure'].update(vals[2], n=batch_size)
+        if with_ed:
+            metric_logger.meters['edit_distance'].update(vals[3], n=batch_size)
     metric_logger.synchronize_between_processes()
     print('* {n} images, Acc {acc.global_avg:.4f} loss {losses.global_avg:.4f} Rec_fmeasure {rec_f.global_avg:.4f}'
-          .format(n=metric_logger.acc.count, acc=metric_logger.acc, losses=metric_logger.loss, rec_f=metric_logger.recognition_fmeasure))
+          .format(n=metric_logger.acc.count, acc=metric_logger.acc, losses=metric_logger.loss, rec_f=metric_logger.recognition_fmeasure)
+          + (' Edit_distance {:.4f}'.format(metric_logger.edit_distance.global_avg) if with_ed else ''))
     return {k: meter.global_avg for k, meter in metric_logger.meters.items()}

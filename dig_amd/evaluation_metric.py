@@ -1,0 +1,264 @@
+"""The reference's `evaluation_metric` package on the device: same keys, signatures and return types, quirks included.
+
+    from dig_amd import evaluation_metric
+    evaluation_metric.factory()["editdistance_with_lexicon"](output, target, dataset, file_names)
+
+`output` / `target` are [B, T] tensors of class ids on the device the library runs on; `dataset` gives the vocabulary the way
+`engine_for_finetuning._vocabulary` reads it (`idx_to_class` or `voc`) and, for the lexicon metrics, `lexicons50`, `lexicons1k` and
+`lexiconsfull`: `Lexicon` objects, or plain {file name: [words]} dicts that are wrapped (and cached on the dataset) on first use.
+
+What runs where: the strings never leave the device.  `dig_tokens_to_text` normalises both label tensors (get_str_list, metrics.py:19-64),
+`dig_lexicon_search` finds each prediction's nearest lexicon word (one launch for the batch, whatever the lexicon size), `dig_edit_distance`
+compares pairs, `dig_seq_confidence` gives RecPostProcess's score; every function reads its results back in one copy.
+
+Mirrored literally from metrics.py:103-186: the search compares NORMALISED lexicon words with the normalised prediction but returns the RAW
+word; accuracy then tests raw word == normalised target (a lexicon word with an upper-case letter or punctuation never counts as correct) and
+the edit distance is taken between the raw word and the normalised target; a lexicon level reports 0 when `file_names` is empty or the
+lexicon of `file_names[0]` is empty -- only the first file name is looked at, and an empty lexicon further down raises as np.argmin does.
+
+Two keys of the reference's factory are left out: `ctc_accuracy` and `multi_label_fmeasure`.  Neither can be reached there (no model of the
+reference emits CTC frames or multi-label outputs for them), and CTC / multi-label metrics are not built here."""
+import string
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import recognizer
+
+MAX_WORD_LEN = 128                      # DIG_LEV_MAX_LEN
+CHUNK = 64                              # DIG_LEXICON_CHUNK: words per workgroup of the search
+_KEEP = string.digits + string.ascii_letters
+
+
+def _normalize_text(text):
+    """metrics.py:14-16."""
+    return "".join(c for c in text if c in _KEEP).lower()
+
+
+# ---------------------------------------------------------------------------------------------- device operators
+def tokens_to_text(tokens, voc):
+    """Normalised strings of [B, T] class ids: (text int32 [B, T] code points, length int32 [B])."""
+    B, T = tokens.shape
+    dev = tokens.device
+    tok, canon = tokens.long().contiguous(), recognizer.class_canon(voc).to(dev)
+    text = torch.empty((B, T), device=dev, dtype=torch.int32)
+    length = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call("dig_tokens_to_text", L.ptr(tok), L.ptr(canon), len(voc), voc.index("EOS"), B, T, L.ptr(text), L.ptr(length), L.stream())
+    return text, length
+
+
+def edit_distance(a, a_len, b, b_len, a_index=None):
+    """Levenshtein distance of n pairs of device strings (int32 rows + int32 lengths): dist int32 [n] = d(a[a_index[i]] or a[i], b[i])."""
+    n = b.shape[0]
+    dist = torch.empty(n, device=b.device, dtype=torch.int32)
+    L.call("dig_edit_distance", L.ptr(a), L.ptr(a_len), a.shape[1], a.shape[0], L.ptr(a_index), L.ptr(b), L.ptr(b_len), b.shape[1], n,
+           L.ptr(dist), L.stream())
+    return dist
+
+
+def lexicon_search_workspace_bytes(B, max_count):
+    import ctypes
+    f = L.lib().dig_lexicon_search_workspace_bytes
+    f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]
+    return int(f(B, max_count))
+
+
+def lexicon_search(query, query_len, words, word_len, lex_begin, lex_count):
+    """For each query row the first nearest word of pool rows [lex_begin[b], lex_begin[b] + lex_count[b]): (best_index, best_dist), int32 [B],
+    both -1 for an empty range.  lex_begin / lex_count are host sequences; a range outside the pool is refused here, before upload."""
+    B, W = query.shape[0], words.shape[0]
+    begin, count = np.asarray(lex_begin, dtype=np.int64).reshape(-1), np.asarray(lex_count, dtype=np.int64).reshape(-1)
+    if begin.shape != (B,) or count.shape != (B,):
+        raise ValueError(f"lex_begin / lex_count need one entry per query ({B})")
+    bad = np.nonzero((begin < 0) | (count < 0) | (begin + count > W))[0]
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"lexicon range of query {b} ([{int(begin[b])}, {int(begin[b] + count[b])})) is outside the pool of {W} words")
+    dev = query.device
+    max_count = int(count.max())
+    ranges = torch.from_numpy(np.stack([begin, count]).astype(np.int32)).to(dev)
+    ws_bytes = lexicon_search_workspace_bytes(B, max_count)
+    ws = torch.empty(ws_bytes // 8, device=dev, dtype=torch.int64)
+    best_index = torch.empty(B, device=dev, dtype=torch.int32)
+    best_dist = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call("dig_lexicon_search", L.ptr(query), L.ptr(query_len), query.shape[1], B, L.ptr(words), L.ptr(word_len), words.shape[1], W,
+           L.ptr(ranges[0]), L.ptr(ranges[1]), max_count, L.ptr(best_index), L.ptr(best_dist), L.ptr(ws), ws_bytes, L.stream())
+    return best_index, best_dist
+
+
+def seq_confidence(score, text_len):
+    """RecPostProcess's score per row (metrics.py:195-200): float64 [B] from score [B, T] fp32 and the normalised lengths."""
+    B, T = score.shape
+    sc, tl = score.float().contiguous(), text_len.to(torch.int32).contiguous()
+    conf = torch.empty(B, device=score.device, dtype=torch.float64)
+    L.call("dig_seq_confidence", L.ptr(sc), L.ptr(tl), B, T, L.ptr(conf), L.stream())
+    return conf
+
+
+def edit_distances(pred_tokens, target_tokens, voc):
+    """Per-sample edit distance of the normalised strings of two [B, T] label tensors: int32 [B] on the device (no host read)."""
+    p, pl = tokens_to_text(pred_tokens, voc)
+    t, tl = tokens_to_text(target_tokens.to(pred_tokens.device), voc)
+    return edit_distance(p, pl, t, tl)
+
+
+# ---------------------------------------------------------------------------------------------- lexicons
+def _pool(words):
+    n, ld = max(len(words), 1), max([len(w) for w in words] + [1])
+    rows, lens = np.zeros((n, ld), dtype=np.int32), np.zeros(n, dtype=np.int32)
+    for i, w in enumerate(words):
+        rows[i, :len(w)] = [ord(c) for c in w]
+        lens[i] = len(w)
+    return rows, lens
+
+
+class Lexicon:
+    """Host preparation of a lexicon set {name: [words]}, done once: the RAW words and their `_normalize_text` as code-point rows with
+    lengths, in two pools indexed alike, and per name a range (begin, count) into them.  Identical lists are stored once and share their
+    range.  `device(dev)` uploads once per device.  `lex[name]` is the list of raw words, as in the reference's dicts."""
+
+    def __init__(self, words_by_name):
+        self.ranges, self._lists = {}, {}
+        raw, seen = [], {}
+        for name, words in words_by_name.items():
+            key = tuple(words)
+            r = seen.get(key)
+            if r is None:
+                for w in key:
+                    if len(w) > MAX_WORD_LEN:
+                        raise ValueError(f"lexicon word longer than {MAX_WORD_LEN} code points ({len(w)}) in {name!r}: {w!r}")
+                r = seen[key] = (len(raw), len(key), list(key))
+                raw.extend(key)
+            self.ranges[name] = r[:2]
+            self._lists[name] = r[2]
+        self.words = raw
+        self.n_words = len(raw)
+        self.raw, self.raw_len = _pool(raw)
+        self.norm, self.norm_len = _pool([_normalize_text(w) for w in raw])
+        self._dev = {}
+
+    def __getitem__(self, name):
+        return self._lists[name]
+
+    def __contains__(self, name):
+        return name in self._lists
+
+    def __len__(self):
+        return len(self._lists)
+
+    def keys(self):
+        return self._lists.keys()
+
+    def device(self, dev):
+        """(raw, raw_len, norm, norm_len) on `dev`."""
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = tuple(torch.from_numpy(a).to(dev) for a in (self.raw, self.raw_len, self.norm, self.norm_len))
+        return t
+
+
+def _lexicon(dataset, attr):
+    lex = getattr(dataset, attr)
+    if isinstance(lex, Lexicon):
+        return lex
+    cache = getattr(dataset, "_dig_lexicons", None)
+    if cache is None:
+        cache = {}
+        setattr(dataset, "_dig_lexicons", cache)
+    ent = cache.get(attr)
+    if ent is None or ent[0] is not lex:
+        ent = cache[attr] = (lex, Lexicon(lex))
+    return ent[1]
+
+
+def _voc(dataset):
+    from .engine_for_finetuning import _vocabulary
+    return _vocabulary(dataset)
+
+
+_LEVELS = ("lexicons50", "lexicons1k", "lexiconsfull")
+
+
+def _with_lexicon(output, target, dataset, file_names):
+    """Per level None (the reference reports 0) or the int32 [n] distances between the chosen RAW word and the normalised target, then
+    the no-lexicon distances [B]; all read back in one copy.  n = min(len(file_names), B), as the reference's zip() cuts."""
+    voc = _voc(dataset)
+    pred, pred_len = tokens_to_text(output, voc)
+    targ, targ_len = tokens_to_text(target.to(output.device), voc)
+    parts = [edit_distance(pred, pred_len, targ, targ_len)]
+    n = min(len(file_names), pred.shape[0])
+    used = []
+    for attr in _LEVELS:
+        if len(file_names) == 0:
+            continue
+        lex = _lexicon(dataset, attr)
+        if len(lex[file_names[0]]) == 0:
+            continue
+        rng = [lex.ranges[f] for f in file_names[:n]]
+        empty = [f for f, r in zip(file_names[:n], rng) if r[1] == 0]
+        if empty:
+            raise ValueError(f"attempt to get argmin of an empty sequence: the {attr} lexicon of {empty[0]!r} is empty")
+        raw, raw_len, norm, norm_len = lex.device(pred.device)
+        best, _ = lexicon_search(pred[:n], pred_len[:n], norm, norm_len, [r[0] for r in rng], [r[1] for r in rng])
+        parts.append(edit_distance(raw, raw_len, targ[:n], targ_len[:n], a_index=best))
+        used.append(attr)
+    vals = torch.cat(parts).tolist()
+    B = pred.shape[0]
+    out = {"none": vals[:B]}
+    for i, attr in enumerate(used):
+        out[attr] = vals[B + i * n:B + (i + 1) * n]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the reference's functions
+def Accuracy(output, target, dataset=None):
+    return float(recognizer.accuracy(output, target, _voc(dataset)).double().item())
+
+
+def recognition_f_measure(output, target, dataset=None):
+    return float(recognizer.recognition_f_measure(output, target, _voc(dataset)).item())
+
+
+def EditDistance(output, target, dataset=None):
+    return int(edit_distances(output, target, _voc(dataset)).sum().item())
+
+
+def Accuracy_with_lexicon(output, target, dataset=None, file_names=None):
+    d = _with_lexicon(output, target, dataset, file_names)
+    return [1.0 * sum(v == 0 for v in d[k]) / len(d[k]) if k in d else 0 for k in ("none",) + _LEVELS]
+
+
+def EditDistance_with_lexicon(output, target, dataset=None, file_names=None):
+    d = _with_lexicon(output, target, dataset, file_names)
+    return [sum(d[k]) if k in d else 0 for k in ("none",) + _LEVELS]
+
+
+def RecPostProcess(output, target, score, dataset=None):
+    voc = _voc(dataset)
+    pred, pred_len = tokens_to_text(output, voc)
+    targ, targ_len = tokens_to_text(target.to(output.device), voc)
+    conf = seq_confidence(score.to(output.device), pred_len)
+    B, T = pred.shape
+    host = torch.cat([pred.reshape(-1).double(), pred_len.double(), targ.reshape(-1).double(), targ_len.double(), conf]).tolist()
+    p, pl, t, tl, c = host[:B * T], host[B * T:B * T + B], host[B * T + B:2 * B * T + B], host[2 * B * T + B:2 * B * T + 2 * B], host[2 * B * T + 2 * B:]
+    strs = lambda cells, lens: ["".join(chr(int(v)) for v in cells[b * T:b * T + int(lens[b])]) for b in range(B)]
+    return strs(p, pl), strs(t, tl), c
+
+
+__factory = {
+    'accuracy': Accuracy,
+    'editdistance': EditDistance,
+    'accuracy_with_lexicon': Accuracy_with_lexicon,
+    'editdistance_with_lexicon': EditDistance_with_lexicon,
+    'recognition_fmeasure': recognition_f_measure,
+}
+
+
+def names():
+    return sorted(__factory.keys())
+
+
+def factory():
+    return __factory

@@ -523,6 +523,37 @@ int dig_seq_cross_entropy(const float* input, const long long* target, const lon
 /* recognition_f_measure (evaluation_metric/metrics.py:83-100) per sample, double precision; same canon table as dig_string_match. */
 int dig_char_fmeasure(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos, int B, int T,
                       double* f_per_sample, hipStream_t stream);
+/* ---- the rest of evaluation_metric/metrics.py on device strings.  A device string is a row of int32 code points plus an int32 length;
+ * a length outside [0, leading dimension] is clamped in the kernels.
+ * dig_tokens_to_text: the normalised string of get_str_list (:19-64) of every row of tokens ([B][T] int64 class ids): cut at `eos`, classes
+ * with canon 0 and ids outside [0, n_classes) dropped, the rest as lower-case ASCII code points ('0'-'9', 'a'-'z'; the canon table of
+ * dig_string_match).  text: [B][T] (cells past the length are zero), len: [B]. */
+int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text, int* len,
+                       hipStream_t stream);
+#define DIG_LEV_MAX_LEN 128
+/* Levenshtein distance (unit costs: what editdistance.eval computes, :145) of n pairs: dist[i] = d(a row, b[i]), where the a row is
+ * a[a_index[i]] when a_index is given (an int32 [n]; an index outside [0, a_rows) reads as the empty string: the "no word" -1 of the
+ * search) and a[i] otherwise (then a_rows >= n).  a: [a_rows][lda], b: [n][ldb]; lda or ldb above DIG_LEV_MAX_LEN:
+ * DIG_ERR_UNSUPPORTED. */
+int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const int* a_index /* nullable */, const int* b,
+                      const int* b_len, int ldb, int n, int* dist, hipStream_t stream);
+/* _lexicon_search (:67-73) for B queries at once: query b ([B][ldq] + query_len) is compared with the words lex_begin[b] ..
+ * lex_begin[b] + lex_count[b] - 1 of the pool words [W][ldw] + word_len (ranges of different queries may coincide, overlap or be
+ * disjoint); best_index[b] = the pool index of the FIRST word of the range at the smallest distance (np.argmin, :72), best_dist[b] that
+ * distance; both -1 for an empty range.  A range is clamped to the pool and to max_count words in the kernel; the caller checks it
+ * beforehand.  max_count >= every lex_count sizes the grid: a range is cut into chunks of DIG_LEXICON_CHUNK words, one workgroup per
+ * (chunk, query), which leaves its smallest (distance, index) pair in the workspace; a second launch takes the smallest pair per
+ * query.  The pairs are distinct and totally ordered, so the result does not depend on the cut.  ldq or ldw above DIG_LEV_MAX_LEN,
+ * or B above 65535: DIG_ERR_UNSUPPORTED.  workspace: 8-byte aligned, dig_lexicon_search_workspace_bytes(B, max_count) =
+ * B * max(1, ceil(max_count / DIG_LEXICON_CHUNK)) * 8 bytes; no initialisation needed. */
+#define DIG_LEXICON_CHUNK 64
+long long dig_lexicon_search_workspace_bytes(int B, int max_count);
+int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, const int* words, const int* word_len, int ldw, int W,
+                       const int* lex_begin, const int* lex_count, int max_count, int* best_index, int* best_dist, void* workspace,
+                       long long workspace_bytes, hipStream_t stream);
+/* RecPostProcess (:189-202): conf[b] = exp(sum_{j < n} log(score[b][j])) in double, summed in index order, n = min(T, text_len[b] + 1)
+ * with text_len the length of the NORMALISED prediction (dig_tokens_to_text), as the reference counts it.  score: [B][T] fp32. */
+int dig_seq_confidence(const float* score, const int* text_len, int B, int T, double* conf, hipStream_t stream);
 
 /* ---- fine-tune training step (drop rates 0)
  * Whole-sequence attention of the recognition decoder and its gradient (models/transformer_layer.py:238-281 under teacher forcing,
