@@ -93,6 +93,39 @@ def join(flats, slots, names, state):
             view(f, slot).copy_(st[k])
 
 
+def group_names(groups):
+    """The parameter names of an optimizer's groups, group by group: position = torch.optim's parameter index."""
+    return [n for g in groups for n in g["names"]]
+
+
+def optimizer_state_dict(moments, slots, groups, step, stateless=()):
+    """A fused optimizer's checkpoint in torch.optim's per-parameter layout (what the reference's checkpoints hold, custom_optim/optimizer.py
+    state_dict): {'state': {i: {'step', moment views}}, 'param_groups': [{..., 'params': [i, ...]}]} with i enumerating the groups' "names" group
+    by group.  moments: {key: flat arena}; step: the one step counter (0: no state yet); stateless: names that hold an index but no state."""
+    state = split(moments, slots, group_names(groups), stateless) if step > 0 else {}
+    for st in state.values():
+        st["step"] = step
+    out, k = [], 0
+    for g in groups:
+        d = {key: v for key, v in g.items() if key not in ("params", "names")}
+        d.setdefault("amsgrad", False)
+        d["params"] = list(range(k, k + len(g["names"])))
+        k += len(g["names"])
+        out.append(d)
+    return {"state": state, "param_groups": out}
+
+
+def load_optimizer_state(moments, slots, groups, sd):
+    """The reverse of optimizer_state_dict: checks the group shapes, writes the moments back (join) and returns the step counter."""
+    if [len(g["params"]) for g in sd["param_groups"]] != [len(g["names"]) for g in groups]:
+        raise ValueError("loaded state dict has different parameter groups")
+    join(moments, slots, group_names(groups), sd["state"])
+    steps = {int(st["step"]) for st in sd["state"].values()}
+    if len(steps) > 1:
+        raise ValueError("per-parameter step counts differ; the fused optimizer keeps one step counter")
+    return steps.pop() if steps else 0
+
+
 def fused(flat, slots, first, count):
     """`count` [out, in] weights registered from `first` on as one [count * out, in] matrix (q|k|v, k|v): they must lie back to back."""
     names = list(slots)

@@ -8,15 +8,15 @@ Same state-dict keys as the reference (`decoder.decoder.attention_unit.{sEmbed,x
 `decoder.decoder.gru.{weight,bias}_{ih,hh}_l0`, `decoder.decoder.fc.*`).  Flat arenas, one autograd node, the encoder on the
 pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head's steps run on `dig_gemm_bf16` + `dig_addattn_*` +
 `dig_gru_cell_*` (csrc/gru_attn.hip), weight gradients as ONE GEMM per weight over the stacked steps.  Beam search is not built."""
-import ctypes
 import math
+import types
 
 import torch
 
 from . import _lib as L
 from . import ops
 from .arena import encoder_shapes
-from .finetune import RecModelTrain, _TrainStep, CLS_PAD
+from .finetune import RecModelTrain, _TrainStep, CLS_PAD, encoder_plan
 from .recognizer import ENCODERS
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -30,6 +30,28 @@ class _AttnTrainStep(_TrainStep):
         M = self.m
         A, S, X, E, C = M.attDim, M.sDim, M.D, M.attDim, M.nb_classes
         return A, S, X, E, C
+
+    def head_inputs(self, x):
+        """What every step of the head reads: the encoder tokens x [B*N, X], xEmbed(x) [B*N, A], the wEmbed vector [A], and the sEmbed / GRU
+        weights, looked up once."""
+        p, w = self.p, self.w
+        xproj = ops.linear_fwd(x, w(PRE + "attention_unit.xEmbed.weight"), bias=p(PRE + "attention_unit.xEmbed.bias"))
+        wv = p(PRE + "attention_unit.wEmbed.weight").reshape(self.m.attDim).contiguous()
+        return types.SimpleNamespace(x=x, xproj=xproj, wv=wv, ws=w(PRE + "attention_unit.sEmbed.weight"), bs=p(PRE + "attention_unit.sEmbed.bias"),
+                                     wih=w(PRE + "gru.weight_ih_l0"), bih=p(PRE + "gru.bias_ih_l0"),
+                                     whh=w(PRE + "gru.weight_hh_l0"), bhh=p(PRE + "gru.bias_hh_l0"))
+
+    def gru_attention_step(self, hd, sbf, s_prev, inp, sproj, alpha, s_new, sbf_new, gates):
+        """One DecoderUnit step (attn_decoder.py:236-272) from the state sbf (bf16; s_prev: the same in fp32, None = zeros): sEmbed(state) ->
+        additive attention over the tokens, whose context lands in inp[:, E:] behind the target embedding the caller put into inp[:, :E] ->
+        the two gate GEMMs -> the GRU cell.  Writes sproj, alpha, gates and the new state (s_new fp32, sbf_new bf16)."""
+        A, S, X, E, _ = self._w()
+        B, N = sbf.shape[0], self.m.N
+        ops.linear_fwd(sbf, hd.ws, bias=hd.bs, out=sproj)
+        L.call("dig_addattn_fwd", L.ptr(hd.xproj), L.ptr(sproj), L.ptr(hd.wv), L.ptr(hd.x), L.ptr(alpha), L.ptr(inp[:, E:]), E + X, B, N, A, X, L.stream())
+        gi = ops.linear_fwd(inp, hd.wih, bias=hd.bih)
+        gh = ops.linear_fwd(sbf, hd.whh, bias=hd.bhh)
+        L.call("dig_gru_cell_fwd", L.ptr(gi), L.ptr(gh), L.ptr(s_prev), L.ptr(s_new), L.ptr(sbf_new), L.ptr(gates), B, S, L.stream())
 
     def forward(self, images, targets, lens):
         M = self.m
@@ -45,36 +67,25 @@ class _AttnTrainStep(_TrainStep):
         logits = torch.zeros((B, M.max_len, C), device=dev, dtype=F32)
         if steps == 0:
             return logits
-        p, w = self.p, self.w
-        xproj = ops.linear_fwd(x, w(PRE + "attention_unit.xEmbed.weight"), bias=p(PRE + "attention_unit.xEmbed.bias"))   # [B*N, A]
-        wv = p(PRE + "attention_unit.wEmbed.weight").reshape(A).contiguous()
+        hd = self.head_inputs(x)
         # teacher forcing: every step's previous token is known up front (attn_decoder.py:46-50): <BOS> = num_classes, then targets[:, i-1]
         yprev = torch.cat([torch.full((B, 1), C, device=dev, dtype=torch.int64), self.targets[:, :steps - 1]], 1).t().contiguous()   # [steps, B]
         inp = torch.empty((steps, B, E + X), device=dev, dtype=BF16)          # GRU inputs [yProj | context] of every step
-        L.call("dig_embed_rows", L.ptr(yprev), L.ptr(p(PRE + "tgt_embedding.weight")), L.ptr(inp), E + X, steps * B, E, C + 1, L.stream())
+        L.call("dig_embed_rows", L.ptr(yprev), L.ptr(self.p(PRE + "tgt_embedding.weight")), L.ptr(inp), E + X, steps * B, E, C + 1, L.stream())
         s_all = torch.empty((steps, B, S), device=dev, dtype=F32)
         sbf_all = torch.empty((steps + 1, B, S), device=dev, dtype=BF16)      # sbf_all[t] = state BEFORE step t (row 0 = zeros)
         sbf_all[0].zero_()
         sproj_all = torch.empty((steps, B, A), device=dev, dtype=BF16)
         alpha_all = torch.empty((steps, B, N), device=dev, dtype=F32)
         gates_all = torch.empty((steps, B, 4 * S), device=dev, dtype=F32)
-        wih, whh = w(PRE + "gru.weight_ih_l0"), w(PRE + "gru.weight_hh_l0")
-        bih, bhh = p(PRE + "gru.bias_ih_l0"), p(PRE + "gru.bias_hh_l0")
-        ws_, bs_ = w(PRE + "attention_unit.sEmbed.weight"), p(PRE + "attention_unit.sEmbed.bias")
         for t in range(steps):
-            ops.linear_fwd(sbf_all[t], ws_, bias=bs_, out=sproj_all[t])
-            L.call("dig_addattn_fwd", L.ptr(xproj), L.ptr(sproj_all[t]), L.ptr(wv), L.ptr(x), L.ptr(alpha_all[t]), L.ptr(inp[t][:, E:]), E + X,
-                   B, N, A, X, L.stream())
-            gi = ops.linear_fwd(inp[t], wih, bias=bih)
-            gh = ops.linear_fwd(sbf_all[t], whh, bias=bhh)
-            L.call("dig_gru_cell_fwd", L.ptr(gi), L.ptr(gh), L.ptr(s_all[t - 1]) if t else None, L.ptr(s_all[t]), L.ptr(sbf_all[t + 1]),
-                   L.ptr(gates_all[t]), B, S, L.stream())
+            self.gru_attention_step(hd, sbf_all[t], s_all[t - 1] if t else None, inp[t], sproj_all[t], alpha_all[t], s_all[t], sbf_all[t + 1], gates_all[t])
         # classifier for all steps at once (rows (t, b))
         self.cls_w, cb = M.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
         out = torch.empty((steps * B, CLS_PAD), device=dev, dtype=F32)
         ops.gemm(sbf_all[1:].reshape(steps * B, S), self.cls_w, steps * B, CLS_PAD, S, out=out, out_kind=ops.OUT_F32, bias=cb)
         logits[:, :steps] = out.view(steps, B, CLS_PAD)[:, :, :C].transpose(0, 1)
-        self.saved = (xproj, wv, yprev, inp, s_all, sbf_all, sproj_all, alpha_all, gates_all)
+        self.saved = (hd.xproj, hd.wv, yprev, inp, s_all, sbf_all, sproj_all, alpha_all, gates_all)
         return logits
 
     def backward(self, dlogits_btc):
@@ -95,12 +106,8 @@ class _AttnTrainStep(_TrainStep):
         # classifier (all steps): dout rows (t, b)
         dl = torch.zeros((rows, CLS_PAD), device=dev, dtype=BF16)
         dl.view(steps, B, CLS_PAD)[:, :, :C] = dlogits_btc[:, :steps].transpose(0, 1).to(BF16)
-        snew = sbf_all[1:].reshape(rows, S)
-        side(lambda: ops.wgrad(dl, snew, g(PRE + "fc.weight"), C, S, rows), dl, snew)
-        cs = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), g(PRE + "fc.bias").add_(cs[:C])), dl, cs)
-        ds_fc = torch.empty((rows, S), device=dev, dtype=F32)                 # classifier path into every step's new state
-        ops.gemm(dl, self.cls_w, rows, S, CLS_PAD, tb=True, out=ds_fc, out_kind=ops.OUT_F32)
+        # classifier path into every step's new state
+        ds_fc = self.classifier_backward(dl, sbf_all[1:].reshape(rows, S), PRE + "fc.weight", PRE + "fc.bias", out_kind=ops.OUT_F32)
         ds_fc = ds_fc.view(steps, B, S)
         wih, whh, ws_ = w(PRE + "gru.weight_ih_l0"), w(PRE + "gru.weight_hh_l0"), w(PRE + "attention_unit.sEmbed.weight")
         dgi_all = torch.empty((steps, B, 3 * S), device=dev, dtype=BF16)
@@ -204,17 +211,12 @@ class AttnRecModelTrain(RecModelTrain):
         if self._dev != dev or self._shadow is None:
             self._bind(dev)
         step = _AttnTrainStep(self)
-        saved = (self.drop_rate, self.attn_drop_rate, self.dpr, self.drop_step)
-        self.drop_rate, self.attn_drop_rate, self.dpr = 0.0, 0.0, [0.0] * self.depth    # eval mode: no dropout
-        try:
-            x = step.encoder_forward(images)
-        finally:
-            self.drop_rate, self.attn_drop_rate, self.dpr, self.drop_step = saved
-        B, N = step.B, self.N
+        self.refresh_shadow()
+        B, N = images.shape[0], self.N
+        # eval mode: the training step's walk without dropout keys (and, like it, with the blocks' activations kept)
+        x, _ = self.encoder_front(images, encoder_plan(self, B * N), True, frozen=self.frozen_blocks)
         A, S, X, E, C = step._w()
-        p, w = step.p, step.w
-        xproj = ops.linear_fwd(x, w(PRE + "attention_unit.xEmbed.weight"), bias=p(PRE + "attention_unit.xEmbed.bias"))
-        wv = p(PRE + "attention_unit.wEmbed.weight").reshape(A).contiguous()
+        hd = step.head_inputs(x)
         cls_w, cb = self.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
         probs = torch.empty((B, self.max_len, C), device=dev, dtype=F32)
         s = torch.zeros((B, S), device=dev, dtype=F32)
@@ -226,15 +228,11 @@ class AttnRecModelTrain(RecModelTrain):
         logit = torch.empty((B, CLS_PAD), device=dev, dtype=F32)
         tok = torch.empty((B,), device=dev, dtype=torch.int64)
         pbuf = torch.empty((B, C), device=dev, dtype=F32)
+        emb = step.p(PRE + "tgt_embedding.weight")
         for t in range(self.max_len):
-            sproj = ops.linear_fwd(sbf, w(PRE + "attention_unit.sEmbed.weight"), bias=p(PRE + "attention_unit.sEmbed.bias"))
-            L.call("dig_embed_rows", L.ptr(y), L.ptr(p(PRE + "tgt_embedding.weight")), L.ptr(inp), E + X, B, E, C + 1, L.stream())
-            L.call("dig_addattn_fwd", L.ptr(xproj), L.ptr(sproj), L.ptr(wv), L.ptr(x), L.ptr(alpha), L.ptr(inp[:, E:]), E + X, B, N, A, X, L.stream())
-            gi = ops.linear_fwd(inp, w(PRE + "gru.weight_ih_l0"), bias=p(PRE + "gru.bias_ih_l0"))
-            gh = ops.linear_fwd(sbf, w(PRE + "gru.weight_hh_l0"), bias=p(PRE + "gru.bias_hh_l0"))
-            s_new = torch.empty_like(s)
-            sbf_new = torch.empty_like(sbf)
-            L.call("dig_gru_cell_fwd", L.ptr(gi), L.ptr(gh), L.ptr(s), L.ptr(s_new), L.ptr(sbf_new), L.ptr(gates), B, S, L.stream())
+            L.call("dig_embed_rows", L.ptr(y), L.ptr(emb), L.ptr(inp), E + X, B, E, C + 1, L.stream())
+            s_new, sbf_new, sproj = torch.empty_like(s), torch.empty_like(sbf), torch.empty((B, A), device=dev, dtype=BF16)
+            step.gru_attention_step(hd, sbf, s, inp, sproj, alpha, s_new, sbf_new, gates)
             s, sbf = s_new, sbf_new
             ops.gemm(sbf, cls_w, B, CLS_PAD, S, out=logit, out_kind=ops.OUT_F32, bias=cb)
             L.call("dig_softmax_argmax", L.ptr(logit), CLS_PAD, L.ptr(pbuf), L.ptr(tok), B, C, L.stream())

@@ -67,6 +67,11 @@ def _mark(name, dev):
         PHASE_MARKS.append((name, ev))
 
 
+# the head stacks of the two branches: (arena, pix_projector, patch_extractor, projection layer, predictor)
+ONLINE_HEADS = ("online", "pix_projector", "patch_extractor", "encoder_projection_layer", "predictor")
+MOMENTUM_HEADS = ("momentum", "pix_projector_m", "momentum_patch_extractor", "momentum_projection_layer", None)
+
+
 class _EncWeights:
     """Per-encoder (online / momentum) accessors resolved once per arena binding."""
 
@@ -159,6 +164,14 @@ class _Step:
                 ops.transpose_bf16(w16[name], dst)
             self.head_wT = tr[6]
         return list(zip(w2t, w1t, projt, qkvt))
+
+    def _backward_transposes(self, ew, training, rows, fresh):
+        """mlp_weight_transposes where the backward over `rows` encoder rows reads them (the fused MLP backward's operands; the direct-form data
+        gradients), else None."""
+        M = self.m
+        if training and ((ops.mlp_chain_supported(M.D, M.F, rows) and (ops.MLP_CHAIN_MASK & 4)) or (ops.DGRAD_DIRECT and rows >= 8192)):
+            return self.mlp_weight_transposes(ew, fresh)
+        return None
 
     # ------------------------------------------------------------------ two-stream helpers (backward)
     def _streams(self, dev):
@@ -290,45 +303,32 @@ class _Step:
         self.comm.grad_ready(M, "encoder.embed")
 
     # ------------------------------------------------------------------ BN-MLP heads
-    def mlp_forward(self, x, pre, arena, save):
-        """_build_mlp stack (modeling_pretrain_moco_mim_ori.py:463-482): Linear(no bias) -> BN(train, cross-rank stats)
-        -> ReLU ... ; the last BN has no affine parameters."""
+    def mlp_forward(self, stacks):
+        """_build_mlp stacks (modeling_pretrain_moco_mim_ori.py:463-482: Linear(no bias) -> BN(train, cross-rank stats) -> ReLU ... ; the last BN
+        has no affine parameters) of the same layer widths, given as [(x, prefix, arena, save)] and run layer by layer in lock step: the
+        cross-rank BatchNorm statistics of a layer travel in ONE all-reduce ([stacks, 2, C]) -- with the online head and its momentum twin as
+        the two stacks, 14 -> 8 latency-bound collectives per forward, all issued from one stream in program order (the all-reduce is
+        elementwise: the same arithmetic per stack as on its own).  What the backward of a `save` stack needs is kept in
+        self.saved_heads[prefix].  Returns the stacks' outputs."""
         M = self.m
-        dims = M.mlps[pre]
-        w16 = M._w(arena)
-        saved = []
+        dims = M.mlps[stacks[0][1]]
+        assert all(M.mlps[pre] == dims for _, pre, _, _ in stacks)
+        xs = [x for x, _, _, _ in stacks]
+        saved = [[] for _ in stacks]
         for l in range(len(dims)):
             last = l == len(dims) - 1
-            h = ops.linear_fwd(x, w16[f"{pre}.{3 * l}.weight"])
-            y, mean, rstd = bn_forward(self, [h], [f"{pre}.{3 * l + 1}"], relu=not last, affine=not last)[0]
-            if save:
-                saved.append((x, h, mean, rstd))
-            x = y
-        return x, saved
-
-    def mlp_forward_pair(self, xa, pre_a, arena_a, save_a, xb, pre_b, arena_b, save_b):
-        """Two BN-MLP stacks of the same layer widths (the online head and its momentum twin) run layer by layer in lock step, so
-        that their cross-rank BatchNorm statistics travel in ONE all-reduce per layer ([2 stacks, 2, C] instead of two [2, C]
-        messages): 14 -> 8 latency-bound collectives per forward, all issued from one stream in program order.  Same arithmetic
-        per stack as mlp_forward (the all-reduce is elementwise), used when there is a process group."""
-        M = self.m
-        dims = M.mlps[pre_a]
-        assert dims == M.mlps[pre_b]
-        xs = [xa, xb]
-        saved = [[], []]
-        for l in range(len(dims)):
-            last = l == len(dims) - 1
-            hs = [ops.linear_fwd(xs[k], M._w(ar)[f"{pre}.{3 * l}.weight"]) for k, (pre, ar) in enumerate(((pre_a, arena_a), (pre_b, arena_b)))]
-            outs = bn_forward(self, hs, [f"{pre}.{3 * l + 1}" for pre in (pre_a, pre_b)], relu=not last, affine=not last)
-            for k, (save, (y, mean, rstd)) in enumerate(zip((save_a, save_b), outs)):
-                if save:
+            hs = [ops.linear_fwd(x, M._w(arena)[f"{pre}.{3 * l}.weight"]) for x, (_, pre, arena, _) in zip(xs, stacks)]
+            outs = bn_forward(self, hs, [f"{pre}.{3 * l + 1}" for _, pre, _, _ in stacks], relu=not last, affine=not last)
+            for k, (y, mean, rstd) in enumerate(outs):
+                if stacks[k][3]:
                     saved[k].append((xs[k], hs[k], mean, rstd))
                 xs[k] = y
-        return (xs[0], saved[0]), (xs[1], saved[1])
+        self.saved_heads.update({pre: kept for (_, pre, _, save), kept in zip(stacks, saved) if save})
+        return xs
 
-    def mlp_backward(self, dy, pre, saved, need_dx=True, dx_out=None):
+    def mlp_backward(self, dy, pre, need_dx=True, dx_out=None):
         M = self.m
-        dims = M.mlps[pre]
+        dims, saved = M.mlps[pre], self.saved_heads[pre]
         w16, g32 = M._w("online"), M._g32
         for l in reversed(range(len(dims))):
             last = l == len(dims) - 1
@@ -358,6 +358,7 @@ class _Step:
         comm = self.comm
         self.B = B
         self._bn_touched = []
+        self.saved_heads = {}                       # prefix of a head stack -> what its backward needs (mlp_forward, patch_extractor)
         images = images.contiguous().float()
         aug = aug.contiguous().float()
         if mask_b2n.dtype == torch.uint8 and mask_b2n.dim() == 2 and tuple(mask_b2n.shape) == (2 * B, N):
@@ -416,30 +417,30 @@ class _Step:
             feat = torch.cat([masked, enc_rows[B * N:]]) if masked.data_ptr() != enc_rows.data_ptr() else enc_rows
             return patchnet.forward(self, feat, pooled, pre, arena, 2 * B, save)
 
-        def online_heads(enc):
+        def heads(encs, branches):
+            """The head pipeline (:500-558) of `branches` (ONLINE_HEADS / MOMENTUM_HEADS) over their encoders' outputs, stage by stage in lock
+            step (mlp_forward): pix_projector -> patch_extractor -> projection layer, then the predictor where a branch has one.  Returns q / k
+            per branch."""
+            def stage(xs, j):
+                return self.mlp_forward([(x, br[j], br[0], br[0] == "online") for x, br in zip(xs, branches)])
             # (`if hasattr(self, 'pix_projector')`, :500-510: the Dis-only models pool the encoder's own rows of both views)
-            masked2, self.saved_pix = self.mlp_forward(enc[:B * N], "pix_projector", "online", True) if pp else (enc[:B * N], None)
-            pooled, self.saved_pnet = extract(masked2, enc, "patch_extractor", "online", True)
-            q, self.saved_proj = self.mlp_forward(pooled, "encoder_projection_layer", "online", True)
-            q, self.saved_pred = self.mlp_forward(q, "predictor", "online", True)
-            return q
+            xs = stage([enc[:B * N] for enc in encs], 1) if pp else [enc[:B * N] for enc in encs]
+            pooled = []
+            for x, enc, br in zip(xs, encs, branches):
+                y, kept = extract(x, enc, br[2], br[0], br[0] == "online")
+                if br[0] == "online":
+                    self.saved_heads[br[2]] = kept
+                pooled.append(y)
+            outs = stage(pooled, 3)
+            return [self.mlp_forward([(x, br[4], br[0], True)])[0] if br[4] else x for x, br in zip(outs, branches)]
 
-        def momentum_heads(enc_m):
-            masked_m = self.mlp_forward(enc_m[:B * N], "pix_projector_m", "momentum", False)[0] if pp else enc_m[:B * N]
-            pooled_m, _ = extract(masked_m, enc_m, "momentum_patch_extractor", "momentum", False)
-            k, _ = self.mlp_forward(pooled_m, "momentum_projection_layer", "momentum", False)
-            return k
-
-        def momentum_branch(heads=True):
+        def momentum_branch(with_heads=True):
             ops.ema_update(M._flat["momentum"], M._flat["online"], M.shadow("momentum"), M.n_ema, m)
-            self.wT = None
-            if training and ((ops.mlp_chain_supported(D, M.F, 2 * B * N) and (ops.MLP_CHAIN_MASK & 4)) or
-                             (ops.DGRAD_DIRECT and 2 * B * N >= 8192)):
-                # K-contiguous copies of the online weights for the backward (the fused MLP backward's operands; the direct-form data
-                # gradients): left by the optimizer launch, or rebuilt here in front of the momentum encoder from this step's shadow
-                self.wT = self.mlp_weight_transposes(ew_on, fresh)
+            # K-contiguous copies of the online weights for the backward: left by the optimizer launch, or rebuilt here in front of the momentum
+            # encoder from this step's shadow
+            self.wT = self._backward_transposes(ew_on, training, 2 * B * N, fresh)
             enc_m, _ = self.encoder_forward(ew_mo, images, aug, mask_u8, False, path=self.path_mo)
-            return enc_m, (momentum_heads(enc_m) if heads else None)
+            return enc_m, (heads([enc_m], [MOMENTUM_HEADS])[0] if with_heads else None)
 
         def decoder():
             # SimMIM decoder on the masked tokens (:560-570; the reference decodes all rows then selects): view 0 only, or both views
@@ -459,7 +460,7 @@ class _Step:
             with torch.cuda.stream(hi_st):
                 enc, self.saved_enc = self.encoder_forward(ew_on, images, aug, mask_u8, True, path=self.path_on)
                 self.enc = enc
-                qs = online_heads(enc)
+                qs = heads([enc], [ONLINE_HEADS])[0]
             # (Measured and not kept, round 4: the SimMIM decoder right behind the online heads instead of after the join: 21.06 vs 21.07 ms.)
             # (Measured and not kept, round 4: the online heads + SimMIM decoder held back until both encoders are done, so that they run
             #  beside the momentum heads instead of between the encoders: 21.84 vs 21.77 ms, two A/B pairs.)
@@ -471,11 +472,11 @@ class _Step:
             # here) and the inputs.  EMA with the current online weights comes first (:526).
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                enc_m, ks = momentum_branch(heads=not dist_mode)
+                enc_m, ks = momentum_branch(with_heads=not dist_mode)
             enc, self.saved_enc = self.encoder_forward(ew_on, images, aug, mask_u8, True, path=self.path_on)
             self.enc = enc
             if not dist_mode:
-                qs = online_heads(enc)
+                qs = heads([enc], [ONLINE_HEADS])[0]
                 main.wait_stream(side)
                 if side is not main:
                     ks.record_stream(main)
@@ -486,17 +487,8 @@ class _Step:
                 # online branch's first one on RCCL's in-order stream)
                 main.wait_stream(side)
                 enc_m.record_stream(main)
-                if pp:
-                    (masked2, self.saved_pix), (masked_m, _) = self.mlp_forward_pair(enc[:B * N], "pix_projector", "online", True,
-                                                                                      enc_m[:B * N], "pix_projector_m", "momentum", False)
-                else:
-                    masked2, self.saved_pix, masked_m = enc[:B * N], None, enc_m[:B * N]
-                pooled, self.saved_pnet = extract(masked2, enc, "patch_extractor", "online", True)
-                pooled_m, _ = extract(masked_m, enc_m, "momentum_patch_extractor", "momentum", False)
-                (qs, self.saved_proj), (ks, _) = self.mlp_forward_pair(pooled, "encoder_projection_layer", "online", True,
-                                                                        pooled_m, "momentum_projection_layer", "momentum", False)
-                qs, self.saved_pred = self.mlp_forward(qs, "predictor", "online", True)
-                del enc_m, masked_m, pooled_m
+                qs, ks = heads([enc, enc_m], [ONLINE_HEADS, MOMENTUM_HEADS])
+                del enc_m
         _mark("forward: both encoders + heads joined", dev)
         M._flat["bn_count"] += 1                                            # all 14 (Dis-only: 8) BatchNorm layers ran once
         # ---- InfoNCE (:444-461): q1 vs gathered k2, q2 vs gathered k1, labels = arange + n*rank
@@ -564,10 +556,7 @@ class _Step:
         dev = images.device
         views = mim_views
         self.gen_views = views
-        self.wT = None
-        if training and ((ops.mlp_chain_supported(M.D, M.F, views * self.B * M.N) and (ops.MLP_CHAIN_MASK & 4)) or
-                         (ops.DGRAD_DIRECT and views * self.B * M.N >= 8192)):
-            self.wT = self.mlp_weight_transposes(ew_on, fresh)
+        self.wT = self._backward_transposes(ew_on, training, views * self.B * M.N, fresh)
         enc_raw, self.saved_enc = self.encoder_forward(ew_on, images, aug, mask_u8, True, views=views, path=self.path_on)
         f32 = M._f32
         self.enc, mu, rs = ops.layernorm_fwd(enc_raw, f32["encoder.norm.weight"], f32["encoder.norm.bias"], M.ln_eps)
@@ -602,32 +591,32 @@ class _Step:
             dq = ops.l2norm_bwd(dqn, self.qn, self.q_inv)
             dq16 = torch.empty(dq.shape, device=dev, dtype=BF16)
             ops.cast_f32_to_bf16(dq, dq16)
-            dproj = self.mlp_backward(dq16, "predictor", self.saved_pred)
+            dproj = self.mlp_backward(dq16, "predictor")
             self._grad_ready(dev, "predictor")
-            dpool = self.mlp_backward(dproj, "encoder_projection_layer", self.saved_proj)
+            dpool = self.mlp_backward(dproj, "encoder_projection_layer")
             self._grad_ready(dev, "encoder_projection_layer")
             acc = False
             if M.patchnet == 'regular':
                 # the patch transformer's backward: d(pooled windows) and the gradient w.r.t. the image tokens through both blocks' keys /
                 # values -- [masked view | augmented view] rows, written where the pooling gradient is then ADDED
                 from . import patchnet
-                dpool, dfeat = patchnet.backward(self, dpool, "patch_extractor", self.saved_pnet, 2 * B)
+                dpool, dfeat = patchnet.backward(self, dpool, "patch_extractor", self.saved_heads["patch_extractor"], 2 * B)
                 self._grad_ready(dev, "patch_extractor")
                 d_enc, acc = dfeat, True
             if M.patchnet == 'conv':
                 # ConvPatchNet's backward hands the gradient w.r.t. the token maps of [masked view | augmented view] straight back
                 from . import convpatchnet
-                d_enc = convpatchnet.backward(self, dpool, "patch_extractor", self.saved_pnet, 2 * B)
+                d_enc = convpatchnet.backward(self, dpool, "patch_extractor", self.saved_heads["patch_extractor"], 2 * B)
                 self._grad_ready(dev, "patch_extractor")
                 if M.has_pix_projector:
-                    self.mlp_backward(d_enc[:B * N], "pix_projector", self.saved_pix, dx_out=d_enc[:B * N])
+                    self.mlp_backward(d_enc[:B * N], "pix_projector", dx_out=d_enc[:B * N])
                     self._grad_ready(dev, "pix_projector")
             elif M.has_pix_projector:
                 dmasked2 = d_enc[:B * N] if acc else torch.empty((B * N, D), device=dev, dtype=BF16)
                 ops.window_pool_bwd(dpool[:n], dmasked2, B, M.gh, M.gw, nw, D, acc)
                 ops.window_pool_bwd(dpool[n:], d_enc[B * N:], B, M.gh, M.gw, nw, D, acc)
                 # (regular: the incoming gradient lives in d_enc's own first half; the stack's last data gradient overwrites it when it is done with it)
-                self.mlp_backward(dmasked2, "pix_projector", self.saved_pix, dx_out=d_enc[:B * N])
+                self.mlp_backward(dmasked2, "pix_projector", dx_out=d_enc[:B * N])
                 self._grad_ready(dev, "pix_projector")
             else:
                 ops.window_pool_bwd(dpool[:n], d_enc[:B * N], B, M.gh, M.gw, nw, D, acc)
@@ -677,7 +666,7 @@ class _Step:
         _mark("backward: encoder done, streams joined", dev)
         self._keep.clear()                          # (blocks go back to the caller's stream's pool: its later work is ordered behind the join)
         self._keep_marks.clear()
-        self.saved_enc = self.saved_pix = self.saved_proj = self.saved_pred = self.saved_dec = self.saved_norm = self.saved_pnet = self.wT = None
+        self.saved_enc = self.saved_heads = self.saved_dec = self.saved_norm = self.wT = None
 
 
 class _DigFn(torch.autograd.Function):

@@ -24,7 +24,7 @@ from . import arena
 from . import dropout as DR
 from . import encoder_blocks as EB
 from . import ops
-from .recognizer import RecModel
+from .recognizer import RecModel, SeqCrossEntropyLoss, SeqLabelSmoothingCrossEntropyLoss  # noqa: F401  (the criteria of this step)
 
 BF16, F32 = torch.bfloat16, torch.float32
 cf = ctypes.c_float
@@ -34,6 +34,12 @@ FT_FUSED_QV = os.environ.get("DIG_FT_FUSED_QV", "1") != "0"
 FT_MLP_CHAIN = os.environ.get("DIG_FT_MLP_CHAIN", "1") != "0"
 FT_BATCH_REDUCE = os.environ.get("DIG_FT_BATCH_REDUCE", "0") == "1"      # opt-in: fewer launches, ~0.3 ms slower per step
 CLS_PAD = 128                     # classifier rows padded to a multiple of 64 (it is a non-transposed GEMM operand in backward)
+
+
+def encoder_plan(M, rows):
+    """The encoder walk of a fine-tune forward over `rows` token rows: with the chain, the LayerNorm behind a block (the next norm1 / the final
+    norm) rides along."""
+    return EB.Plan(chain_ln=FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(M.D, M.F, rows))
 
 
 def _ref(spec):
@@ -268,37 +274,24 @@ class _TrainStep:
             t.record_stream(self._side_st)
 
     def encoder_forward(self, images):
-        """PretrainVisionTransformerEncoder.forward (modeling_pretrain_vit.py:89-112, mask=None) on the pre-training hot-path kernels;
-        returns the normalised tokens [B*N, D] (bf16) and keeps what `encoder_backward` needs."""
+        """RecModel.encoder_front under this step's dropout / drop-path keys; returns the normalised tokens [B*N, D] (bf16) and keeps what
+        `encoder_backward` needs."""
         M = self.m
-        dev = images.device
         M.refresh_shadow()
-        D, H, N = M.D, M.H, M.N
-        B = images.shape[0]
-        self.B, self.images = B, images.contiguous().float()
-        self.zmask = torch.zeros((B, N), device=dev, dtype=torch.uint8)
-        # ---- encoder (PretrainVisionTransformerEncoder.forward_features, mask=None) -- the pre-training hot-path kernels
-        x = ops.patch_embed_fwd(self.images, self.p("encoder.patch_embed.proj.weight").view(D, 48), self.p("encoder.patch_embed.proj.bias"),
-                                self.zmask, self.p("encoder.mask_token").view(D), M._w["enc_pos"], D, M.gh, M.gw)
+        N = M.N
+        self.B = images.shape[0]
         # dropout / drop-path keys of this step (dig_amd/dropout.py); every spec is None when its rate is 0
         plan = self.plan = DR.DropPlan(M.drop_seed, M.drop_step)
         M.drop_step += 1
         pe, pa = M.drop_rate, M.attn_drop_rate
-        self.ds_pos = None                              # PretrainVisionTransformerEncoder has no pos_drop (modeling_pretrain_vit.py:89-106)
         self.ds_enc = [(plan.spec(DR.enc_site(i, 0), pa),                                            # (attention, proj branch, MLP branch)
                         plan.spec(DR.enc_site(i, 1), pe, DR.enc_site(i, 2), M.dpr[i], N),
                         plan.spec(DR.enc_site(i, 3), pe, DR.enc_site(i, 4), M.dpr[i], N)) for i in range(M.depth)]
-        x = ops.dropout_apply(x, self.ds_pos, out=x)
-        self.use_chain = FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(D, M.F, B * N)
-        # x + drop_path(proj_drop(proj(.))) / x + drop_path(drop(fc2(.))) (modeling_finetune.py:120,59,156-158): GEMM epilogues.  With the chain, the
-        # LayerNorm behind a block (the next norm1 / the final norm) rides along; no gradient flows into a frozen block: nothing of it is kept
-        x, self.enc_saved, ln_next = EB.forward(EB.Plan(chain_ln=self.use_chain), M.enc_blocks(), x, B, H, 1e-6, True, drops=self.ds_enc,
-                                                tail=(self.p("encoder.norm.weight"), self.p("encoder.norm.bias")), frozen=M.frozen_blocks)
-        if ln_next is not None:
-            enc, emu, ers = ln_next
-        else:
-            enc, emu, ers = ops.layernorm_fwd(x, self.p("encoder.norm.weight"), self.p("encoder.norm.bias"), 1e-6)
-        self.enc_last = (x, emu, ers, enc)
+        # x + drop_path(proj_drop(proj(.))) / x + drop_path(drop(fc2(.))) (modeling_finetune.py:120,59,156-158): GEMM epilogues.  No gradient flows
+        # into a frozen block: nothing of it is kept
+        eplan = encoder_plan(M, self.B * N)
+        self.use_chain = eplan.chain_ln
+        enc, (self.images, self.zmask, self.enc_saved, self.enc_last) = M.encoder_front(images, eplan, True, drops=self.ds_enc, frozen=M.frozen_blocks)
         return enc
 
     # ---------------------------------------------------------------- forward
@@ -308,11 +301,8 @@ class _TrainStep:
         enc = self.encoder_forward(images)
         D, H, N = M.D, M.H, M.n_mem                                           # N: memory tokens per sample the decoder attends over
         B = self.B
-        if M.use_1d_attdec:                                                   # model_builder.py:145-148: column means of the 8 x 32 grid
-            cols = torch.empty((B * M.gw, D), device=dev, dtype=BF16)
-            ops.window_pool_fwd(enc, cols, B, M.gh, M.gw, M.gw, D)
-            enc = cols
-        self.mem_in = enc
+        mem, (self.mem_in, h, mmu, mrs) = M.linear_norm(enc)
+        self.ln_saved = (h, mmu, mrs, mem)
         T, d, nh, dk = M.max_len, M.d, M.nh, M.dk
         hk = nh * dk
         plan = self.plan
@@ -321,10 +311,6 @@ class _TrainStep:
         self.ds_dec = [dict(sattn=plan.spec(DR.dec_site(i, 0), pd), sproj=plan.spec(DR.dec_site(i, 1), pd),
                             cattn=plan.spec(DR.dec_site(i, 2), pd), cproj=plan.spec(DR.dec_site(i, 3), pd),
                             act=plan.spec(DR.dec_site(i, 4), pd), out=plan.spec(DR.dec_site(i, 5), pd)) for i in range(M.n_layers)]
-        # ---- linear_norm
-        h = ops.linear_fwd(enc, self.w("linear_norm.0.weight"), bias=self.p("linear_norm.0.bias"))
-        mem, mmu, mrs = ops.layernorm_fwd(h, self.p("linear_norm.1.weight"), self.p("linear_norm.1.bias"), 1e-5)
-        self.ln_saved = (h, mmu, mrs, mem)
         # ---- decoder, teacher forcing (decoder.py:196-222)
         bos = torch.full((B, 1), M.start_idx, device=dev, dtype=torch.int64)
         query = torch.cat([bos, targets.long()], dim=-1)[:, :-1].contiguous()
@@ -417,10 +403,19 @@ class _TrainStep:
         dx = EB.backward(plan, blocks, self.enc_saved, dx, wT, self.B, H, self.side, first=M.frozen_blocks, drops=self.ds_enc)
         if "encoder.patch_embed.proj.weight" in M.frozen:
             return
-        dx = ops.dropout_apply(dx, self.ds_pos, out=dx)
         gtok = torch.zeros(D, device=dev, dtype=F32)                          # mask_token takes no part at fine-tune: gradient discarded
         ops.patch_embed_bwd_mfma(dx, self.images, self.zmask, self.g("encoder.patch_embed.proj.weight").view(D, 48),
                                  self.g("encoder.patch_embed.proj.bias"), gtok, D, M.gh, M.gw)
+
+    def classifier_backward(self, dl, o, weight, bias, out_kind=ops.OUT_BF16):
+        """The backward of the classifier zero-padded to CLS_PAD rows (self.cls_w): dl bf16 [rows, CLS_PAD], the gradient of its logits with
+        zero pad columns; o [rows, d], its input.  Weight and bias gradients on the second stream (the column sums through a padded vector);
+        returns the gradient w.r.t. o, bf16 or (out_kind = ops.OUT_F32) fp32."""
+        C, (rows, d) = self.m.nb_classes, o.shape
+        self.side(lambda: ops.wgrad(dl, o, self.g(weight), C, d, rows), dl, o)
+        cs = torch.zeros(CLS_PAD, device=dl.device, dtype=F32)
+        self.side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), self.g(bias).add_(cs[:C])), dl, cs)
+        return ops.gemm(dl, self.cls_w, rows, d, CLS_PAD, tb=True, out_kind=out_kind)
 
     # ---------------------------------------------------------------- backward
     def backward(self, dlogits_btc):
@@ -435,11 +430,7 @@ class _TrainStep:
         dl = torch.zeros((rows, CLS_PAD), device=dev, dtype=BF16)
         dl[:, :C] = dlogits_btc.reshape(rows, C).to(BF16)
         x, fm, fr, o = self.fin_saved
-        # classifier
-        side(lambda: ops.wgrad(dl, o, self.g("decoder.classifier.weight"), C, d, rows), dl, o)
-        cs = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), self.g("decoder.classifier.bias").add_(cs[:C])), dl, cs)
-        do = ops.gemm(dl, self.cls_w, rows, d, CLS_PAD, tb=True)
+        do = self.classifier_backward(dl, o, "decoder.classifier.weight", "decoder.classifier.bias")
         dx = ops.layernorm_bwd(do, x, self.p("decoder.layer_norm.weight"), self.p("decoder.layer_norm.bias"), fm, fr, None,
                                self.g("decoder.layer_norm.weight"), self.g("decoder.layer_norm.bias"))
         self._dmem = None
@@ -536,74 +527,6 @@ class _RecTrainFn(torch.autograd.Function):
         step, ctx.step = ctx.step, None
         step.backward(g.contiguous().float())
         return None, None, None, None, None
-
-
-class SeqCrossEntropyLoss(torch.nn.Module):
-    """loss/seqCrossEntropyLoss.py (sample_normalize) with its gradient: forward(logits [B,T,C] fp32, target [B,T], length [B])."""
-
-    def forward(self, input, target, length):
-        return _SeqCEFn.apply(input, target.to(input.device).long().contiguous(), length.to(input.device).long().contiguous())
-
-
-class _SeqCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, length):
-        B, T, C = logits.shape
-        x = logits.detach().float().contiguous()
-        rows = torch.empty(B * T, device=x.device, dtype=F32)
-        loss = torch.empty(1, device=x.device, dtype=F32)
-        L.call("dig_seq_cross_entropy", L.ptr(x), L.ptr(target), L.ptr(length), B, T, C, L.ptr(rows), L.ptr(loss), L.stream())
-        ctx.save_for_backward(x, target, length)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        x, target, length = ctx.saved_tensors
-        B, T, C = x.shape
-        Cp = (C + 7) // 8 * 8
-        dl = torch.empty((B * T, Cp), device=x.device, dtype=BF16)
-        gs = g.reshape(1).float().contiguous()                         # (named: a converted copy must outlive the call)
-        L.call("dig_seq_cross_entropy_bwd", L.ptr(x), C, L.ptr(target), L.ptr(length), L.ptr(gs), B, T, C, L.ptr(dl), Cp, L.stream())
-        return dl[:, :C].float().reshape(B, T, C), None, None
-
-
-class SeqLabelSmoothingCrossEntropyLoss(torch.nn.Module):
-    """loss/seqLabelSmoothingCrossEntropyLoss.py (sample_normalize), the criterion `--smoothing > 0` selects
-    (run_class_finetuning.py:538-541), with the value the reference really computes: its smoothing term broadcasts to a [BT, BT]
-    matrix (include/dig_hip.h `dig_seq_ls_cross_entropy`), which this class reproduces."""
-
-    def __init__(self, smoothing=0.1):
-        super().__init__()
-        if not 0.0 <= smoothing <= 1.0:
-            raise ValueError("smoothing must be in [0, 1]")
-        self.smoothing = float(smoothing)
-
-    def forward(self, input, target, length):
-        return _SeqLSCEFn.apply(input, target.to(input.device).long().contiguous(), length.to(input.device).long().contiguous(), self.smoothing)
-
-
-class _SeqLSCEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target, length, smoothing):
-        B, T, C = logits.shape
-        x = logits.detach().float().contiguous()
-        rows = torch.empty(2 * B * T, device=x.device, dtype=F32)
-        loss = torch.empty(1, device=x.device, dtype=F32)
-        L.call("dig_seq_ls_cross_entropy", L.ptr(x), L.ptr(target), L.ptr(length), B, T, C, cf(smoothing), L.ptr(rows), L.ptr(loss), L.stream())
-        ctx.save_for_backward(x, target, length)
-        ctx.smoothing = smoothing
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        x, target, length = ctx.saved_tensors
-        B, T, C = x.shape
-        Cp = (C + 7) // 8 * 8
-        dl = torch.empty((B * T, Cp), device=x.device, dtype=BF16)
-        gs = g.reshape(1).float().contiguous()
-        L.call("dig_seq_ls_cross_entropy_bwd", L.ptr(x), C, L.ptr(target), L.ptr(length), L.ptr(gs), B, T, C, cf(ctx.smoothing), L.ptr(dl), Cp,
-               L.stream())
-        return dl[:, :C].float().reshape(B, T, C), None, None, None
 
 
 # -------------------------------------------------------------------------------------------------- optimizer
@@ -713,31 +636,17 @@ class FineTuneAdamW:
 
     # ---- checkpoints: torch.optim's per-parameter layout (what utils.save_model / auto_load_model exchange, utils/utils.py:546-651)
     def _ordered_names(self):
-        return [n for g in self.param_groups for n in g["names"]]
+        return arena.group_names(self.param_groups)
+
+    def _moments(self):
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
 
     def state_dict(self):
-        moments = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
-        state = arena.split(moments, self.model._offsets, self._ordered_names(), self._stateless) if self._step > 0 else {}
-        for st in state.values():
-            st["step"] = self._step
-        groups, k = [], 0
-        for g in self.param_groups:
-            d = {key: v for key, v in g.items() if key not in ("params", "names")}
-            d.setdefault("amsgrad", False)
-            d["params"] = list(range(k, k + len(g["names"])))
-            k += len(g["names"])
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
+        return arena.optimizer_state_dict(self._moments(), self.model._offsets, self.param_groups, self._step, self._stateless)
 
     def load_state_dict(self, sd):
         self._tables()
-        if [len(g["params"]) for g in sd["param_groups"]] != [len(g["names"]) for g in self.param_groups]:
-            raise ValueError("loaded state dict has different parameter groups")
-        arena.join({"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}, self.model._offsets, self._ordered_names(), sd["state"])
-        steps = {int(st["step"]) for st in sd["state"].values()}
-        if len(steps) > 1:
-            raise ValueError("per-parameter step counts differ; the fused optimizer keeps one step counter")
-        self._step = steps.pop() if steps else 0
+        self._step = arena.load_optimizer_state(self._moments(), self.model._offsets, self.param_groups, sd)
         for g, lg in zip(self.param_groups, sd["param_groups"]):
             for key in ("lr", "weight_decay", "lr_scale", "betas", "eps"):
                 if key in lg:

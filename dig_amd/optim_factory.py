@@ -12,8 +12,7 @@ import torch
 
 import os
 
-from . import ops
-from .arena import join, split
+from . import arena, ops
 
 # the optimizer launch also writes the bf16 operand shadow and the transposed weight copies the next forward needs (dig_adamw_step_tr);
 # "0": the plain launch, the forward re-casts and re-transposes every step (the round-5 plan)
@@ -108,41 +107,22 @@ class FusedAdamW(torch.optim.Optimizer):
     #   {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [{..., 'params': [i, ...]}, ...]}
     # with i enumerating the parameters group by group (decay first), so checkpoints interchange with the reference.
     def _named_specs(self):
-        out = []
-        for g in self.param_groups:
-            out.extend(g["names"])
-        return out
+        return arena.group_names(self.param_groups)
+
+    def _moments(self):
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
 
     def state_dict(self):
-        moments = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
-        state = split(moments, self.model.specs, self._named_specs()) if self._step > 0 else {}
-        for st in state.values():
-            st["step"] = self._step
-        groups, k = [], 0
-        for g in self.param_groups:
-            d = {key: v for key, v in g.items() if key not in ("params", "names")}
-            d.setdefault("amsgrad", False)
-            d["params"] = list(range(k, k + len(g["names"])))
-            k += len(g["names"])
-            groups.append(d)
-        return {"state": state, "param_groups": groups}
+        return arena.optimizer_state_dict(self._moments(), self.model.specs, self.param_groups, self._step)
 
     def load_state_dict(self, sd):
         self._bind()
-        names = self._named_specs()
         if "state" not in sd:                                   # round-0 flat format of this package
             self._step = int(sd["step"])
             self.exp_avg.copy_(sd["exp_avg"])
             self.exp_avg_sq.copy_(sd["exp_avg_sq"])
             return
-        if len(sd["param_groups"]) != len(self.param_groups) or \
-                [len(g["params"]) for g in sd["param_groups"]] != [len(g["names"]) for g in self.param_groups]:
-            raise ValueError("loaded state dict has different parameter groups")
-        join({"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}, self.model.specs, names, sd["state"])
-        steps = {int(st["step"]) for st in sd["state"].values()}
-        if len(steps) > 1:
-            raise ValueError("per-parameter step counts differ; the fused optimizer keeps one step counter")
-        self._step = steps.pop() if steps else 0
+        self._step = arena.load_optimizer_state(self._moments(), self.model.specs, self.param_groups, sd)
         for g, s_ in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in s_.items() if k not in ("params", "names", "amsgrad")})
 

@@ -37,7 +37,7 @@ LOCAL = LocalComm()
 # ---- a train-mode BatchNorm layer (SyncBatchNorm semantics) for a step object: .m (the model), .comm, ._bn_touched (running buffers written)
 def bn_forward(step, hs, names, relu, affine=True):
     """BatchNorm (train) over the rows of every matrix in hs with this step's cross-rank statistics; running buffers updated.  names: the
-    layers' parameter prefixes.  Several matrices (the lock-step stacks of mlp_forward_pair) share ONE all-reduce: [len(hs), 2, C].
+    layers' parameter prefixes.  Several matrices (the lock-step stacks of engine_core's mlp_forward) share ONE all-reduce: [len(hs), 2, C].
     Returns [(y, mean, rstd)]."""
     M = step.m
     rows, C = hs[0].shape

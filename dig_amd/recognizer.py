@@ -8,8 +8,9 @@ models/decoder.py:224-252; encoder factory `simmim_vit_small_patch4_32x128`, mod
 
 What differs from the reference: the decoder keeps a K/V cache (one token per step instead of re-running all 26 positions 25
 times -- same result, position t only depends on tokens <= t) and the cross-attention keys/values of the encoder memory are
-projected once per layer.  Inference only (the fine-tune *training* step is row N1, not built yet): there is no CPU fallback
-and no autograd through this module."""
+projected once per layer.  The encoder front and the memory projection are written once here for evaluation and for the fine-tune training
+step (dig_amd/finetune.py), which passes its own plan and dropout keys; the sequence losses at the end carry their gradient.  There is no
+CPU fallback."""
 import ctypes
 from collections import OrderedDict
 
@@ -217,27 +218,43 @@ class RecModel(torch.nn.Module):
             self._fresh = ver
 
     # ------------------------------------------------------------------ forward pieces
-    def encoder_features(self, images):
-        """PretrainVisionTransformerEncoder.forward_features(x, mask=None): bf16 [B*256, D]."""
-        w, D, H = self._w, self.D, self.H
-        B = images.shape[0]
-        zeros = torch.zeros((B, self.N), device=images.device, dtype=torch.uint8)
-        x = ops.patch_embed_fwd(images.contiguous().float(), w["pe_w"], w["pe_b"], zeros, w["mask_token"], w["enc_pos"], D, self.gh, self.gw)
-        x, _, _ = EB.forward(EB.Plan(), w["enc_blocks"], x, B, H, 1e-6, False)              # the plain form, nothing kept
-        y, _, _ = ops.layernorm_fwd(x, w["enc_nw"], w["enc_nb"], 1e-6)
-        return y
+    def enc_blocks(self):
+        return self._w["enc_blocks"]
 
-    def memory(self, enc):
-        """linear_norm (model_builder.py:86-89): Linear + LayerNorm(eps 1e-5) on the feature map."""
+    def encoder_front(self, images, plan, save, drops=None, frozen=0):
+        """PretrainVisionTransformerEncoder.forward (modeling_pretrain_vit.py:89-112, mask=None) on the pre-training hot-path kernels: patch
+        embedding -> the blocks under `plan` (encoder_blocks.Plan; drops / frozen: see encoder_blocks.forward) -> encoder.norm, which rides
+        behind the last block where the plan's chain makes it.  Returns the normalised tokens, bf16 [B*256, D], and what the backward reads:
+        (fp32 images, the all-zero token mask, the blocks' saved activations, (x behind the last block, mean, rstd, tokens))."""
         w = self._w
-        if self.use_1d_attdec:                                          # enc_x.view(B, gh, gw, C).mean(1): [B*gw, D]
+        B = images.shape[0]
+        images = images.contiguous().float()
+        zmask = torch.zeros((B, self.N), device=images.device, dtype=torch.uint8)
+        x = ops.patch_embed_fwd(images, w["pe_w"], w["pe_b"], zmask, w["mask_token"], w["enc_pos"], self.D, self.gh, self.gw)
+        x, saved, ln_next = EB.forward(plan, self.enc_blocks(), x, B, self.H, 1e-6, save, drops=drops, tail=(w["enc_nw"], w["enc_nb"]), frozen=frozen)
+        enc, mu, rs = ln_next if ln_next is not None else ops.layernorm_fwd(x, w["enc_nw"], w["enc_nb"], 1e-6)
+        return enc, (images, zmask, saved, (x, mu, rs, enc))
+
+    def encoder_features(self, images):
+        """PretrainVisionTransformerEncoder.forward_features(x, mask=None): bf16 [B*256, D] -- the plain form, nothing kept."""
+        return self.encoder_front(images, EB.Plan(), False)[0]
+
+    def linear_norm(self, enc):
+        """linear_norm (model_builder.py:86-89): Linear + LayerNorm(eps 1e-5) on the feature map, or with use_1d_attdec on the column means of
+        the gh x gw grid (model_builder.py:145-148: enc_x.view(B, gh, gw, C).mean(1), [B*gw, D]).  Returns the memory the decoder attends over
+        and what the backward reads: (the Linear's input, its output, mean, rstd)."""
+        w = self._w
+        if self.use_1d_attdec:
             B = enc.shape[0] // self.N
             cols = torch.empty((B * self.gw, self.D), device=enc.device, dtype=enc.dtype)
             ops.window_pool_fwd(enc, cols, B, self.gh, self.gw, self.gw, self.D)
             enc = cols
         h = ops.linear_fwd(enc, w["ln_w"], bias=w["ln_b"])
-        m, _, _ = ops.layernorm_fwd(h, w["ln_nw"], w["ln_nb"], 1e-5)
-        return m
+        m, mu, rs = ops.layernorm_fwd(h, w["ln_nw"], w["ln_nb"], 1e-5)
+        return m, (enc, h, mu, rs)
+
+    def memory(self, enc):
+        return self.linear_norm(enc)[0]
 
     def _decode_state(self, mem, n_mem, slots_per_mem=1):
         """Buffers of a K/V-cached decode over S = B * slots_per_mem sequences (greedy: 1 slot per sample; beam search: beam_width
@@ -445,16 +462,48 @@ def recognition_f_measure(pred_tokens, target_tokens, voc):
     return f.mean()
 
 
+class _SeqCEFn(torch.autograd.Function):
+    """The sequence cross-entropy launch and its gradient; smoothing None: dig_seq_cross_entropy, else dig_seq_ls_cross_entropy (one more scalar)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, length, smoothing):
+        B, T, C = logits.shape
+        x = logits.detach().float().contiguous()
+        name, extra = ("dig_seq_cross_entropy", ()) if smoothing is None else ("dig_seq_ls_cross_entropy", (cf(smoothing),))
+        rows = torch.empty((1 + len(extra)) * B * T, device=x.device, dtype=F32)
+        loss = torch.empty(1, device=x.device, dtype=F32)
+        L.call(name, L.ptr(x), L.ptr(target), L.ptr(length), B, T, C, *extra, L.ptr(rows), L.ptr(loss), L.stream())
+        ctx.save_for_backward(x, target, length)
+        ctx.entry = (name + "_bwd", extra)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, target, length = ctx.saved_tensors
+        B, T, C = x.shape
+        Cp = (C + 7) // 8 * 8
+        dl = torch.empty((B * T, Cp), device=x.device, dtype=BF16)
+        gs = g.reshape(1).float().contiguous()                         # (named: a converted copy must outlive the call)
+        name, extra = ctx.entry
+        L.call(name, L.ptr(x), C, L.ptr(target), L.ptr(length), L.ptr(gs), B, T, C, *extra, L.ptr(dl), Cp, L.stream())
+        return dl[:, :C].float().reshape(B, T, C), None, None, None
+
+
 class SeqCrossEntropyLoss(torch.nn.Module):
-    """loss/seqCrossEntropyLoss.py (sample_normalize): forward(input [B,T,C] fp32, target [B,T], length [B]) -> 0-dim loss.
-    Forward only (evaluation); the training loss with its gradient belongs to row N1."""
+    """loss/seqCrossEntropyLoss.py (sample_normalize) with its gradient: forward(input [B,T,C] fp32, target [B,T], length [B]) -> 0-dim loss."""
+    smoothing = None
 
     def forward(self, input, target, length):
-        B, T, C = input.shape
-        dev = input.device
-        inp = input.detach().float().contiguous()
-        rows = torch.empty(B * T, device=dev, dtype=F32)
-        loss = torch.empty(1, device=dev, dtype=F32)
-        tgt, lens = target.to(dev).long().contiguous(), length.to(dev).long().contiguous()
-        L.call("dig_seq_cross_entropy", L.ptr(inp), L.ptr(tgt), L.ptr(lens), B, T, C, L.ptr(rows), L.ptr(loss), L.stream())
-        return loss[0]
+        return _SeqCEFn.apply(input, target.to(input.device).long().contiguous(), length.to(input.device).long().contiguous(), self.smoothing)
+
+
+class SeqLabelSmoothingCrossEntropyLoss(SeqCrossEntropyLoss):
+    """loss/seqLabelSmoothingCrossEntropyLoss.py (sample_normalize), the criterion `--smoothing > 0` selects
+    (run_class_finetuning.py:538-541), with the value the reference really computes: its smoothing term broadcasts to a [BT, BT]
+    matrix (include/dig_hip.h `dig_seq_ls_cross_entropy`), which this class reproduces."""
+
+    def __init__(self, smoothing=0.1):
+        super().__init__()
+        if not 0.0 <= smoothing <= 1.0:
+            raise ValueError("smoothing must be in [0, 1]")
+        self.smoothing = float(smoothing)
