@@ -94,7 +94,9 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                # the ABINet augmentation of fine-tuning (abiaug.hip): the same
                "abiaug_sample_kernel", "abiaug_warp_kernel", "abiaug_det_kernel", "abiaug_tail_kernel",
                # the lexicon search of the evaluation metrics (metrics.hip): its DP row is in LDS, the rest in registers
-               "lexicon_search_kernel")
+               "lexicon_search_kernel",
+               # the folded text-conditional cross-attention (text_cond_attn.hip): u / dc / the accumulators of a query row stay in registers
+               "tcv_fwd_kernel", "tcv_bwd_q_kernel", "tcv_bwd_k_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

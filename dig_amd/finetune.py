@@ -11,7 +11,8 @@ come from a keyed counter hash instead of torch's generator, see dig_amd/dropout
 Parameters, gradients, Adam moments and the bf16 GEMM operands live in flat arenas (dig_amd/arena.py: each tensor padded to the granule) whose
 layout keeps q|k|v (and k|v) projection weights adjacent, so the fused projections are views.  The whole model is ONE autograd
 node with a hand-written backward on the hot-path kernels (encoder: the pre-training kernels; decoder: `dig_seq_attn_*`,
-`dig_seq_embed_*`, `dig_gemm_bf16`, `dig_layernorm_*`).  The CPU checker of this step lives with the tests."""
+`dig_seq_embed_*`, `dig_gemm_bf16`, `dig_layernorm_*`; with `--text_cond_vis` the cross-attention is `dig_tcv_attn_fwd / _bwd` between per-head
+fold GEMMs, see dig_amd/recognizer.py).  The CPU checker of this step lives with the tests."""
 import ctypes
 import math
 import os
@@ -321,8 +322,23 @@ class _TrainStep:
         x = ops.dropout_apply(x, self.ds_tgt, out=x)                            # decoder.py:180
         sc = dk ** -0.5
         self.dec_saved = []
-        mfma_cross = N == 256 and dk == 64
+        tcv = M.text_cond_vis
+        mfma_cross = N == 256 and dk == 64 and not tcv
         kv_ready = []
+        if tcv:
+            # --text_cond_vis: vk = LN_vis(vis_proj(mem)) depends on no decoder state either: all layers' on the second stream, one event per layer
+            main = torch.cuda.current_stream(dev)
+            sd = M._side_stream(dev) if getattr(M, "overlap_streams", True) else main
+            sd.wait_stream(main)
+            with torch.cuda.stream(sd):
+                for i in range(M.n_layers):
+                    vk, vsaved = M.tcv_memory(mem, M._w[f"decoder.layer_stack.{i}."])
+                    ev = torch.cuda.Event()
+                    ev.record(sd)
+                    for t_ in (vk,) + vsaved:
+                        t_.record_stream(main)
+                    kv_ready.append((vk, vsaved, ev))
+            mem.record_stream(sd)
         if mfma_cross:
             # K|V projections of the encoder memory depend on no decoder state: all layers' are issued on the second stream now and
             # overlap the (small, latency-bound) self-attention kernels of the decoder chain; one event per layer
@@ -349,8 +365,21 @@ class _TrainStep:
                    L.ptr(lse1), B, nh, T, T, cf(sc), 1, L.ptr(self.lens), _ref(ds["sattn"]), L.stream())
             x1 = ops.linear_fwd(a, self.w(p + "self_attn.fc.weight"), resid=x, drop=ds["sproj"])
             h2, m2, r2 = ops.layernorm_fwd(x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), 1e-5)
-            q2 = ops.linear_fwd(h2, self.w(p + "enc_attn.linear_q.weight"))
-            if mfma_cross:
+            q2 = None if tcv else ops.linear_fwd(h2, self.w(p + "enc_attn.linear_q.weight"))
+            if tcv:
+                # the text-conditional cross-attention, folded (csrc/text_cond_attn.hip): film = gamma_decode(h2); the scaled queries through
+                # Wk head by head (u); the attention over cond, which only exists row by row inside the kernel; its result through Wv head by head
+                pv = M._w[p]
+                film = ops.linear_fwd(h2, pv["gd"], bias=pv["gdb"])
+                q2 = self.padded_rows(B * T, hk, dev)                             # (a weight-gradient operand read in 128-column tiles)
+                ops.linear_fwd(h2, pv["q2"], alpha=sc, alpha_cols=hk, out=q2)
+                u2 = M.tcv_fold_queries(q2, pv["k2"])
+                vk, vsaved, ev = kv_ready[i]
+                torch.cuda.current_stream(dev).wait_event(ev)
+                c2, lse2 = ops.tcv_attn_fwd(film, u2, vk, mem, pv["cnw"], pv["cnb"], B, T, N, nh, 1, ds["cattn"])
+                a2 = M.tcv_fold_values(c2, pv["v2"])
+                kvm = dict(film=film, u=u2, vk=vk, vsaved=vsaved, c=c2)
+            elif mfma_cross:
                 # cross-attention on the MFMA kernel of the encoder (256 keys, head dim 64): the T queries of a sample sit in rows
                 # [0, T) of a fused q|k|v buffer of 256 rows per sample, and the kernels are told to compute the first
                 # ceil(T / 32) query blocks only (rows T..31 are zero queries with a zero output gradient: no contribution).
@@ -378,6 +407,61 @@ class _TrainStep:
         logits = torch.empty((B * T, CLS_PAD), device=dev, dtype=F32)
         ops.gemm(o, self.cls_w, B * T, CLS_PAD, d, out=logits, out_kind=ops.OUT_F32, bias=cb)
         return logits[:, :C].reshape(B, T, C)
+
+    @staticmethod
+    def padded_rows(rows, cols, dev):
+        """bf16 [rows, cols] with one zero row behind it: an operand whose 64-column head slices are read in 128-column tiles by the
+        weight-gradient GEMM (the last head's tile runs 64 columns past the last row)."""
+        buf = torch.empty((rows + 1, cols), device=dev, dtype=BF16)
+        buf[rows:].zero_()
+        return buf[:rows]
+
+    def add_dmem(self, dm):
+        if self._dmem is None:
+            self._dmem = dm
+        else:
+            ops.add_bf16(self._dmem, dm, self._dmem)
+
+    def tcv_cross_backward(self, p, dz, drop, h2, q2, kvm, lse2, mem):
+        """The backward of the folded text-conditional cross-attention of layer `p` (see forward): dz = the gradient behind enc_attn.fc's
+        proj_drop.  The Wv fold gives dc and linear_v's gradient, dig_tcv_attn_bwd gives du / dfilm / dvk / the residual term of dmem and
+        vis_cond_norm's gradients, the Wk fold gives the query gradient and linear_k's; gamma_decode, vis_proj and vis_norm are a Linear and a
+        LayerNorm.  Returns the gradient w.r.t. norm2's output; the memory gradient is summed into self._dmem on the second stream."""
+        M, side = self.m, self.side
+        B, T, d, nh, dk, N = self.B, M.max_len, M.d, M.nh, M.dk, M.n_mem
+        hk, rows, sc = nh * dk, self.B * M.max_len, M.dk ** -0.5
+        pv, a = M._w[p], p + "enc_attn."
+        film, u2, vk, (hv, vmu, vrs), c2 = kvm["film"], kvm["u"], kvm["vk"], kvm["vsaved"], kvm["c"]
+        head = lambda t_, h, w_: t_[:, h * w_:(h + 1) * w_]
+        da2 = self.padded_rows(rows, hk, dz.device)
+        ops.linear_dgrad(dz, self.w(a + "fc.weight"), out=da2)
+        dc = torch.empty_like(c2)
+        for h in range(nh):
+            ops.gemm(head(da2, h, dk), pv["v2"][h * dk:(h + 1) * dk], rows, d, dk, tb=True, out=head(dc, h, d))
+        gv, gk = self.g(a + "linear_v.weight"), self.g(a + "linear_k.weight")
+        side(lambda: [ops.wgrad(head(da2, h, dk), head(c2, h, d), gv[h * dk:(h + 1) * dk], dk, d, rows) for h in range(nh)], da2, c2)
+        du, dfilm, dvk, dmem = ops.tcv_attn_bwd(film, u2, vk, mem, pv["cnw"], pv["cnb"], c2, lse2, dc, self.g(a + "vis_cond_norm.weight"),
+                                                self.g(a + "vis_cond_norm.bias"), B, T, N, nh, drop)
+        dq2 = torch.empty((rows, hk), device=dz.device, dtype=BF16)
+        for h in range(nh):                                                       # q2 carries the scale: so does its gradient
+            ops.gemm(head(du, h, d), pv["k2"][h * dk:(h + 1) * dk], rows, dk, d, out=head(dq2, h, dk), alpha=sc, alpha_cols=dk)
+        side(lambda: [ops.wgrad(head(q2, h, dk), head(du, h, d), gk[h * dk:(h + 1) * dk], dk, d, rows) for h in range(nh)], q2, du)
+        side(lambda: ops.linear_wgrad(dq2, h2, self.g(a + "linear_q.weight")), dq2, h2)
+        side(lambda: ops.linear_wgrad(dfilm, h2, self.g(a + "gamma_decode.weight")), dfilm, h2)
+        side(lambda: ops.colsum(dfilm, self.g(a + "gamma_decode.bias")), dfilm)
+        dh2 = ops.linear_dgrad(dq2, pv["q2"])
+        dh2b = ops.linear_dgrad(dfilm, pv["gd"])
+        ops.add_bf16(dh2, dh2b, dh2)
+
+        def vis_path():
+            dhv = ops.layernorm_bwd(dvk, hv, pv["vnw"], pv["vnb"], vmu, vrs, None, self.g(a + "vis_norm.weight"), self.g(a + "vis_norm.bias"))
+            ops.linear_wgrad(dhv, mem, self.g(a + "vis_proj.weight"))
+            ops.colsum(dhv, self.g(a + "vis_proj.bias"))
+            dm = ops.linear_dgrad(dhv, pv["vp"])
+            ops.add_bf16(dm, dmem, dm)
+            self.add_dmem(dm)
+        side(vis_path, dvk, dmem, hv, vmu, vrs, mem)
+        return dh2
 
     def encoder_backward(self, denc):
         """denc: bf16 [B*N, D] gradient w.r.t. the tokens `encoder_forward` returned (call `begin_backward` first)."""
@@ -454,27 +538,30 @@ class _TrainStep:
             # cross-attention over the encoder memory
             dz = ops.dropout_apply(dx2, ds["cproj"])
             side(lambda: ops.linear_wgrad(dz, a2, self.g(p + "enc_attn.fc.weight")), dz, a2)
-            da2 = ops.linear_dgrad(dz, self.w(p + "enc_attn.fc.weight"))
-            if isinstance(lse2, tuple):                                           # MFMA path (see forward)
-                lse2, ctx2 = lse2                                                 # padded rows: finite outputs, zero dO -> delta = 0
-                dq2, dkvm = EB.cross_attn_bwd(kvm, ctx2, lse2, da2, B, T, nh, hk, sc, drop=ds["cattn"])   # kvm = the fused q|k|v buffer
+            if isinstance(kvm, dict):                                             # --text_cond_vis (see forward)
+                dh2 = self.tcv_cross_backward(p, dz, ds["cattn"], h2, q2, kvm, lse2, mem)
             else:
-                dq2 = torch.empty_like(q2)
-                dkvm = torch.empty_like(kvm)
-                L.call("dig_seq_attn_bwd_dropout", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(da2), hk, L.ptr(lse2),
-                       L.ptr(dq2), hk, L.ptr(dkvm), 2 * hk, L.ptr(dkvm[:, hk:]), 2 * hk, B, nh, T, N, cf(sc), 0, None, _ref(ds["cattn"]),
-                       L.stream())
-            side(lambda: ops.linear_wgrad(dq2, h2, self.g(p + "enc_attn.linear_q.weight")), dq2, h2)
-            dh2 = ops.linear_dgrad(dq2, self.w(p + "enc_attn.linear_q.weight"))
-            side(lambda: ops.wgrad(dkvm, mem, self.g_of(M._w[p]["kv2"]), 2 * hk, hk, B * N), dkvm, mem)
-            # the gradient w.r.t. the encoder memory is needed only after the decoder loop: its GEMMs run on the second stream too
-            def mem_grad(dkvm=dkvm, wkv=M._w[p]["kv2"]):
-                dm = ops.gemm(dkvm, wkv, B * N, hk, 2 * hk, tb=True)
-                if self._dmem is None:
-                    self._dmem = dm
+                da2 = ops.linear_dgrad(dz, self.w(p + "enc_attn.fc.weight"))
+                if isinstance(lse2, tuple):                                           # MFMA path (see forward)
+                    lse2, ctx2 = lse2                                                 # padded rows: finite outputs, zero dO -> delta = 0
+                    dq2, dkvm = EB.cross_attn_bwd(kvm, ctx2, lse2, da2, B, T, nh, hk, sc, drop=ds["cattn"])   # kvm = the fused q|k|v buffer
                 else:
-                    ops.add_bf16(self._dmem, dm, self._dmem)
-            side(mem_grad, dkvm)
+                    dq2 = torch.empty_like(q2)
+                    dkvm = torch.empty_like(kvm)
+                    L.call("dig_seq_attn_bwd_dropout", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(da2), hk, L.ptr(lse2),
+                           L.ptr(dq2), hk, L.ptr(dkvm), 2 * hk, L.ptr(dkvm[:, hk:]), 2 * hk, B, nh, T, N, cf(sc), 0, None, _ref(ds["cattn"]),
+                           L.stream())
+                side(lambda: ops.linear_wgrad(dq2, h2, self.g(p + "enc_attn.linear_q.weight")), dq2, h2)
+                dh2 = ops.linear_dgrad(dq2, self.w(p + "enc_attn.linear_q.weight"))
+                side(lambda: ops.wgrad(dkvm, mem, self.g_of(M._w[p]["kv2"]), 2 * hk, hk, B * N), dkvm, mem)
+                # the gradient w.r.t. the encoder memory is needed only after the decoder loop: its GEMMs run on the second stream too
+                def mem_grad(dkvm=dkvm, wkv=M._w[p]["kv2"]):
+                    dm = ops.gemm(dkvm, wkv, B * N, hk, 2 * hk, tb=True)
+                    if self._dmem is None:
+                        self._dmem = dm
+                    else:
+                        ops.add_bf16(self._dmem, dm, self._dmem)
+                side(mem_grad, dkvm)
             dx1 = ops.layernorm_bwd(dh2, x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), m2, r2, dx2, self.g(p + "norm2.weight"),
                                     self.g(p + "norm2.bias"))
             # masked self-attention

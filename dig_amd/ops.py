@@ -750,6 +750,29 @@ def attn_fwd(qkv, n_img, heads, D, drop=None, q_rows=256):
     return ctx, lse
 
 
+def tcv_attn_fwd(film, u, vk, mem, lnc_g, lnc_b, S, Lq, N, heads, slots_per_mem=1, drop=None, wmean=None, eps=1e-5):
+    """The folded text-conditional cross-attention (csrc/text_cond_attn.hip): film [S*Lq, 2d], u [S*Lq, heads*d], vk / mem [S/slots*N, d]
+    -> c [S*Lq, heads*d] bf16, lse [S*Lq, heads] fp32; wmean ([S*Lq, N] fp32, optional) receives the head-mean weights before dropout."""
+    d = vk.shape[1]
+    c = torch.empty((S * Lq, heads * d), device=u.device, dtype=BF16)
+    lse = torch.empty((S * Lq, heads), device=u.device, dtype=F32)
+    L.call("dig_tcv_attn_fwd", L.ptr(film), L.ptr(u), L.ptr(vk), L.ptr(mem), L.ptr(lnc_g), L.ptr(lnc_b), cf(eps), L.ptr(c), L.ptr(lse), L.ptr(wmean),
+           S, Lq, N, heads, d, slots_per_mem, ctypes.byref(drop) if drop is not None else None, L.stream())
+    return c, lse
+
+
+def tcv_attn_bwd(film, u, vk, mem, lnc_g, lnc_b, c, lse, dc, dlnc_g, dlnc_b, S, Lq, N, heads, drop=None, eps=1e-5):
+    """Gradient of tcv_attn_fwd (one memory per sequence): returns du, dfilm, dvk, dmem (bf16; dmem is the residual term only) and adds
+    vis_cond_norm's gradients into dlnc_g / dlnc_b (fp32 [d])."""
+    d = vk.shape[1]
+    du, dfilm, dvk, dmem = torch.empty_like(u), torch.empty_like(film), torch.empty_like(vk), torch.empty_like(mem)
+    ws = _workspace(u.device, S * Lq * (2 * d + heads))
+    L.call("dig_tcv_attn_bwd", L.ptr(film), L.ptr(u), L.ptr(vk), L.ptr(mem), L.ptr(lnc_g), L.ptr(lnc_b), cf(eps), L.ptr(c), L.ptr(lse), L.ptr(dc),
+           L.ptr(du), L.ptr(dfilm), L.ptr(dvk), L.ptr(dmem), L.ptr(dlnc_g), L.ptr(dlnc_b), L.ptr(ws), S, Lq, N, heads, d, 1,
+           ctypes.byref(drop) if drop is not None else None, L.stream())
+    return du, dfilm, dvk, dmem
+
+
 ATTN_BLOCK = os.environ.get("DIG_ATTN_BLOCK", "1") != "0"    # the fused attention sub-block (csrc/attn_block.hip) where the widths allow it
 
 

@@ -1,4 +1,5 @@
-/* dig_hip.h -- C ABI of libdig_hip.so: the MI355X (gfx950) kernels behind the DiG pre-training hot path.
+/* dig_hip.h -- C ABI of libdig_hip.so: the MI355X (gfx950) kernels behind the DiG pre-training hot path and the recognition rows either side of
+ * it (input transforms, fine-tune step, K/V-cached decode, the folded text-conditional cross-attention of `--text_cond_vis`, metrics).
  *
  * The reference (ayumiymk/DiG) is pure PyTorch: it has no plugin / FFI boundary of its own.  The boundary this
  * library offers sits one level below the three Python surfaces the reference exposes (model factory, step engine,
@@ -644,6 +645,36 @@ int dig_seq_attn_fwd_dropout(const void* q, int ldq, const void* k, int ldk, con
 int dig_seq_attn_bwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo,
                              const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq, int Lk,
                              float scale, int causal, const long long* lens, const dig_dropout_t* drop, hipStream_t stream);
+
+/* ---- text-conditional cross-attention of the recognition decoder (`--text_cond_vis`: TextConditionalMultiHeadAttention,
+ * models/transformer_layer.py:284-383), folded.  The reference FiLM-modulates the whole memory for every query,
+ *     cond[t,k] = mem[k] + LN_cond(tanh(gamma[t]) * vk[k] + tanh(beta[t])),   vk = LN_vis(vis_proj(mem)),  (gamma|beta)[t] = gamma_decode(q_in[t])
+ * and pushes the [B, Lq, Lk, d] tensor through linear_k / linear_v.  Neither has a bias, so with Wk_h / Wv_h the 64 rows of head h
+ *     logit[t,h,k] = u[t,h] . cond[t,k],   u[t,h] = scale * Wk_h^T q_h[t];      out_h[t] = Wv_h c[t,h],   c[t,h] = sum_k w[t,h,k] cond[t,k]
+ * and the two entry points work on u and c: the folds are [rows, 64] x [64, d] GEMMs either side (dig_gemm_bf16 on strided views), cond
+ * lives one row at a time in registers.
+ * S sequences of Lq queries (R = S * Lq rows, row = s * Lq + t); M = S / slots_per_mem memories of N rows, sequence s reads memory
+ * s / slots_per_mem (beam search: the slots of a sample share its memory).  bf16: film [R, 2d] (gamma | beta BEFORE the tanh), u and c
+ * [R, heads * d] (head-major), vk and mem [M * N, d]; fp32: lnc_g, lnc_b [d] (vis_cond_norm, eps = 1e-5 in the reference), lse [R, heads],
+ * wmean [R, N] (optional: the head mean of the weights before dropout, the reference's vis_attn_maps, :372).
+ * Dropout acts on the weights after the normalisation by the full row sum (:361-373), keep rule of dig_seq_attn_fwd_dropout:
+ * (a, b) = ((t << 16) | k, s * heads + h); drop = NULL or thr = 0: none.
+ * Supported: d in {128, 384, 512}, heads = d / 64, 1 <= N <= 256, 1 <= Lq <= 32, slots_per_mem >= 1 dividing S (-4 otherwise); all bf16
+ * pointers 16-byte aligned (-2).
+ * dig_tcv_attn_bwd (slots_per_mem must be 1): from the forward's inputs, c, lse and dc [R, heads * d] -> du [R, heads * d], dfilm [R, 2d]
+ * (the tanh derivative applied), dvk [M * N, d], dmem [M * N, d] (the residual term only: the path through vk is the caller's GEMM /
+ * LayerNorm backward), all bf16 and overwritten; dlnc_g, dlnc_b [d] fp32, ACCUMULATED into.  workspace: R * (2d + heads) floats.
+ * delta = dc . c is re-summed over the keys in fp32 (the bf16 c is accepted and checked, not read: dlogit sums to zero over the keys only for
+ * an exact delta, and du = sum_k dlogit cond[k] keeps none of what the rows of cond share -- a rounding error of c would not cancel there).
+ * Deterministic (every sum has a fixed order, no floating-point atomics); a query row's c / lse / wmean / du / dfilm do not depend on
+ * what else is in the batch. */
+int dig_tcv_attn_fwd(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, float eps,
+                     void* c, float* lse, float* wmean, int S, int Lq, int N, int heads, int d, int slots_per_mem,
+                     const dig_dropout_t* drop, hipStream_t stream);
+int dig_tcv_attn_bwd(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, float eps,
+                     const void* c, const float* lse, const void* dc, void* du, void* dfilm, void* dvk, void* dmem, float* dlnc_g,
+                     float* dlnc_b, float* workspace, int S, int Lq, int N, int heads, int d, int slots_per_mem,
+                     const dig_dropout_t* drop, hipStream_t stream);
 
 
 /* ---- GRU attention recognition head (`--decoder_type attention`: models/model_builder.py:40-72 AttnRecModel,
