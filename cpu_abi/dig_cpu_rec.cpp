@@ -218,29 +218,29 @@ int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_
 
 int dig_decode_self_attn(const void* qkv_cache, void* out_, int B, int T, int heads, int head_dim, int t, float scale, hipStream_t) {
   if (!qkv_cache || !out_ || B <= 0 || heads <= 0 || t < 0 || t >= T) return DIG_ERR_ARG;
-  if (head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
   const bf16_t* qkv = (const bf16_t*)qkv_cache;
   bf16_t* out = (bf16_t*)out_;
-  const int hk = heads * 64;
+  const int hk = heads * head_dim;
   const size_t row = (size_t)3 * hk;
 #pragma omp parallel for collapse(2)
   for (int b = 0; b < B; ++b)
     for (int h = 0; h < heads; ++h) {
-      const bf16_t* base = qkv + (size_t)b * T * row + h * 64;
+      const bf16_t* base = qkv + (size_t)b * T * row + h * head_dim;
       std::vector<float> s(t + 1);
       float m = NEG_INF;
       for (int j = 0; j <= t; ++j) {
         float a = 0.f;
-        for (int c = 0; c < 64; ++c) a += bf2f(base[(size_t)t * row + c]) * scale * bf2f(base[(size_t)j * row + hk + c]);
+        for (int c = 0; c < head_dim; ++c) a += bf2f(base[(size_t)t * row + c]) * scale * bf2f(base[(size_t)j * row + hk + c]);
         s[j] = a;
         m = std::max(m, a);
       }
       float l = 0.f;
       for (int j = 0; j <= t; ++j) { s[j] = std::exp(s[j] - m); l += s[j]; }
-      for (int c = 0; c < 64; ++c) {
+      for (int c = 0; c < head_dim; ++c) {
         float a = 0.f;
         for (int j = 0; j <= t; ++j) a += s[j] * bf2f(base[(size_t)j * row + 2 * hk + c]);
-        out[(size_t)b * hk + h * 64 + c] = f2bf(a / l);
+        out[(size_t)b * hk + h * head_dim + c] = f2bf(a / l);
       }
     }
   return DIG_OK;
@@ -249,21 +249,21 @@ int dig_decode_self_attn(const void* qkv_cache, void* out_, int B, int T, int he
 int dig_decode_cross_attn(const void* q_, const void* kv_mem, void* out_, float* weights, int B, int n_mem, int heads, int head_dim, float scale,
                           int slots_per_mem, hipStream_t) {
   if (!q_ || !kv_mem || !out_ || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
-  if (head_dim != 64 || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
+  if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
   if (!aligned16(kv_mem)) return DIG_ERR_ALIGN;
   const bf16_t* q = (const bf16_t*)q_;
   const bf16_t* kv = (const bf16_t*)kv_mem;
   bf16_t* out = (bf16_t*)out_;
-  const int hk = heads * 64;
+  const int hk = heads * head_dim;
 #pragma omp parallel for collapse(2)
   for (int b = 0; b < B; ++b)
     for (int h = 0; h < heads; ++h) {
-      const bf16_t* kb = kv + (size_t)(b / slots_per_mem) * n_mem * 2 * hk + h * 64;
+      const bf16_t* kb = kv + (size_t)(b / slots_per_mem) * n_mem * 2 * hk + h * head_dim;
       std::vector<float> s(n_mem);
       float m = NEG_INF;
       for (int j = 0; j < n_mem; ++j) {
         float a = 0.f;
-        for (int c = 0; c < 64; ++c) a += bf2f(q[(size_t)b * hk + h * 64 + c]) * scale * bf2f(kb[(size_t)j * 2 * hk + c]);
+        for (int c = 0; c < head_dim; ++c) a += bf2f(q[(size_t)b * hk + h * head_dim + c]) * scale * bf2f(kb[(size_t)j * 2 * hk + c]);
         s[j] = a;
         m = std::max(m, a);
       }
@@ -272,10 +272,10 @@ int dig_decode_cross_attn(const void* q_, const void* kv_mem, void* out_, float*
       const float inv = 1.f / l;
       if (weights)
         for (int j = 0; j < n_mem; ++j) weights[((size_t)b * heads + h) * n_mem + j] = s[j] * inv;
-      for (int c = 0; c < 64; ++c) {
+      for (int c = 0; c < head_dim; ++c) {
         float a = 0.f;
         for (int j = 0; j < n_mem; ++j) a += s[j] * bf2f(kb[(size_t)j * 2 * hk + hk + c]);
-        out[(size_t)b * hk + h * 64 + c] = f2bf(a * inv);
+        out[(size_t)b * hk + h * head_dim + c] = f2bf(a * inv);
       }
     }
   return DIG_OK;
@@ -515,9 +515,11 @@ int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* t
 // ---------------------------------------------------------------------------------------------------------------- fine-tune step (N1): sequence attention
 // per (sample, head): logits = (q . k) * scale, masked keys -> probability 0, lse of the unmasked logits kept; attention dropout multiplies
 // the normalised probabilities (csrc/seq_attn.hip)
-int dig_seq_attn_fwd_dropout(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, void* out_, int ldo, float* lse, int B,
-                             int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, hipStream_t) {
+int dig_seq_attn_fwd_hd(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, void* out_, int ldo, float* lse, int B,
+                        int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, int head_dim,
+                        hipStream_t) {
   if (!q_ || !k_ || !v_ || !out_ || !lse || B <= 0 || heads <= 0 || Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
+  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
   if ((ldk & 7) || (ldv & 7) || !aligned16(k_) || !aligned16(v_)) return DIG_ERR_ALIGN;
   const bf16_t* q = (const bf16_t*)q_; const bf16_t* k = (const bf16_t*)k_; const bf16_t* v = (const bf16_t*)v_;
   bf16_t* out = (bf16_t*)out_;
@@ -528,15 +530,15 @@ int dig_seq_attn_fwd_dropout(const void* q_, int ldq, const void* k_, int ldk, c
       const long long len = lens ? lens[b] : (long long)Lk;
       std::vector<float> S((size_t)Lk);
       for (int i = 0; i < Lq; ++i) {
-        const bf16_t* qr = q + ((size_t)b * Lq + i) * ldq + h * 64;
+        const bf16_t* qr = q + ((size_t)b * Lq + i) * ldq + h * head_dim;
         float m = NEG_INF;
         for (int j = 0; j < Lk; ++j) {
           const bool ok = (!causal || j <= i) && (!lens || j < len);
           float a = NEG_INF;
           if (ok) {
             a = 0.f;
-            const bf16_t* kr = k + ((size_t)b * Lk + j) * ldk + h * 64;
-            for (int c = 0; c < 64; ++c) a += bf2f(qr[c]) * scale * bf2f(kr[c]);
+            const bf16_t* kr = k + ((size_t)b * Lk + j) * ldk + h * head_dim;
+            for (int c = 0; c < head_dim; ++c) a += bf2f(qr[c]) * scale * bf2f(kr[c]);
           }
           S[j] = a;
           m = std::max(m, a);
@@ -549,14 +551,19 @@ int dig_seq_attn_fwd_dropout(const void* q_, int ldq, const void* k_, int ldk, c
         }
         const float inv = 1.f / sum;
         lse[((size_t)b * heads + h) * Lq + i] = m + std::log(sum);
-        for (int c = 0; c < 64; ++c) {
+        for (int c = 0; c < head_dim; ++c) {
           float a = 0.f;
-          for (int j = 0; j < Lk; ++j) a += S[j] * bf2f(v[((size_t)b * Lk + j) * ldv + h * 64 + c]);
-          out[((size_t)b * Lq + i) * ldo + h * 64 + c] = f2bf(a * inv);
+          for (int j = 0; j < Lk; ++j) a += S[j] * bf2f(v[((size_t)b * Lk + j) * ldv + h * head_dim + c]);
+          out[((size_t)b * Lq + i) * ldo + h * head_dim + c] = f2bf(a * inv);
         }
       }
     }
   return DIG_OK;
+}
+
+int dig_seq_attn_fwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
+                             int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, hipStream_t st) {
+  return dig_seq_attn_fwd_hd(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, drop, 64, st);
 }
 
 int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B, int heads,
@@ -564,10 +571,11 @@ int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void*
   return dig_seq_attn_fwd_dropout(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, nullptr, st);
 }
 
-int dig_seq_attn_bwd_dropout(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, const void* dout_, int ldo, const float* lse,
-                             void* dq_, int lddq, void* dk_, int lddk, void* dv_, int lddv, int B, int heads, int Lq, int Lk, float scale, int causal,
-                             const long long* lens, const dig_dropout_t* drop, hipStream_t) {
+int dig_seq_attn_bwd_hd(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, const void* dout_, int ldo, const float* lse,
+                        void* dq_, int lddq, void* dk_, int lddk, void* dv_, int lddv, int B, int heads, int Lq, int Lk, float scale, int causal,
+                        const long long* lens, const dig_dropout_t* drop, int head_dim, hipStream_t) {
   if (!q_ || !k_ || !v_ || !dout_ || !lse || !dq_ || !dk_ || !dv_ || B <= 0 || heads <= 0 || Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
+  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
   if ((ldk & 7) || (ldv & 7) || !aligned16(k_) || !aligned16(v_)) return DIG_ERR_ALIGN;
   const bf16_t* q = (const bf16_t*)q_; const bf16_t* k = (const bf16_t*)k_; const bf16_t* v = (const bf16_t*)v_;
   const bf16_t* dout = (const bf16_t*)dout_;
@@ -579,8 +587,8 @@ int dig_seq_attn_bwd_dropout(const void* q_, int ldq, const void* k_, int ldk, c
       const long long len = lens ? lens[b] : (long long)Lk;
       std::vector<float> P((size_t)Lq * Lk), dS((size_t)Lq * Lk), F((size_t)Lq * Lk);
       for (int i = 0; i < Lq; ++i) {
-        const bf16_t* qr = q + ((size_t)b * Lq + i) * ldq + h * 64;
-        const bf16_t* gr = dout + ((size_t)b * Lq + i) * ldo + h * 64;
+        const bf16_t* qr = q + ((size_t)b * Lq + i) * ldq + h * head_dim;
+        const bf16_t* gr = dout + ((size_t)b * Lq + i) * ldo + h * head_dim;
         const float l = lse[((size_t)b * heads + h) * Lq + i];
         float del = 0.f;
         for (int j = 0; j < Lk; ++j) {
@@ -589,9 +597,9 @@ int dig_seq_attn_bwd_dropout(const void* q_, int ldq, const void* k_, int ldk, c
           if (dropping) f = drop_keep(drop->k0, drop->k1, ((unsigned)i << 16) | (unsigned)j, (unsigned)(b * heads + h), drop->thr) ? drop->scale : 0.f;
           if (ok) {
             float sc = 0.f;
-            const bf16_t* kr = k + ((size_t)b * Lk + j) * ldk + h * 64;
-            const bf16_t* vr = v + ((size_t)b * Lk + j) * ldv + h * 64;
-            for (int c = 0; c < 64; ++c) { sc += bf2f(qr[c]) * bf2f(kr[c]); dp += bf2f(gr[c]) * bf2f(vr[c]); }
+            const bf16_t* kr = k + ((size_t)b * Lk + j) * ldk + h * head_dim;
+            const bf16_t* vr = v + ((size_t)b * Lk + j) * ldv + h * head_dim;
+            for (int c = 0; c < head_dim; ++c) { sc += bf2f(qr[c]) * bf2f(kr[c]); dp += bf2f(gr[c]) * bf2f(vr[c]); }
             pr = std::exp(sc * scale - l);
             dp *= f;
           }
@@ -601,23 +609,29 @@ int dig_seq_attn_bwd_dropout(const void* q_, int ldq, const void* k_, int ldk, c
         for (int j = 0; j < Lk; ++j) dS[(size_t)i * Lk + j] = P[(size_t)i * Lk + j] * (dS[(size_t)i * Lk + j] - del);
       }
       for (int j = 0; j < Lk; ++j)
-        for (int c = 0; c < 64; ++c) {
+        for (int c = 0; c < head_dim; ++c) {
           float ak = 0.f, av = 0.f;
           for (int i = 0; i < Lq; ++i) {
-            ak += dS[(size_t)i * Lk + j] * bf2f(q[((size_t)b * Lq + i) * ldq + h * 64 + c]);
-            av += P[(size_t)i * Lk + j] * F[(size_t)i * Lk + j] * bf2f(dout[((size_t)b * Lq + i) * ldo + h * 64 + c]);
+            ak += dS[(size_t)i * Lk + j] * bf2f(q[((size_t)b * Lq + i) * ldq + h * head_dim + c]);
+            av += P[(size_t)i * Lk + j] * F[(size_t)i * Lk + j] * bf2f(dout[((size_t)b * Lq + i) * ldo + h * head_dim + c]);
           }
-          dk[((size_t)b * Lk + j) * lddk + h * 64 + c] = f2bf(ak * scale);
-          dv[((size_t)b * Lk + j) * lddv + h * 64 + c] = f2bf(av);
+          dk[((size_t)b * Lk + j) * lddk + h * head_dim + c] = f2bf(ak * scale);
+          dv[((size_t)b * Lk + j) * lddv + h * head_dim + c] = f2bf(av);
         }
       for (int i = 0; i < Lq; ++i)
-        for (int c = 0; c < 64; ++c) {
+        for (int c = 0; c < head_dim; ++c) {
           float a = 0.f;
-          for (int j = 0; j < Lk; ++j) a += dS[(size_t)i * Lk + j] * bf2f(k[((size_t)b * Lk + j) * ldk + h * 64 + c]);
-          dq[((size_t)b * Lq + i) * lddq + h * 64 + c] = f2bf(a * scale);
+          for (int j = 0; j < Lk; ++j) a += dS[(size_t)i * Lk + j] * bf2f(k[((size_t)b * Lk + j) * ldk + h * head_dim + c]);
+          dq[((size_t)b * Lq + i) * lddq + h * head_dim + c] = f2bf(a * scale);
         }
     }
   return DIG_OK;
+}
+
+int dig_seq_attn_bwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo, const float* lse,
+                             void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq, int Lk, float scale, int causal,
+                             const long long* lens, const dig_dropout_t* drop, hipStream_t st) {
+  return dig_seq_attn_bwd_hd(q, ldq, k, ldk, v, ldv, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, Lq, Lk, scale, causal, lens, drop, 64, st);
 }
 
 int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo, const float* lse, void* dq,

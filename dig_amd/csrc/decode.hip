@@ -1,15 +1,16 @@
 // Greedy decode with a K/V cache: the per-step pieces of TFDecoder.forward_test
 // (models/decoder.py:224-252) that are not GEMMs / LayerNorms.  The reference re-runs the whole decoder over all 26 positions
 // at every one of the 25 steps; position t only depends on tokens <= t, so the device path feeds one token per step, keeps
-// the self-attention keys/values of each layer in HBM ([B, T, 3*H*64] bf16: the fused q|k|v projection writes row t in place)
+// the self-attention keys/values of each layer in HBM ([B, T, 3*H*dk] bf16: the fused q|k|v projection writes row t in place)
 // and projects the cross-attention keys/values of the encoder memory once per layer.
 //
 //   dig_decode_embed       x[b,:] = trg_word_emb[token[b],:] + position_table[t,:]              (decoder.py:173-181)
 //   dig_decode_self_attn   one query (row t) against cached rows 0..t, per (sample, head)        (transformer_layer.py:238-281)
 //   dig_decode_cross_attn  one query against the Nm memory keys/values, per (sample, head); optional per-head weights
 //   dig_softmax_argmax     probabilities + greedy token of a logit row                           (decoder.py:238-246)
-// Head dimension 64 (d_k = d_v = 64: `tf_decoder` and `small_tf_decoder`).  All HBM-bound and tiny; one wave (self) or four
-// waves (cross) per (sample, head), fp32 softmax.
+// Head dimension d_k = d_v = 64 (`tf_decoder`, `small_tf_decoder`, `corres_base_tf_decoder`), 48 (`corres_small_tf_decoder`) or 24
+// (`corres_tiny_tf_decoder`): a template parameter of the two attention kernels, heads are not padded.  All HBM-bound and tiny; one
+// wave (self) or four waves (cross) per (sample, head), fp32 softmax.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,8 +18,6 @@
 #include "common.h"
 
 namespace {
-
-constexpr int DK = 64;
 
 __global__ __launch_bounds__(256) void embed_kernel(const long long* __restrict__ tok, const float* __restrict__ emb,
                                                     const float* __restrict__ pe_row, bf16_t* __restrict__ x, int B, int d, int vocab) {
@@ -30,13 +29,16 @@ __global__ __launch_bounds__(256) void embed_kernel(const long long* __restrict_
   x[i] = f2bf(emb[(size_t)t * d + c] + pe_row[c]);
 }
 
-// qkv: [B, T, 3*hk] bf16 (q | k | v), row t holds this step's projections; out: [B, hk] bf16
+// qkv: [B, T, 3*hk] bf16 (q | k | v), row t holds this step's projections; out: [B, hk] bf16.  One wave, lane = channel: at head dim
+// 24 / 48 the lanes >= DK read channel 0 (never past the head: the last head's v columns end the row), carry a zero query and write nothing.
+template <int DK>
 __global__ __launch_bounds__(64) void self_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int T, int hk, int t,
                                                        float scale) {
   const int b = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+  const bool live = DK == 64 || lane < DK;
   const size_t row = (size_t)3 * hk;
-  const bf16_t* base = qkv + (size_t)b * T * row + h * DK + lane;
-  const float q = bf2f(base[(size_t)t * row]) * scale;
+  const bf16_t* base = qkv + (size_t)b * T * row + h * DK + (live ? lane : 0);
+  const float q = live ? bf2f(base[(size_t)t * row]) * scale : 0.f;
   float m = -INFINITY, l = 0.f, acc = 0.f;                             // online softmax over the t+1 cached positions
   for (int j = 0; j <= t; ++j) {
     const float s = wave_sum(q * bf2f(base[(size_t)j * row + hk]));
@@ -46,22 +48,28 @@ __global__ __launch_bounds__(64) void self_attn_kernel(const bf16_t* __restrict_
     acc = acc * c + p * bf2f(base[(size_t)j * row + 2 * hk]);
     m = mn;
   }
-  out[(size_t)b * hk + h * DK + lane] = f2bf(acc / l);
+  if (live) out[(size_t)b * hk + h * DK + lane] = f2bf(acc / l);
 }
 
 // q: [B, hk] bf16; kv: [B, Nm, 2*hk] bf16 (k | v); out: [B, hk] bf16; weights (optional): [B, H, Nm] fp32
 // 256 threads = 32 key slots x 8 channel chunks: a lane loads 16 bytes (8 channels) of one key row, so 8 consecutive lanes
 // cover a whole 128-byte row and every load instruction of a wave moves 8 full rows (coalesced; the first version gave each
 // thread its own row and ran at 1.8 TB/s).  Scores: partial dot over the lane's 8 channels + 3 shuffles.  Values: each lane
-// accumulates its 8 channels over its key slot's keys, then shuffles / LDS combine the 32 slots.
+// accumulates its 8 channels over its key slot's keys, then shuffles / LDS combine the 32 slots.  At head dim 24 / 48 a row has
+// DK / 8 = 3 / 6 chunks: a key slot keeps its 8 lanes (the three shuffles stay inside the slot), the surplus lanes (chunk >= DK / 8) load
+// nothing and add zero.
+template <int DK>
 __global__ __launch_bounds__(256) void cross_attn_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kv, bf16_t* __restrict__ out,
                                                          float* __restrict__ weights, int Nm, int hk, float scale, int slots_per_mem) {
-  extern __shared__ float sm[];                                        // [Nm] scores / probabilities, then [4][64] partial outputs
+  extern __shared__ float sm[];                                        // [Nm] scores / probabilities, then [4][DK] partial outputs
   __shared__ float red[8];
   const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, H = gridDim.y;
   const int chunk = tid & 7, slot = tid >> 3;                           // 8 channels [chunk*8, +8); keys slot, slot+32, ...
+  const bool live = DK == 64 || chunk < DK / 8;
   float qv[8];
-  {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) qv[e] = 0.f;
+  if (live) {
     const uint4 v = *reinterpret_cast<const uint4*>(q + (size_t)b * hk + h * DK + chunk * 8);
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -70,11 +78,13 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const bf16_t* __restric
   const bf16_t* kb = kv + (size_t)(b / slots_per_mem) * Nm * 2 * hk + h * DK + chunk * 8;   // beam search: `slots_per_mem` queries share a memory
   float lmax = -INFINITY;
   for (int j = slot; j < Nm; j += 32) {
-    const uint4 v = *reinterpret_cast<const uint4*>(kb + (size_t)j * 2 * hk);
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
     float s = 0.f;
+    if (live) {
+      const uint4 v = *reinterpret_cast<const uint4*>(kb + (size_t)j * 2 * hk);
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) s += qv[2 * e] * bf2f((bf16_t)(w[e] & 0xffff)) + qv[2 * e + 1] * bf2f((bf16_t)(w[e] >> 16));
+      for (int e = 0; e < 4; ++e) s += qv[2 * e] * bf2f((bf16_t)(w[e] & 0xffff)) + qv[2 * e + 1] * bf2f((bf16_t)(w[e] >> 16));
+    }
     s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
     if (chunk == 0) sm[j] = s;
     lmax = fmaxf(lmax, s);
@@ -98,7 +108,7 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const bf16_t* __restric
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-  for (int j = slot; j < Nm; j += 32) {
+  for (int j = slot; live && j < Nm; j += 32) {
     const uint4 v = *reinterpret_cast<const uint4*>(kb + (size_t)j * 2 * hk + hk);
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
     const float p = sm[j];
@@ -111,7 +121,7 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const bf16_t* __restric
   }
   __syncthreads();                                                      // probabilities are no longer needed
   float* part = sm;
-  if ((tid & 63) < 8) {
+  if ((tid & 63) < 8 && live) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) part[(tid >> 6) * DK + chunk * 8 + e] = acc[e];
   }
@@ -380,19 +390,27 @@ extern "C" int dig_decode_embed(const long long* tokens, const float* emb, const
 extern "C" int dig_decode_self_attn(const void* qkv_cache, void* out, int B, int T, int heads, int head_dim, int t, float scale,
                                     hipStream_t stream) {
   if (!qkv_cache || !out || B <= 0 || heads <= 0 || t < 0 || t >= T) return DIG_ERR_ARG;
-  if (head_dim != DK) return DIG_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(self_attn_kernel, dim3(B, heads), dim3(64), 0, stream, (const bf16_t*)qkv_cache, (bf16_t*)out, T, heads * DK, t, scale);
+  const bf16_t* in = (const bf16_t*)qkv_cache;
+  const int hk = heads * head_dim;
+  if (head_dim == 64) hipLaunchKernelGGL(self_attn_kernel<64>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
+  else if (head_dim == 48) hipLaunchKernelGGL(self_attn_kernel<48>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
+  else if (head_dim == 24) hipLaunchKernelGGL(self_attn_kernel<24>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
+  else return DIG_ERR_UNSUPPORTED;
   return dig_check_launch();
 }
 
 extern "C" int dig_decode_cross_attn(const void* q, const void* kv_mem, void* out, float* weights, int B, int n_mem, int heads,
                                      int head_dim, float scale, int slots_per_mem, hipStream_t stream) {
   if (!q || !kv_mem || !out || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
-  if (head_dim != DK || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
+  if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
   if (!aligned16(kv_mem)) return DIG_ERR_ALIGN;
-  const size_t lds = (size_t)std::max(n_mem, 4 * DK) * sizeof(float);
-  hipLaunchKernelGGL(cross_attn_kernel, dim3(B, heads), dim3(256), lds, stream, (const bf16_t*)q, (const bf16_t*)kv_mem, (bf16_t*)out, weights,
-                     n_mem, heads * DK, scale, slots_per_mem);
+  const size_t lds = (size_t)std::max(n_mem, 4 * head_dim) * sizeof(float);
+  const bf16_t* qp = (const bf16_t*)q;
+  const bf16_t* kv = (const bf16_t*)kv_mem;
+  const int hk = heads * head_dim;
+  if (head_dim == 64) hipLaunchKernelGGL(cross_attn_kernel<64>, dim3(B, heads), dim3(256), lds, stream, qp, kv, (bf16_t*)out, weights, n_mem, hk, scale, slots_per_mem);
+  else if (head_dim == 48) hipLaunchKernelGGL(cross_attn_kernel<48>, dim3(B, heads), dim3(256), lds, stream, qp, kv, (bf16_t*)out, weights, n_mem, hk, scale, slots_per_mem);
+  else hipLaunchKernelGGL(cross_attn_kernel<24>, dim3(B, heads), dim3(256), lds, stream, qp, kv, (bf16_t*)out, weights, n_mem, hk, scale, slots_per_mem);
   return dig_check_launch();
 }
 

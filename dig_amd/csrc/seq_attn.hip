@@ -3,7 +3,9 @@
 //   self-attention : 25 queries x 25 keys per (sample, head), mask = causal & (key < length[sample])   (decoder.py:183-184)
 //   cross-attention: 25 queries x 256 memory keys, no mask
 // A few GFLOP per batch: one workgroup per (sample, head), K and V of that head in LDS (bf16, padded rows), scores / probabilities
-// in LDS (fp32), plain FMA loops -- these kernels are launch- and latency-bound, not worth MFMA tiles.  Head dim 64.
+// in LDS (fp32), plain FMA loops -- these kernels are launch- and latency-bound, not worth MFMA tiles.  The head dim is a template
+// parameter: 64 (`tf_decoder`, `small_tf_decoder`, `corres_base_tf_decoder`), 48 (`corres_small_tf_decoder`) and 24 (`corres_tiny_tf_decoder`);
+// heads are NOT padded to 64 (that would multiply the K|V projection of the memory and its bytes by up to 2.7).
 // logits = (q . k) * scale; masked logits -> probability 0; lse saved for the backward, which recomputes the probabilities.
 #include <hip/hip_runtime.h>
 
@@ -13,8 +15,7 @@
 
 namespace {
 
-constexpr int DK = 64;
-constexpr int KROW = DK + 2;                   // bf16 elements per K / V row in LDS (132 B: consecutive rows hit different banks)
+template <int DK> constexpr int KROW = DK + 2;   // bf16 elements per K / V row in LDS: an odd dword stride at every head dim (13, 25, 33), so consecutive rows hit different banks
 constexpr int MAXQ = 32;
 
 struct SeqAttnParams {
@@ -38,14 +39,17 @@ __device__ __forceinline__ bool key_ok(const SeqAttnParams& p, int i, int j, lon
 
 // L8 (few keys: the 25 x 25 self-attention, where a thread per key would leave 231 of 256 threads idle): 8 lanes share one key,
 // 8 channels each (a wave load covers 8 whole 128-byte rows), 32 keys per pass, dot products finished by three lane shuffles.
+// At head dim 24 / 48 a key has DK / 8 = 3 / 6 chunks: the group stays 8 lanes wide (the shuffles never leave a key's group), its
+// surplus lanes (chunk >= DK / 8) hold zeros for K / V, read chunk 0 of the query side and store nothing.
 // Work split otherwise.  Score-shaped products (S = Q K^T, dP = dO V^T, dK = dS^T Q, dV = P^T dO): a thread owns ONE key, its K / V rows
 // (or dK / dV accumulators) live in registers and the query-side rows are read from LDS as broadcasts -- pure FMA streams.
-// Output-shaped products (O = P V, dQ = dS K): a thread owns one channel d and every 4th query, K / V come from LDS (bf16,
+// Output-shaped products (O = P V, dQ = dS K): a thread owns one channel d and every (256 / DK)-th query, K / V come from LDS (bf16,
 // consecutive lanes = consecutive channels) and the probabilities are broadcast reads.
 
-__device__ __forceinline__ void load_row64(const bf16_t* __restrict__ src, float (&r)[DK]) {
+template <int DK>
+__device__ __forceinline__ void load_row(const bf16_t* __restrict__ src, float (&r)[DK]) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c) {
+  for (int c = 0; c < DK / 8; ++c) {
     const uint4 v = reinterpret_cast<const uint4*>(src)[c];
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -53,14 +57,16 @@ __device__ __forceinline__ void load_row64(const bf16_t* __restrict__ src, float
   }
 }
 
-__device__ __forceinline__ void store_row64(bf16_t* __restrict__ dst, const float (&r)[DK], float scale) {
+template <int DK>
+__device__ __forceinline__ void store_row(bf16_t* __restrict__ dst, const float (&r)[DK], float scale) {
 #pragma unroll
-  for (int c = 0; c < 8; ++c)
+  for (int c = 0; c < DK / 8; ++c)
     reinterpret_cast<uint4*>(dst)[c] = make_uint4(pack_bf2(r[c * 8] * scale, r[c * 8 + 1] * scale), pack_bf2(r[c * 8 + 2] * scale, r[c * 8 + 3] * scale),
                                                  pack_bf2(r[c * 8 + 4] * scale, r[c * 8 + 5] * scale), pack_bf2(r[c * 8 + 6] * scale, r[c * 8 + 7] * scale));
 }
 
-__device__ __forceinline__ float dot64(const float* __restrict__ q, const float (&k)[DK]) {
+template <int DK>
+__device__ __forceinline__ float dot_row(const float* __restrict__ q, const float (&k)[DK]) {
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;                        // four independent chains (a single one is latency-bound)
 #pragma unroll
   for (int d4 = 0; d4 < DK / 4; ++d4) {
@@ -84,38 +90,44 @@ __device__ __forceinline__ float dot8_reduce(const float* __restrict__ q8, const
   return s;
 }
 
-// stage one [Lk][64] bf16 operand of this (sample, head) into LDS, 16 bytes per thread and step
-__device__ __forceinline__ void stage64(const bf16_t* __restrict__ src, int ld, int b, int h, int Lk, bf16_t* __restrict__ dst) {
-  for (int e = threadIdx.x; e < Lk * 8; e += blockDim.x) {
-    const int j = e >> 3, c = e & 7;
+// stage one [Lk][DK] bf16 operand of this (sample, head) into LDS, 16 bytes per thread and step
+template <int DK>
+__device__ __forceinline__ void stage_rows(const bf16_t* __restrict__ src, int ld, int b, int h, int Lk, bf16_t* __restrict__ dst) {
+  constexpr unsigned CH = DK / 8;
+  for (unsigned e = threadIdx.x; e < Lk * CH; e += blockDim.x) {
+    const unsigned j = e / CH, c = e % CH;
     reinterpret_cast<uint4*>(dst)[e] = reinterpret_cast<const uint4*>(src + ((size_t)b * Lk + j) * ld + h * DK)[c];
   }
 }
 
-// out[i][d] = scale_i * sum_j W[i][j] * X[j][d] for the queries i = (tid>>6), +4, ...  (W fp32 [Lq][Lk] in LDS, X bf16 [Lk][64] in LDS)
-template <typename Store>
+// out[i][d] = scale_i * sum_j W[i][j] * X[j][d]  (W fp32 [Lq][Lk] in LDS, X bf16 [Lk][DK] in LDS).  The 256 threads form G = 256 / DK
+// groups of DK consecutive threads (4 / 5 / 10 at head dim 64 / 48 / 24; the 256 - G * DK threads behind them idle): a thread owns channel
+// d = tid % DK and the queries i = tid / DK, + G, ...
+template <int DK, typename Store>
 __device__ __forceinline__ void rows_times_x(const float* __restrict__ W, const bf16_t* __restrict__ X, int Lq, int Lk, Store store) {
-  const int d = threadIdx.x & 63, g = threadIdx.x >> 6;
-  float acc[MAXQ / 4];
+  constexpr int G = 256 / DK, NU = (MAXQ + G - 1) / G;
+  const int d = threadIdx.x % (unsigned)DK, g = threadIdx.x / (unsigned)DK;
+  if (G * DK < 256 && g >= G) return;
+  float acc[NU];
 #pragma unroll
-  for (int u = 0; u < MAXQ / 4; ++u) acc[u] = 0.f;
+  for (int u = 0; u < NU; ++u) acc[u] = 0.f;
   for (int j = 0; j < Lk; ++j) {
     const float x = bf2f(X[j * DK + d]);
 #pragma unroll
-    for (int u = 0; u < MAXQ / 4; ++u) {
-      const int i = g + 4 * u;
+    for (int u = 0; u < NU; ++u) {
+      const int i = g + G * u;
       if (i < Lq) acc[u] += W[i * Lk + j] * x;
     }
   }
 #pragma unroll
-  for (int u = 0; u < MAXQ / 4; ++u) {
-    const int i = g + 4 * u;
+  for (int u = 0; u < NU; ++u) {
+    const int i = g + G * u;
     if (i < Lq) store(i, d, acc[u]);
   }
 }
 
-// LDS: Qs [MAXQ][64] f32 | S [MAXQ][Lk] f32 | rowinv [MAXQ] f32 | Vs [Lk][64] bf16
-template <bool L8>
+// LDS: Qs [MAXQ][DK] f32 | S [MAXQ][Lk] f32 | rowinv [MAXQ] f32 | Vs [Lk][DK] bf16
+template <int DK, bool L8>
 __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqAttnParams p, bf16_t* __restrict__ out, int ldo, float* __restrict__ lse) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Qs = reinterpret_cast<float*>(smem);
@@ -128,28 +140,30 @@ __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqAttnParams p, bf16
     const int i = e / DK, d = e - i * DK;
     Qs[e] = bf2f(p.q[((size_t)b * p.Lq + i) * p.ldq + h * DK + d]) * p.scale;
   }
-  stage64(p.v, p.ldv, b, h, p.Lk, Vs);
+  stage_rows<DK>(p.v, p.ldv, b, h, p.Lk, Vs);
   __syncthreads();
   if (L8) {
     const int ch = tid & 7;
+    const bool live = DK == 64 || ch < DK / 8;                          // (a surplus lane of the key's group: zeros against chunk 0)
+    const int cq = live ? ch : 0;
     for (int j0 = 0; j0 < p.Lk; j0 += 32) {
       const int j = j0 + (tid >> 3);
       float k8[8];
-      if (j < p.Lk) load8(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK + ch * 8, k8);
+      if (j < p.Lk && live) load8(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK + ch * 8, k8);
       else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) k8[e] = 0.f;
       }
       for (int i = 0; i < p.Lq; ++i) {
-        const float sc = dot8_reduce(Qs + i * DK + ch * 8, k8);
+        const float sc = dot8_reduce(Qs + i * DK + cq * 8, k8);
         if (ch == 0 && j < p.Lk) S[i * p.Lk + j] = key_ok(p, i, j, len) ? sc : -INFINITY;
       }
     }
   } else {
     for (int j = tid; j < p.Lk; j += 256) {                              // logits of my key against every query
       float kr[DK];
-      load_row64(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK, kr);
-      for (int i = 0; i < p.Lq; ++i) S[i * p.Lk + j] = key_ok(p, i, j, len) ? dot64(Qs + i * DK, kr) : -INFINITY;
+      load_row<DK>(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK, kr);
+      for (int i = 0; i < p.Lq; ++i) S[i * p.Lk + j] = key_ok(p, i, j, len) ? dot_row<DK>(Qs + i * DK, kr) : -INFINITY;
     }
   }
   __syncthreads();
@@ -170,11 +184,11 @@ __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqAttnParams p, bf16
     }
   }
   __syncthreads();
-  rows_times_x(S, Vs, p.Lq, p.Lk, [&](int i, int d, float a) { out[((size_t)b * p.Lq + i) * ldo + h * DK + d] = f2bf(a * rowinv[i]); });
+  rows_times_x<DK>(S, Vs, p.Lq, p.Lk, [&](int i, int d, float a) { out[((size_t)b * p.Lq + i) * ldo + h * DK + d] = f2bf(a * rowinv[i]); });
 }
 
-// LDS: Qs, Gs [MAXQ][64] f32 | P, dS [MAXQ][Lk] f32 | Ks [Lk][64] bf16
-template <bool L8>
+// LDS: Qs, Gs [MAXQ][DK] f32 | P, dS [MAXQ][Lk] f32 | Ks [Lk][DK] bf16
+template <int DK, bool L8>
 __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, const bf16_t* __restrict__ dout, int ldo, const float* __restrict__ lse,
                                                            bf16_t* __restrict__ dq, int lddq, bf16_t* __restrict__ dk, int lddk,
                                                            bf16_t* __restrict__ dv, int lddv) {
@@ -193,14 +207,15 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, cons
     Qs[e] = bf2f(p.q[r * p.ldq + h * DK + d]);
     Gs[e] = bf2f(dout[r * ldo + h * DK + d]);
   }
-  stage64(p.k, p.ldk, b, h, p.Lk, Ks);
+  stage_rows<DK>(p.k, p.ldk, b, h, p.Lk, Ks);
   __syncthreads();
+  const bool live = DK == 64 || (tid & 7) < DK / 8;                     // L8: a surplus lane of the key's group holds zeros, reads chunk 0, stores nothing
   if (L8) {
-    const int ch = tid & 7;
+    const int ch = tid & 7, cq = live ? ch : 0;
     for (int j0 = 0; j0 < p.Lk; j0 += 32) {                              // P[:, j] and dP[:, j]
       const int j = j0 + (tid >> 3);
       float k8[8], v8[8];
-      if (j < p.Lk) {
+      if (j < p.Lk && live) {
         load8(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK + ch * 8, k8);
         load8(p.v + ((size_t)b * p.Lk + j) * p.ldv + h * DK + ch * 8, v8);
       } else {
@@ -208,8 +223,8 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, cons
         for (int e = 0; e < 8; ++e) { k8[e] = 0.f; v8[e] = 0.f; }
       }
       for (int i = 0; i < p.Lq; ++i) {
-        const float sc = dot8_reduce(Qs + i * DK + ch * 8, k8) * p.scale;
-        const float dp = dot8_reduce(Gs + i * DK + ch * 8, v8);
+        const float sc = dot8_reduce(Qs + i * DK + cq * 8, k8) * p.scale;
+        const float dp = dot8_reduce(Gs + i * DK + cq * 8, v8);
         if (ch == 0 && j < p.Lk) {
           const bool ok = key_ok(p, i, j, len);
           P[i * p.Lk + j] = ok ? __expf(sc - lse_row[i]) : 0.f;
@@ -220,13 +235,13 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, cons
   } else {
     for (int j = tid; j < p.Lk; j += 256) {                                // my key: P[:, j] and dP[:, j]
       float kr[DK], vr[DK];
-      load_row64(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK, kr);
-      load_row64(p.v + ((size_t)b * p.Lk + j) * p.ldv + h * DK, vr);
+      load_row<DK>(p.k + ((size_t)b * p.Lk + j) * p.ldk + h * DK, kr);
+      load_row<DK>(p.v + ((size_t)b * p.Lk + j) * p.ldv + h * DK, vr);
       for (int i = 0; i < p.Lq; ++i) {
         float pr = 0.f, dp = 0.f;
         if (key_ok(p, i, j, len)) {
-          pr = __expf(dot64(Qs + i * DK, kr) * p.scale - lse_row[i]);
-          dp = dot64(Gs + i * DK, vr) * drop_factor(p, b * gridDim.y + h, i, j);   // dP = mask * (dO V^T) / (1 - p)
+          pr = __expf(dot_row<DK>(Qs + i * DK, kr) * p.scale - lse_row[i]);
+          dp = dot_row<DK>(Gs + i * DK, vr) * drop_factor(p, b * gridDim.y + h, i, j);   // dP = mask * (dO V^T) / (1 - p)
         }
         P[i * p.Lk + j] = pr;
         dS[i * p.Lk + j] = dp;
@@ -245,7 +260,7 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, cons
     const int ch = tid & 7;
     for (int j0 = 0; j0 < p.Lk; j0 += 32) {                              // dK[j, 8 ch] = scale * sum_i dS[i,j] Q[i, ch], dV[j, 8 ch] = sum_i P~[i,j] dO[i, ch]
       const int j = j0 + (tid >> 3);
-      if (j >= p.Lk) continue;
+      if (j >= p.Lk || !live) continue;                                   // (a 16-byte store of a surplus lane would land in the next head's columns)
       float ak[8], av[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { ak[e] = 0.f; av[e] = 0.f; }
@@ -278,11 +293,11 @@ __global__ __launch_bounds__(256) void seq_attn_bwd_kernel(SeqAttnParams p, cons
         }
       }
       const size_t r = (size_t)b * p.Lk + j;
-      store_row64(dk + r * lddk + h * DK, ak, p.scale);
-      store_row64(dv + r * lddv + h * DK, av, 1.f);
+      store_row<DK>(dk + r * lddk + h * DK, ak, p.scale);
+      store_row<DK>(dv + r * lddv + h * DK, av, 1.f);
     }
   }
-  rows_times_x(dS, Ks, p.Lq, p.Lk, [&](int i, int d, float a) { dq[((size_t)b * p.Lq + i) * lddq + h * DK + d] = f2bf(a * p.scale); });
+  rows_times_x<DK>(dS, Ks, p.Lq, p.Lk, [&](int i, int d, float a) { dq[((size_t)b * p.Lq + i) * lddq + h * DK + d] = f2bf(a * p.scale); });
 }
 
 // x[b*T + t, :] = emb[token[b, t], :] + pos[t, :]   (decoder.py:173-181: trg_word_emb + PositionalEncoding; dropout p = 0)
@@ -362,63 +377,94 @@ __global__ __launch_bounds__(64) void seq_ce_bwd_kernel(const float* __restrict_
   for (int c = lane; c < ldd; c += 64) out[c] = c < C ? f2bf(sc * (__expf(x[c] - m) * inv - (c == y ? 1.f : 0.f))) : (bf16_t)0;
 }
 
-size_t lds_fwd(int Lk) { return (size_t)MAXQ * DK * 4 + (size_t)MAXQ * Lk * 4 + MAXQ * 4 + (size_t)Lk * DK * 2; }
-size_t lds_bwd(int Lk) { return (size_t)2 * MAXQ * DK * 4 + (size_t)2 * MAXQ * Lk * 4 + (size_t)Lk * DK * 2; }
+template <int DK> size_t lds_fwd(int Lk) { return (size_t)MAXQ * DK * 4 + (size_t)MAXQ * Lk * 4 + MAXQ * 4 + (size_t)Lk * DK * 2; }
+template <int DK> size_t lds_bwd(int Lk) { return (size_t)2 * MAXQ * DK * 4 + (size_t)2 * MAXQ * Lk * 4 + (size_t)Lk * DK * 2; }
+
+template <int DK>
+int launch_fwd(const SeqAttnParams& p, void* out, int ldo, float* lse, int B, int heads, hipStream_t stream) {
+  const size_t lds = lds_fwd<DK>(p.Lk);
+  static size_t attr = 0;
+  static size_t attr8 = 0;
+  if (p.Lk <= 64) {                                                          // few keys: 8 lanes per key
+    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
+    hipLaunchKernelGGL((seq_attn_fwd_kernel<DK, true>), dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
+    return dig_check_launch();
+  }
+  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
+  hipLaunchKernelGGL((seq_attn_fwd_kernel<DK, false>), dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
+  return dig_check_launch();
+}
+
+template <int DK>
+int launch_bwd(const SeqAttnParams& p, const void* dout, int ldo, const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B,
+               int heads, hipStream_t stream) {
+  const size_t lds = lds_bwd<DK>(p.Lk);
+  static size_t attr = 0;
+  static size_t attr8 = 0;
+  if (p.Lk <= 64 && !(lddk & 7) && !(lddv & 7) && aligned16(dk) && aligned16(dv)) {   // few keys: 8 lanes per key (16-byte dK / dV stores)
+    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
+    hipLaunchKernelGGL((seq_attn_bwd_kernel<DK, true>), dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq,
+                       (bf16_t*)dk, lddk, (bf16_t*)dv, lddv);
+    return dig_check_launch();
+  }
+  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
+  hipLaunchKernelGGL((seq_attn_bwd_kernel<DK, false>), dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq, (bf16_t*)dk,
+                     lddk, (bf16_t*)dv, lddv);
+  return dig_check_launch();
+}
 
 }  // namespace
 
 // C-ABI: see include/dig_hip.h
+extern "C" int dig_seq_attn_fwd_hd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
+                                   int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop,
+                                   int head_dim, hipStream_t stream) {
+  if (!q || !k || !v || !out || !lse || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
+  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
+  SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
+  if (head_dim == 24) return launch_fwd<24>(p, out, ldo, lse, B, heads, stream);
+  if (head_dim == 48) return launch_fwd<48>(p, out, ldo, lse, B, heads, stream);
+  return launch_fwd<64>(p, out, ldo, lse, B, heads, stream);
+}
+
 extern "C" int dig_seq_attn_fwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse,
                                         int B, int heads, int Lq, int Lk, float scale, int causal, const long long* lens,
                                         const dig_dropout_t* drop, hipStream_t stream) {
-  if (!q || !k || !v || !out || !lse || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
-  SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
-  const size_t lds = lds_fwd(Lk);
-  static size_t attr = 0;
-  static size_t attr8 = 0;
-  if (Lk <= 64) {                                                            // few keys: 8 lanes per key
-    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
-    hipLaunchKernelGGL(seq_attn_fwd_kernel<true>, dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
-    return dig_check_launch();
-  }
-  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
-  hipLaunchKernelGGL(seq_attn_fwd_kernel<false>, dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
-  return dig_check_launch();
+  return dig_seq_attn_fwd_hd(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, drop, 64, stream);
 }
 
 extern "C" int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
                                 int heads, int Lq, int Lk, float scale, int causal, const long long* lens, hipStream_t stream) {
-  return dig_seq_attn_fwd_dropout(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, nullptr, stream);
+  return dig_seq_attn_fwd_hd(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, nullptr, 64, stream);
+}
+
+extern "C" int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo,
+                                   const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq,
+                                   int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, int head_dim,
+                                   hipStream_t stream) {
+  if (!q || !k || !v || !dout || !lse || !dq || !dk || !dv || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
+  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
+  SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
+  if (head_dim == 24) return launch_bwd<24>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
+  if (head_dim == 48) return launch_bwd<48>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
+  return launch_bwd<64>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
 }
 
 extern "C" int dig_seq_attn_bwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo,
                                         const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq,
                                         int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop,
                                         hipStream_t stream) {
-  if (!q || !k || !v || !dout || !lse || !dq || !dk || !dv || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
-  SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
-  const size_t lds = lds_bwd(Lk);
-  static size_t attr = 0;
-  static size_t attr8 = 0;
-  if (Lk <= 64 && !(lddk & 7) && !(lddv & 7) && aligned16(dk) && aligned16(dv)) {   // few keys: 8 lanes per key (16-byte dK / dV stores)
-    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
-    hipLaunchKernelGGL(seq_attn_bwd_kernel<true>, dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq,
-                       (bf16_t*)dk, lddk, (bf16_t*)dv, lddv);
-    return dig_check_launch();
-  }
-  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
-  hipLaunchKernelGGL(seq_attn_bwd_kernel<false>, dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq, (bf16_t*)dk,
-                     lddk, (bf16_t*)dv, lddv);
-  return dig_check_launch();
+  return dig_seq_attn_bwd_hd(q, ldq, k, ldk, v, ldv, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, Lq, Lk, scale, causal, lens, drop, 64,
+                             stream);
 }
 
 extern "C" int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo,
                                 const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq, int Lk,
                                 float scale, int causal, const long long* lens, hipStream_t stream) {
-  return dig_seq_attn_bwd_dropout(q, ldq, k, ldk, v, ldv, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, Lq, Lk, scale, causal, lens,
-                                  nullptr, stream);
+  return dig_seq_attn_bwd_hd(q, ldq, k, ldk, v, ldv, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, Lq, Lk, scale, causal, lens, nullptr,
+                             64, stream);
 }
 
 extern "C" int dig_seq_embed_fwd(const long long* tokens, const float* emb, const float* pos_table, void* x, int B, int T, int d, int vocab,

@@ -10,7 +10,7 @@ come from a keyed counter hash instead of torch's generator, see dig_amd/dropout
     run_class_finetuning.py:471-520) as one fused AdamW launch over a flat parameter arena.
 Parameters, gradients, Adam moments and the bf16 GEMM operands live in flat arenas (dig_amd/arena.py: each tensor padded to the granule) whose
 layout keeps q|k|v (and k|v) projection weights adjacent, so the fused projections are views.  The whole model is ONE autograd
-node with a hand-written backward on the hot-path kernels (encoder: the pre-training kernels; decoder: `dig_seq_attn_*`,
+node with a hand-written backward on the hot-path kernels (encoder: the pre-training kernels; decoder: `dig_seq_attn_*_hd` at the decoder's head dim (24 / 48 / 64),
 `dig_seq_embed_*`, `dig_gemm_bf16`, `dig_layernorm_*`; with `--text_cond_vis` the cross-attention is `dig_tcv_attn_fwd / _bwd` between per-head
 fold GEMMs, see dig_amd/recognizer.py).  The CPU checker of this step lives with the tests."""
 import ctypes
@@ -361,8 +361,8 @@ class _TrainStep:
             qkv = ops.linear_fwd(h1, M._w[p]["qkv"])
             a = torch.empty((B * T, hk), device=dev, dtype=BF16)
             lse1 = torch.empty((B, nh, T), device=dev, dtype=F32)
-            L.call("dig_seq_attn_fwd_dropout", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(a), hk,
-                   L.ptr(lse1), B, nh, T, T, cf(sc), 1, L.ptr(self.lens), _ref(ds["sattn"]), L.stream())
+            L.call("dig_seq_attn_fwd_hd", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(a), hk,
+                   L.ptr(lse1), B, nh, T, T, cf(sc), 1, L.ptr(self.lens), _ref(ds["sattn"]), dk, L.stream())
             x1 = ops.linear_fwd(a, self.w(p + "self_attn.fc.weight"), resid=x, drop=ds["sproj"])
             h2, m2, r2 = ops.layernorm_fwd(x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), 1e-5)
             q2 = None if tcv else ops.linear_fwd(h2, self.w(p + "enc_attn.linear_q.weight"))
@@ -388,11 +388,12 @@ class _TrainStep:
                 a2, ctx2, lse2 = EB.cross_attn_fwd(fused, q2, B, T, nh, hk, sc, drop=ds["cattn"])
                 kvm, lse2 = fused, (lse2, ctx2)
             else:
+                # head dim 24 / 48 (the `corres_*` decoders), --use_1d_attdec (32 keys): the sequence kernels over all N keys
                 kvm = ops.linear_fwd(mem, M._w[p]["kv2"])
                 a2 = torch.empty((B * T, hk), device=dev, dtype=BF16)
                 lse2 = torch.empty((B, nh, T), device=dev, dtype=F32)
-                L.call("dig_seq_attn_fwd_dropout", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(a2), hk, L.ptr(lse2), B, nh,
-                       T, N, cf(sc), 0, None, _ref(ds["cattn"]), L.stream())
+                L.call("dig_seq_attn_fwd_hd", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(a2), hk, L.ptr(lse2), B, nh,
+                       T, N, cf(sc), 0, None, _ref(ds["cattn"]), dk, L.stream())
             x2 = ops.linear_fwd(a2, self.w(p + "enc_attn.fc.weight"), resid=x1, drop=ds["cproj"])
             h3, m3, r3 = ops.layernorm_fwd(x2, self.p(p + "norm3.weight"), self.p(p + "norm3.bias"), 1e-5)
             pre = torch.empty((B * T, M.d_inner), device=dev, dtype=BF16)
@@ -548,9 +549,9 @@ class _TrainStep:
                 else:
                     dq2 = torch.empty_like(q2)
                     dkvm = torch.empty_like(kvm)
-                    L.call("dig_seq_attn_bwd_dropout", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(da2), hk, L.ptr(lse2),
+                    L.call("dig_seq_attn_bwd_hd", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(da2), hk, L.ptr(lse2),
                            L.ptr(dq2), hk, L.ptr(dkvm), 2 * hk, L.ptr(dkvm[:, hk:]), 2 * hk, B, nh, T, N, cf(sc), 0, None, _ref(ds["cattn"]),
-                           L.stream())
+                           dk, L.stream())
                 side(lambda: ops.linear_wgrad(dq2, h2, self.g(p + "enc_attn.linear_q.weight")), dq2, h2)
                 dh2 = ops.linear_dgrad(dq2, self.w(p + "enc_attn.linear_q.weight"))
                 side(lambda: ops.wgrad(dkvm, mem, self.g_of(M._w[p]["kv2"]), 2 * hk, hk, B * N), dkvm, mem)
@@ -569,9 +570,9 @@ class _TrainStep:
             side(lambda: ops.linear_wgrad(dz, a, self.g(p + "self_attn.fc.weight")), dz, a)
             da = ops.linear_dgrad(dz, self.w(p + "self_attn.fc.weight"))
             dqkv = torch.empty_like(qkv)
-            L.call("dig_seq_attn_bwd_dropout", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(da), hk,
+            L.call("dig_seq_attn_bwd_hd", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(da), hk,
                    L.ptr(lse1), L.ptr(dqkv), 3 * hk, L.ptr(dqkv[:, hk:]), 3 * hk, L.ptr(dqkv[:, 2 * hk:]), 3 * hk, B, nh, T, T, cf(sc), 1,
-                   L.ptr(self.lens), _ref(ds["sattn"]), L.stream())
+                   L.ptr(self.lens), _ref(ds["sattn"]), dk, L.stream())
             side(lambda: ops.linear_wgrad(dqkv, h1, self.g_of(M._w[p]["qkv"])), dqkv, h1)
             dh1 = ops.linear_dgrad(dqkv, M._w[p]["qkv"])
             dx = ops.layernorm_bwd(dh1, x0, self.p(p + "norm1.weight"), self.p(p + "norm1.bias"), m1, r1, dx1, self.g(p + "norm1.weight"),

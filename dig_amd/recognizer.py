@@ -31,7 +31,12 @@ cf = ctypes.c_float
 
 ENCODERS = {"simmim_vit_tiny_patch4_32x128": (192, 3), "simmim_vit_small_patch4_32x128": (384, 6), "simmim_vit_base_patch4_32x128": (512, 8)}
 DECODERS = {"tf_decoder": dict(n_layers=6, d_model=512, n_head=8, d_k=64, d_inner=256),
-            "small_tf_decoder": dict(n_layers=2, d_model=384, n_head=6, d_k=64, d_inner=192)}
+            "small_tf_decoder": dict(n_layers=2, d_model=384, n_head=6, d_k=64, d_inner=192),
+            # the decoders "consistent to the encoder" (models/decoder.py:35-72): 8 heads of d_model / 8, d_inner = 4 * d_model
+            "corres_tiny_tf_decoder": dict(n_layers=6, d_model=192, n_head=8, d_k=24, d_inner=768),
+            "corres_small_tf_decoder": dict(n_layers=6, d_model=384, n_head=8, d_k=48, d_inner=1536),
+            "corres_base_tf_decoder": dict(n_layers=6, d_model=512, n_head=8, d_k=64, d_inner=2048)}
+HEAD_DIMS = (24, 48, 64)          # the decoder head dims the attention kernels are built for (csrc/seq_attn.hip, csrc/decode.hip)
 
 
 def _sinusoid(n_position, d_hid):
@@ -49,6 +54,9 @@ class RecModel(torch.nn.Module):
         super().__init__()
         if args is not None:
             embed_dim, num_heads = ENCODERS[args.model]
+            if args.decoder_name == "decoupled_tf_decoder":
+                raise NotImplementedError("decoupled_tf_decoder is not built: DecoupledTransformerDecoderLayer.forward reads cls_query_attn_maps.size(), "
+                                          "and RecModel.forward passes None for it with every encoder factory of the reference")
             dk = DECODERS[args.decoder_name]
             n_layers, d_model, n_head, d_k, d_inner = dk["n_layers"], dk["d_model"], dk["n_head"], dk["d_k"], dk["d_inner"]
             nb_classes, max_len = args.nb_classes, args.max_len
@@ -56,8 +64,10 @@ class RecModel(torch.nn.Module):
             text_cond_vis = bool(getattr(args, "text_cond_vis", False))
             if getattr(args, "insert_sem", False):
                 raise NotImplementedError("semantic insertion (--insert_sem) is not built: no encoder factory of the reference enables it")
-        if d_k != 64 or embed_dim // num_heads != 64:
-            raise NotImplementedError("head dimension 64 only")
+        if embed_dim // num_heads != 64:
+            raise NotImplementedError("encoder head dimension 64 only")
+        if d_k not in HEAD_DIMS:
+            raise NotImplementedError(f"decoder head dimension {d_k}: the attention kernels are built for {HEAD_DIMS}")
         self.D, self.H, self.depth, self.F = embed_dim, num_heads, depth, 4 * embed_dim
         self.gh, self.gw, self.N = 8, 32, 256
         # --use_1d_attdec (run_class_finetuning.py:89, model_builder.py:145-148): the decoder attends over the gw column means of the
@@ -66,8 +76,9 @@ class RecModel(torch.nn.Module):
         self.n_mem = self.gw if self.use_1d_attdec else self.N
         # --text_cond_vis (run_class_finetuning.py, models/decoder.py:13-73): the decoder's cross-attention is the text-conditional one
         self.text_cond_vis = bool(text_cond_vis)
-        if self.text_cond_vis and (n_head * d_k != d_model or d_model not in (128, 384, 512)):
-            raise NotImplementedError("text-conditional attention is built for d_model = 64 * n_head in {128, 384, 512}")
+        if self.text_cond_vis and (d_k != 64 or n_head * d_k != d_model or d_model not in (128, 384, 512)):
+            raise NotImplementedError(f"text-conditional attention is built for d_model = 64 * n_head in {{128, 384, 512}} (the fold kernels are 64-wide "
+                                      f"per head), not for head dimension {d_k} with d_model {d_model}")
         self.n_layers, self.d, self.nh, self.dk, self.d_inner = n_layers, d_model, n_head, d_k, d_inner
         self.nb_classes, self.max_len, self.n_position = nb_classes, max_len, n_position
         self.start_idx = nb_classes                                         # decoder.py:149

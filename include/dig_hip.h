@@ -494,10 +494,11 @@ int dig_abiaug_tail(const unsigned char* packed, const long long* offsets, const
 
 /* ---- greedy decode with a K/V cache (models/decoder.py:173-252, models/transformer_layer.py:238-281)
  * One decode step of TFDecoder.forward_test per call sequence: dig_decode_embed (token embedding + position row t), then per
- * layer LayerNorm / dig_gemm_bf16 for the projections (the fused q|k|v GEMM writes row t of the [B, T, 3*heads*64] cache in
- * place), dig_decode_self_attn (row t against rows 0..t), dig_decode_cross_attn (against [B, n_mem, 2*heads*64] = k|v of the
+ * layer LayerNorm / dig_gemm_bf16 for the projections (the fused q|k|v GEMM writes row t of the [B, T, 3*heads*head_dim] cache in
+ * place), dig_decode_self_attn (row t against rows 0..t), dig_decode_cross_attn (against [B, n_mem, 2*heads*head_dim] = k|v of the
  * encoder memory, projected once; `weights` optional [B, heads, n_mem] fp32), and dig_softmax_argmax on the classifier logits.
- * head_dim must be 64. */
+ * head_dim is 24, 48 or 64 (heads are not padded: head h sits at columns [head_dim*h, head_dim*(h+1))); any other value returns
+ * DIG_ERR_UNSUPPORTED before anything is launched. */
 int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_row, void* x, int B, int d, int vocab,
                      hipStream_t stream);
 int dig_decode_self_attn(const void* qkv_cache, void* out, int B, int T, int heads, int head_dim, int t, float scale,
@@ -558,9 +559,10 @@ int dig_seq_confidence(const float* score, const int* text_len, int B, int T, do
 
 /* ---- fine-tune training step (drop rates 0)
  * Whole-sequence attention of the recognition decoder and its gradient (models/transformer_layer.py:238-281 under teacher forcing,
- * models/decoder.py:173-222): per (sample, head), Lq <= 32 queries against Lk <= 512 keys, head dim 64, logits = q.k * scale,
+ * models/decoder.py:173-222): per (sample, head), Lq <= 32 queries against Lk <= 512 keys, logits = q.k * scale,
  * mask = (causal ? key <= query : 1) & (lens ? key < lens[sample] : 1).  q / k / v / out rows are (sample, position) with the
- * given leading dimensions (elements), head h at columns [64h, 64h+64); lse: fp32 [B][heads][Lq]. */
+ * given leading dimensions (elements), head h at columns [head_dim*h, head_dim*(h+1)); lse: fp32 [B][heads][Lq].  These two entry
+ * points are head dim 64 (dig_seq_attn_fwd_hd / _bwd_hd below with head_dim = 64 and no dropout). */
 int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
                      int heads, int Lq, int Lk, float scale, int causal, const long long* lens, hipStream_t stream);
 int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo, const float* lse,
@@ -645,6 +647,16 @@ int dig_seq_attn_fwd_dropout(const void* q, int ldq, const void* k, int ldk, con
 int dig_seq_attn_bwd_dropout(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo,
                              const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq, int Lk,
                              float scale, int causal, const long long* lens, const dig_dropout_t* drop, hipStream_t stream);
+/* The same with the head dimension as an argument: head_dim 24 (`corres_tiny_tf_decoder`), 48 (`corres_small_tf_decoder`) or 64; any
+ * other value returns DIG_ERR_UNSUPPORTED before anything is launched.  Heads are not padded (head h at columns [head_dim*h,
+ * head_dim*(h+1)) of q / k / v / out and of the gradients; nothing outside those columns is written).  drop = NULL: no dropout.  The
+ * four entry points above forward here with head_dim = 64. */
+int dig_seq_attn_fwd_hd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
+                        int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, int head_dim,
+                        hipStream_t stream);
+int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo, const float* lse,
+                        void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq, int Lk, float scale, int causal,
+                        const long long* lens, const dig_dropout_t* drop, int head_dim, hipStream_t stream);
 
 /* ---- text-conditional cross-attention of the recognition decoder (`--text_cond_vis`: TextConditionalMultiHeadAttention,
  * models/transformer_layer.py:284-383), folded.  The reference FiLM-modulates the whole memory for every query,
