@@ -151,10 +151,10 @@ def test_seq_attention_hd_rejects_other_head_dims(abi_dev):
 
 
 # ------------------------------------------------------------------------------------------------ 2. decode kernels
-@pytest.mark.parametrize("dk", [24, 48])
+@pytest.mark.parametrize("dk", [24, 48, 64])
 def test_decode_attention_kernels_hd_vs_torch(abi_dev, dk):
-    """dig_decode_self_attn (T = 8, t in {0, 3, 7}) and dig_decode_cross_attn (n_mem in {32, 33, 256}, slots_per_mem in {1, 2}, with and without
-    `weights`) at head dim 24 / 48; tolerances of test_decode.py::test_decode_attention_kernels_vs_torch.  Rows behind the outputs stay untouched."""
+    """dig_decode_self_attn (T = 8, t in {0, 3, 7}) and dig_decode_cross_attn (n_mem in {1, 7, 32, 33, 256, 257}: fewer keys than the 32 key
+    slots, a second pass of the 256-thread loops; slots_per_mem in {1, 2}, with and without `weights`) at head dim 24 / 48 / 64; tolerances of test_decode.py::test_decode_attention_kernels_vs_torch.  Rows behind the outputs stay untouched."""
     from dig_amd import _lib as L
     dev = abi_dev
     torch.manual_seed(dk)
@@ -169,7 +169,7 @@ def test_decode_attention_kernels_hd_vs_torch(abi_dev, dk):
         v = qkv[:, :t + 1, 2 * hk:].float().view(B, t + 1, H, dk).permute(0, 2, 1, 3)
         ref = ((q @ k.transpose(-1, -2) * scale).softmax(-1) @ v).reshape(B, hk)
         assert (ob[:B].float() - ref).abs().max().item() < 2e-2 and bool((ob[B:].float() == POISON).all())
-    for Nm in (32, 33, 256):
+    for Nm in (1, 7, 32, 33, 256, 257):
         for spm in (1, 2):
             q = torch.randn(B, hk, device=dev).to(torch.bfloat16)
             kv = torch.randn(B // spm, Nm, 2 * hk, device=dev).to(torch.bfloat16)
