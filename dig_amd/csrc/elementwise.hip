@@ -445,7 +445,8 @@ __global__ void mse_fwd_bwd_kernel(const float* __restrict__ pred, int ld_p, con
   if (dig_grid_sum_last<1>(ws, mine, tot, red)) loss[0] += tot[0];
 }
 
-__global__ void add_bf16_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ o, size_t n8) {
+// (no __restrict__: the fine-tune gradient adds call it in place, o == a or o == b; every thread reads its 16 bytes of both before it writes them)
+__global__ void add_bf16_kernel(const bf16_t* a, const bf16_t* b, bf16_t* o, size_t n8) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
     const uint4 x = reinterpret_cast<const uint4*>(a)[i], y = reinterpret_cast<const uint4*>(b)[i];
     const unsigned xx[4] = {x.x, x.y, x.z, x.w}, yy[4] = {y.x, y.y, y.z, y.w};
@@ -465,8 +466,8 @@ __global__ void gelu_bwd_kernel(const bf16_t* __restrict__ dact, const bf16_t* _
     unsigned r[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      r[k] = pack_bf2(bf2f((bf16_t)(xx[k] & 0xffff)) * dgelu_acc_f(bf2f((bf16_t)(yy[k] & 0xffff))),
-                      bf2f((bf16_t)(xx[k] >> 16)) * dgelu_acc_f(bf2f((bf16_t)(yy[k] >> 16))));
+      r[k] = pack_bf2(bf2f((bf16_t)(xx[k] & 0xffff)) * dgelu_erf_f(bf2f((bf16_t)(yy[k] & 0xffff))),
+                      bf2f((bf16_t)(xx[k] >> 16)) * dgelu_erf_f(bf2f((bf16_t)(yy[k] >> 16))));
     reinterpret_cast<uint4*>(dpre)[i] = make_uint4(r[0], r[1], r[2], r[3]);
   }
 }

@@ -12,7 +12,8 @@
 
 namespace {
 
-// One element's AdamW update (custom_optim/_functional.py:115-140), shared by the flat and the tiled loop: identical arithmetic, in this order.
+// One element's AdamW update (custom_optim/_functional.py:115-140), shared by the flat loop, the tiled loop and the grouped
+// kernel: identical arithmetic, in this order.
 __device__ __forceinline__ void adamw_elem(float& P, float G, float& M, float& V, float decay, float step_size, float beta1, float beta2, float eps,
                                            float inv_sqrt_bc2, float grad_scale) {
   const float gk = G * grad_scale;
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     const AdamTrMat mt = mats[k];
     const int tcn = mt.cols >> 6, local = t - mt.tile0;
     const int r0 = (local / tcn) << 6, c0 = (local % tcn) << 6;
-    const int grp = group[mt.off >> 8] & 1;
-    const float lr = grp ? lr1 : lr0, wd = grp ? wd1 : wd0;
+    const int gflag = group[mt.off >> 8] & 0x7f;                        // 2: a listed weight without a gradient -- shadow and W^T of the unchanged values
+    const float lr = gflag ? lr1 : lr0, wd = gflag ? wd1 : wd0;
     const float decay = 1.0f - lr * wd, step_size = lr * inv_bc1;
     const int c4 = threadIdx.x & 15;
 #pragma unroll
@@ -61,15 +62,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
       const int r = (threadIdx.x >> 4) + 16 * q;
       const long long i = (mt.off + (long long)(r0 + r) * mt.cols + c0 + c4 * 4) >> 2;
       float4 pp = reinterpret_cast<float4*>(p)[i];
-      float4 gg = reinterpret_cast<const float4*>(g)[i];
-      float4 mm = reinterpret_cast<float4*>(m)[i];
-      float4 vv = reinterpret_cast<float4*>(v)[i];
-      float P[4] = {pp.x, pp.y, pp.z, pp.w}, G[4] = {gg.x, gg.y, gg.z, gg.w}, M[4] = {mm.x, mm.y, mm.z, mm.w}, V[4] = {vv.x, vv.y, vv.z, vv.w};
+      float P[4] = {pp.x, pp.y, pp.z, pp.w};
+      if (gflag != 2) {
+        float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i];
+        float4 vv = reinterpret_cast<float4*>(v)[i];
+        float G[4] = {gg.x, gg.y, gg.z, gg.w}, M[4] = {mm.x, mm.y, mm.z, mm.w}, V[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) adamw_elem(P[e], G[e], M[e], V[e], decay, step_size, beta1, beta2, eps, inv_sqrt_bc2, grad_scale);
-      reinterpret_cast<float4*>(p)[i] = make_float4(P[0], P[1], P[2], P[3]);
-      reinterpret_cast<float4*>(m)[i] = make_float4(M[0], M[1], M[2], M[3]);
-      reinterpret_cast<float4*>(v)[i] = make_float4(V[0], V[1], V[2], V[3]);
+        for (int e = 0; e < 4; ++e) adamw_elem(P[e], G[e], M[e], V[e], decay, step_size, beta1, beta2, eps, inv_sqrt_bc2, grad_scale);
+        reinterpret_cast<float4*>(p)[i] = make_float4(P[0], P[1], P[2], P[3]);
+        reinterpret_cast<float4*>(m)[i] = make_float4(M[0], M[1], M[2], M[3]);
+        reinterpret_cast<float4*>(v)[i] = make_float4(V[0], V[1], V[2], V[3]);
+      }
       const uint2 sh = make_uint2(pack_bf2(P[0], P[1]), pack_bf2(P[2], P[3]));
       if (shadow) reinterpret_cast<uint2*>(shadow)[i] = sh;
       *reinterpret_cast<uint2*>(&tile[r][c4 * 4]) = sh;
@@ -127,14 +131,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
       float G[4] = {gg.x, gg.y, gg.z, gg.w}, M[4] = {mm.x, mm.y, mm.z, mm.w}, V[4] = {vv.x, vv.y, vv.z, vv.w};
       const float decay = 1.0f - lr * wd, step_size = lr * inv_bc1;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float gk = G[k] * grad_scale;
-        P[k] *= decay;
-        M[k] = M[k] * beta1 + gk * (1.0f - beta1);
-        V[k] = V[k] * beta2 + gk * gk * (1.0f - beta2);
-        const float denom = sqrtf(V[k]) * inv_sqrt_bc2 + eps;
-        P[k] -= step_size * (M[k] / denom);
-      }
+      for (int k = 0; k < 4; ++k) adamw_elem(P[k], G[k], M[k], V[k], decay, step_size, beta1, beta2, eps, inv_sqrt_bc2, grad_scale);
       reinterpret_cast<float4*>(p)[i] = make_float4(P[0], P[1], P[2], P[3]);
       reinterpret_cast<float4*>(m)[i] = make_float4(M[0], M[1], M[2], M[3]);
       reinterpret_cast<float4*>(v)[i] = make_float4(V[0], V[1], V[2], V[3]);

@@ -420,7 +420,10 @@ int dig_colsum_partials(const float* partials, int n_parts, int C, float* out, h
 #define DIG_COLSUM_MAX_SEGS 112
 typedef struct dig_colsum_seg { const float* partials; float* out; long long stride; int n_parts; int C; } dig_colsum_seg_t;
 int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_segs, hipStream_t stream);
+/* dpre = bf16(dact * gelu'(pre)), bf16 in / out, gelu'(x) = Phi(x) + x phi(x) of the erf GELU to fp32 round-off (|abs err| < 1e-6) at every finite
+ * bf16 x; n % 8 == 0, 16-byte aligned pointers. */
 int dig_gelu_bwd(const void* dact, const void* pre, void* dpre, long long n, hipStream_t stream);
+/* out = bf16(float(a) + float(b)); `out` may be `a` or `b` (the fine-tune gradient adds run in place); n % 8 == 0, 16-byte aligned pointers. */
 int dig_add_bf16(const void* a, const void* b, void* out, long long n, hipStream_t stream);
 int dig_cast_f32_to_bf16(const float* x, void* y, long long n, hipStream_t stream);
 int dig_cast_bf16_to_f32(const void* x, float* y, long long n, hipStream_t stream);

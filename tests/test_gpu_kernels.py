@@ -588,6 +588,7 @@ def test_adamw_ema_sumsq_colsum(dev):
     lr = torch.full((n,), 1e-3, device=dev); lr[n // 2:] = 2e-3
     rp -= (lr / (1 - 0.9 ** 3)) * rm / den
     assert float((p - rp).abs().max()) < 2e-6 and rel(m, rm) < 1e-6 and rel(v, rv) < 1e-6 and rel(sh, rp) < 5e-3
+    assert torch.equal(sh, p.bfloat16())                            # the shadow is defined exactly: bf16(p), round to nearest even
     pm = torch.randn(n, device=dev); pm0 = pm.clone()
     ops.ema_update(pm, p, sh, n, 0.99)
     assert float((pm - (pm0 * 0.99 + p * (1 - 0.99))).abs().max()) < 1e-6
@@ -601,10 +602,11 @@ def test_adamw_ema_sumsq_colsum(dev):
 
 def test_adamw_step_tr_equals_plain_step_plus_transposes(dev):
     """dig_adamw_step_tr: the plain launch's p / m / v / shadow bit for bit (flat granules and the 64 x 64 tiles of the listed weights),
-    W^T of every listed weight == the transposed shadow, group 2 (a parameter without a gradient) untouched, the non-finite gate a no-op."""
+    W^T of every listed weight == the transposed shadow, group 2 (a parameter without a gradient) untouched -- as a flat granule and as a
+    listed weight (0x80 | 2), whose shadow and W^T are those of the unchanged values --, the non-finite gate a no-op."""
     import struct
     from dig_amd import ops
-    mats = [(128, 192), (192, 64), (64, 64)]                      # (rows, cols) of the listed weights, with other parameters between them
+    mats = [(128, 192), (192, 64), (64, 64), (64, 128)]           # (rows, cols) of the listed weights, with other parameters between them
     layout, off = [], 0
     for k, (r, c) in enumerate(mats):
         off += 256 * (k + 1)                                      # a few 1-D parameters in front
@@ -617,6 +619,8 @@ def test_adamw_step_tr_equals_plain_step_plus_transposes(dev):
     flags = torch.zeros(n // 256, dtype=torch.uint8, device=dev)
     flags[0] = 1
     flags[-1] = 2                                                 # the last granule: no gradient, untouched
+    ng0, ng1 = layout[-1][0], layout[-1][0] + mats[-1][0] * mats[-1][1]
+    flags[ng0 // 256:ng1 // 256] = 2                              # the last listed weight: no gradient either
     hyp = (1e-3, 0.1, 2e-3, 0.0, 0.9, 0.999, 1e-8, 3)
     p1, m1, v1 = p0.clone(), m0.clone(), v0.clone()
     sh1 = torch.zeros(n, device=dev, dtype=torch.bfloat16)
@@ -635,6 +639,8 @@ def test_adamw_step_tr_equals_plain_step_plus_transposes(dev):
     tr = torch.zeros(dst, device=dev, dtype=torch.bfloat16)
     ops.adamw_step_tr(p2, g, m2, v2, sh2, fl, *hyp, table, len(layout), t0, tr, 0.5)
     assert torch.equal(p1, p2) and torch.equal(m1, m2) and torch.equal(v1, v2) and torch.equal(sh1, sh2)
+    assert torch.equal(p2[ng0:ng1], p0[ng0:ng1]) and torch.equal(m2[ng0:ng1], m0[ng0:ng1]) and torch.equal(v2[ng0:ng1], v0[ng0:ng1])
+    assert torch.equal(sh2[ng0:ng1], p0[ng0:ng1].bfloat16())
     d = 0
     for o, r, c in layout:
         assert torch.equal(tr[d:d + r * c].view(c, r), sh1[o:o + r * c].view(r, c).t())
