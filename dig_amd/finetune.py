@@ -11,12 +11,14 @@ come from a keyed counter hash instead of torch's generator, see dig_amd/dropout
 Parameters, gradients, Adam moments and the bf16 GEMM operands live in flat arenas (dig_amd/arena.py: each tensor padded to the granule) whose
 layout keeps q|k|v (and k|v) projection weights adjacent, so the fused projections are views.  The whole model is ONE autograd
 node with a hand-written backward on the hot-path kernels (encoder: the pre-training kernels; decoder: `dig_seq_attn_*_hd` at the decoder's head dim (24 / 48 / 64),
-`dig_seq_embed_*`, `dig_gemm_bf16`, `dig_layernorm_*`; with `--text_cond_vis` the cross-attention is `dig_tcv_attn_fwd / _bwd` between per-head
-fold GEMMs, see dig_amd/recognizer.py).  The CPU checker of this step lives with the tests."""
+`dig_seq_embed_*`, `dig_gemm_bf16`, `dig_layernorm_*`).  The decoder's cross-attention over the encoder memory has three forms -- the encoder's
+MFMA kernel on a few query rows, the sequence kernels, the folded text-conditional one -- and the step knows none of them: the model picked
+one when it was built (`model.cross`, dig_amd/decoder_cross.py), and the layer loops below hand it norm2's output on the way up and the
+gradient behind enc_attn.fc on the way down.  The CPU checker of this step lives with the tests."""
 import ctypes
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -43,8 +45,8 @@ def encoder_plan(M, rows):
     return EB.Plan(chain_ln=FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(M.D, M.F, rows))
 
 
-def _ref(spec):
-    return ctypes.byref(spec) if spec is not None else None
+# what a decoder layer's backward reads of its forward; cross: the saved state of the cross-attention form, opaque here
+_LayerSaved = namedtuple("_LayerSaved", "x h1 m1 r1 qkv a lse1 x1 m2 r2 cross a2 x2 h3 m3 r3 pre u")
 
 
 class RecModelTrain(RecModel):
@@ -300,7 +302,6 @@ class _TrainStep:
         M = self.m
         dev = images.device
         enc = self.encoder_forward(images)
-        D, H, N = M.D, M.H, M.n_mem                                           # N: memory tokens per sample the decoder attends over
         B = self.B
         mem, (self.mem_in, h, mmu, mrs) = M.linear_norm(enc)
         self.ln_saved = (h, mmu, mrs, mem)
@@ -322,84 +323,23 @@ class _TrainStep:
         x = ops.dropout_apply(x, self.ds_tgt, out=x)                            # decoder.py:180
         sc = dk ** -0.5
         self.dec_saved = []
-        tcv = M.text_cond_vis
-        mfma_cross = N == 256 and dk == 64 and not tcv
-        kv_ready = []
-        if tcv:
-            # --text_cond_vis: vk = LN_vis(vis_proj(mem)) depends on no decoder state either: all layers' on the second stream, one event per layer
-            main = torch.cuda.current_stream(dev)
-            sd = M._side_stream(dev) if getattr(M, "overlap_streams", True) else main
-            sd.wait_stream(main)
-            with torch.cuda.stream(sd):
-                for i in range(M.n_layers):
-                    vk, vsaved = M.tcv_memory(mem, M._w[f"decoder.layer_stack.{i}."])
-                    ev = torch.cuda.Event()
-                    ev.record(sd)
-                    for t_ in (vk,) + vsaved:
-                        t_.record_stream(main)
-                    kv_ready.append((vk, vsaved, ev))
-            mem.record_stream(sd)
-        if mfma_cross:
-            # K|V projections of the encoder memory depend on no decoder state: all layers' are issued on the second stream now and
-            # overlap the (small, latency-bound) self-attention kernels of the decoder chain; one event per layer
-            main = torch.cuda.current_stream(dev)
-            sd = M._side_stream(dev) if getattr(M, "overlap_streams", True) else main
-            sd.wait_stream(main)
-            with torch.cuda.stream(sd):
-                for i in range(M.n_layers):
-                    fused = torch.empty((B * N, 3 * hk), device=dev, dtype=BF16)
-                    ops.gemm(mem, M._w[f"decoder.layer_stack.{i}."]["kv2"], B * N, 2 * hk, d, out=fused[:, hk:], ldc=3 * hk)
-                    ev = torch.cuda.Event()
-                    ev.record(sd)
-                    fused.record_stream(main)
-                    kv_ready.append((fused, ev))
-            mem.record_stream(sd)
+        self.mem = mem
+        self.prepare_memory(dev)
         for i in range(M.n_layers):
             p = f"decoder.layer_stack.{i}."
             ds = self.ds_dec[i]
             h1, m1, r1 = ops.layernorm_fwd(x, self.p(p + "norm1.weight"), self.p(p + "norm1.bias"), 1e-5)
             qkv = ops.linear_fwd(h1, M._w[p]["qkv"])
-            a = torch.empty((B * T, hk), device=dev, dtype=BF16)
-            lse1 = torch.empty((B, nh, T), device=dev, dtype=F32)
-            L.call("dig_seq_attn_fwd_hd", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(a), hk,
-                   L.ptr(lse1), B, nh, T, T, cf(sc), 1, L.ptr(self.lens), _ref(ds["sattn"]), dk, L.stream())
+            a, lse1 = ops.seq_attn_fwd(qkv, qkv[:, hk:], qkv[:, 2 * hk:], B, nh, T, T, dk, sc, True, self.lens, ds["sattn"])
             x1 = ops.linear_fwd(a, self.w(p + "self_attn.fc.weight"), resid=x, drop=ds["sproj"])
             h2, m2, r2 = ops.layernorm_fwd(x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), 1e-5)
-            q2 = None if tcv else ops.linear_fwd(h2, self.w(p + "enc_attn.linear_q.weight"))
-            if tcv:
-                # the text-conditional cross-attention, folded (csrc/text_cond_attn.hip): film = gamma_decode(h2); the scaled queries through
-                # Wk head by head (u); the attention over cond, which only exists row by row inside the kernel; its result through Wv head by head
-                pv = M._w[p]
-                film = ops.linear_fwd(h2, pv["gd"], bias=pv["gdb"])
-                q2 = self.padded_rows(B * T, hk, dev)                             # (a weight-gradient operand read in 128-column tiles)
-                ops.linear_fwd(h2, pv["q2"], alpha=sc, alpha_cols=hk, out=q2)
-                u2 = M.tcv_fold_queries(q2, pv["k2"])
-                vk, vsaved, ev = kv_ready[i]
-                torch.cuda.current_stream(dev).wait_event(ev)
-                c2, lse2 = ops.tcv_attn_fwd(film, u2, vk, mem, pv["cnw"], pv["cnb"], B, T, N, nh, 1, ds["cattn"])
-                a2 = M.tcv_fold_values(c2, pv["v2"])
-                kvm = dict(film=film, u=u2, vk=vk, vsaved=vsaved, c=c2)
-            elif mfma_cross:
-                # cross-attention on the MFMA kernel of the encoder (256 keys, head dim 64): the T queries of a sample sit in rows
-                # [0, T) of a fused q|k|v buffer of 256 rows per sample, and the kernels are told to compute the first
-                # ceil(T / 32) query blocks only (rows T..31 are zero queries with a zero output gradient: no contribution).
-                fused, ev = kv_ready[i]
-                torch.cuda.current_stream(dev).wait_event(ev)
-                a2, ctx2, lse2 = EB.cross_attn_fwd(fused, q2, B, T, nh, hk, sc, drop=ds["cattn"])
-                kvm, lse2 = fused, (lse2, ctx2)
-            else:
-                # head dim 24 / 48 (the `corres_*` decoders), --use_1d_attdec (32 keys): the sequence kernels over all N keys
-                kvm = ops.linear_fwd(mem, M._w[p]["kv2"])
-                a2 = torch.empty((B * T, hk), device=dev, dtype=BF16)
-                lse2 = torch.empty((B, nh, T), device=dev, dtype=F32)
-                L.call("dig_seq_attn_fwd_hd", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(a2), hk, L.ptr(lse2), B, nh,
-                       T, N, cf(sc), 0, None, _ref(ds["cattn"]), dk, L.stream())
+            a2, cross = M.cross.forward(self, p, h2, ds["cattn"])
             x2 = ops.linear_fwd(a2, self.w(p + "enc_attn.fc.weight"), resid=x1, drop=ds["cproj"])
             h3, m3, r3 = ops.layernorm_fwd(x2, self.p(p + "norm3.weight"), self.p(p + "norm3.bias"), 1e-5)
             pre = torch.empty((B * T, M.d_inner), device=dev, dtype=BF16)
             u = ops.linear_fwd(h3, self.w(p + "mlp.w_1.weight"), bias=self.p(p + "mlp.w_1.bias"), act=1, pre=pre, drop=ds["act"])
             x3 = ops.linear_fwd(u, self.w(p + "mlp.w_2.weight"), bias=self.p(p + "mlp.w_2.bias"), resid=x2, drop=ds["out"])
-            self.dec_saved.append((x, h1, m1, r1, qkv, a, lse1, x1, h2, m2, r2, q2, kvm, a2, lse2, x2, h3, m3, r3, pre, u))
+            self.dec_saved.append(_LayerSaved(x, h1, m1, r1, qkv, a, lse1, x1, m2, r2, cross, a2, x2, h3, m3, r3, pre, u))
             x = x3
         o, fm, fr = ops.layernorm_fwd(x, self.p("decoder.layer_norm.weight"), self.p("decoder.layer_norm.bias"), 1e-6)
         self.fin_saved = (x, fm, fr, o)
@@ -423,46 +363,32 @@ class _TrainStep:
         else:
             ops.add_bf16(self._dmem, dm, self._dmem)
 
-    def tcv_cross_backward(self, p, dz, drop, h2, q2, kvm, lse2, mem):
-        """The backward of the folded text-conditional cross-attention of layer `p` (see forward): dz = the gradient behind enc_attn.fc's
-        proj_drop.  The Wv fold gives dc and linear_v's gradient, dig_tcv_attn_bwd gives du / dfilm / dvk / the residual term of dmem and
-        vis_cond_norm's gradients, the Wk fold gives the query gradient and linear_k's; gamma_decode, vis_proj and vis_norm are a Linear and a
-        LayerNorm.  Returns the gradient w.r.t. norm2's output; the memory gradient is summed into self._dmem on the second stream."""
-        M, side = self.m, self.side
-        B, T, d, nh, dk, N = self.B, M.max_len, M.d, M.nh, M.dk, M.n_mem
-        hk, rows, sc = nh * dk, self.B * M.max_len, M.dk ** -0.5
-        pv, a = M._w[p], p + "enc_attn."
-        film, u2, vk, (hv, vmu, vrs), c2 = kvm["film"], kvm["u"], kvm["vk"], kvm["vsaved"], kvm["c"]
-        head = lambda t_, h, w_: t_[:, h * w_:(h + 1) * w_]
-        da2 = self.padded_rows(rows, hk, dz.device)
-        ops.linear_dgrad(dz, self.w(a + "fc.weight"), out=da2)
-        dc = torch.empty_like(c2)
-        for h in range(nh):
-            ops.gemm(head(da2, h, dk), pv["v2"][h * dk:(h + 1) * dk], rows, d, dk, tb=True, out=head(dc, h, d))
-        gv, gk = self.g(a + "linear_v.weight"), self.g(a + "linear_k.weight")
-        side(lambda: [ops.wgrad(head(da2, h, dk), head(c2, h, d), gv[h * dk:(h + 1) * dk], dk, d, rows) for h in range(nh)], da2, c2)
-        du, dfilm, dvk, dmem = ops.tcv_attn_bwd(film, u2, vk, mem, pv["cnw"], pv["cnb"], c2, lse2, dc, self.g(a + "vis_cond_norm.weight"),
-                                                self.g(a + "vis_cond_norm.bias"), B, T, N, nh, drop)
-        dq2 = torch.empty((rows, hk), device=dz.device, dtype=BF16)
-        for h in range(nh):                                                       # q2 carries the scale: so does its gradient
-            ops.gemm(head(du, h, d), pv["k2"][h * dk:(h + 1) * dk], rows, dk, d, out=head(dq2, h, dk), alpha=sc, alpha_cols=dk)
-        side(lambda: [ops.wgrad(head(q2, h, dk), head(du, h, d), gk[h * dk:(h + 1) * dk], dk, d, rows) for h in range(nh)], q2, du)
-        side(lambda: ops.linear_wgrad(dq2, h2, self.g(a + "linear_q.weight")), dq2, h2)
-        side(lambda: ops.linear_wgrad(dfilm, h2, self.g(a + "gamma_decode.weight")), dfilm, h2)
-        side(lambda: ops.colsum(dfilm, self.g(a + "gamma_decode.bias")), dfilm)
-        dh2 = ops.linear_dgrad(dq2, pv["q2"])
-        dh2b = ops.linear_dgrad(dfilm, pv["gd"])
-        ops.add_bf16(dh2, dh2b, dh2)
+    def prepare_memory(self, dev):
+        """What the cross-attention form computes from the encoder memory alone depends on no decoder state: every layer's is issued on the
+        second stream now and overlaps the (small, latency-bound) self-attention kernels of the decoder chain; one event per layer."""
+        M, mem = self.m, self.mem
+        self._prepared = {}
+        if not M.cross.prepares_memory:
+            return
+        main = torch.cuda.current_stream(dev)
+        sd = M._side_stream(dev) if getattr(M, "overlap_streams", True) else main
+        sd.wait_stream(main)
+        with torch.cuda.stream(sd):
+            for i in range(M.n_layers):
+                p = f"decoder.layer_stack.{i}."
+                kept = M.cross.prepare(mem, M._w[p])
+                ev = torch.cuda.Event()
+                ev.record(sd)
+                for t_ in kept:
+                    t_.record_stream(main)
+                self._prepared[p] = (kept, ev)
+        mem.record_stream(sd)
 
-        def vis_path():
-            dhv = ops.layernorm_bwd(dvk, hv, pv["vnw"], pv["vnb"], vmu, vrs, None, self.g(a + "vis_norm.weight"), self.g(a + "vis_norm.bias"))
-            ops.linear_wgrad(dhv, mem, self.g(a + "vis_proj.weight"))
-            ops.colsum(dhv, self.g(a + "vis_proj.bias"))
-            dm = ops.linear_dgrad(dhv, pv["vp"])
-            ops.add_bf16(dm, dmem, dm)
-            self.add_dmem(dm)
-        side(vis_path, dvk, dmem, hv, vmu, vrs, mem)
-        return dh2
+    def prepared(self, p):
+        """The tensors `prepare_memory` made for layer p, the current stream made to wait for them."""
+        kept, ev = self._prepared[p]
+        torch.cuda.current_stream(self.mem.device).wait_event(ev)
+        return kept
 
     def encoder_backward(self, denc):
         """denc: bf16 [B*N, D] gradient w.r.t. the tokens `encoder_forward` returned (call `begin_backward` first)."""
@@ -509,7 +435,7 @@ class _TrainStep:
         dev = dlogits_btc.device
         main, sd = self.begin_backward(dev)
         side = self.side
-        B, T, d, nh, dk, C, N, D, H = self.B, M.max_len, M.d, M.nh, M.dk, M.nb_classes, M.n_mem, M.D, M.H
+        B, T, d, nh, dk, C, D = self.B, M.max_len, M.d, M.nh, M.dk, M.nb_classes, M.D
         hk = nh * dk
         rows = B * T
         dl = torch.zeros((rows, CLS_PAD), device=dev, dtype=BF16)
@@ -520,62 +446,36 @@ class _TrainStep:
                                self.g("decoder.layer_norm.weight"), self.g("decoder.layer_norm.bias"))
         self._dmem = None
         sc = dk ** -0.5
-        mem = self.ln_saved[3]
         for i in reversed(range(M.n_layers)):
             p = f"decoder.layer_stack.{i}."
-            (x0, h1, m1, r1, qkv, a, lse1, x1, h2, m2, r2, q2, kvm, a2, lse2, x2, h3, m3, r3, pre, u) = self.dec_saved[i]
-            self.dec_saved[i] = None
+            s, self.dec_saved[i] = self.dec_saved[i], None
             ds = self.ds_dec[i]
             # feed-forward (every dropped branch: its gradient is the residual gradient under the same mask)
             dz = ops.dropout_apply(dx, ds["out"])
-            side(lambda: ops.linear_wgrad(dz, u, self.g(p + "mlp.w_2.weight")), dz, u)
+            side(lambda: ops.linear_wgrad(dz, s.u, self.g(p + "mlp.w_2.weight")), dz, s.u)
             side(lambda: ops.colsum(dz, self.g(p + "mlp.w_2.bias")), dz)
-            du, bparts = ops.linear_dgrad(dz, self.w(p + "mlp.w_2.weight"), gelu_pre=pre, colsum=True, drop=ds["act"])
+            du, bparts = ops.linear_dgrad(dz, self.w(p + "mlp.w_2.weight"), gelu_pre=s.pre, colsum=True, drop=ds["act"])
             side(lambda: ops.colsum_partials(bparts, self.g(p + "mlp.w_1.bias")), bparts)
-            side(lambda: ops.linear_wgrad(du, h3, self.g(p + "mlp.w_1.weight")), du, h3)
+            side(lambda: ops.linear_wgrad(du, s.h3, self.g(p + "mlp.w_1.weight")), du, s.h3)
             dh3 = ops.linear_dgrad(du, self.w(p + "mlp.w_1.weight"))
-            dx2 = ops.layernorm_bwd(dh3, x2, self.p(p + "norm3.weight"), self.p(p + "norm3.bias"), m3, r3, dx, self.g(p + "norm3.weight"),
+            dx2 = ops.layernorm_bwd(dh3, s.x2, self.p(p + "norm3.weight"), self.p(p + "norm3.bias"), s.m3, s.r3, dx, self.g(p + "norm3.weight"),
                                     self.g(p + "norm3.bias"))
             # cross-attention over the encoder memory
             dz = ops.dropout_apply(dx2, ds["cproj"])
-            side(lambda: ops.linear_wgrad(dz, a2, self.g(p + "enc_attn.fc.weight")), dz, a2)
-            if isinstance(kvm, dict):                                             # --text_cond_vis (see forward)
-                dh2 = self.tcv_cross_backward(p, dz, ds["cattn"], h2, q2, kvm, lse2, mem)
-            else:
-                da2 = ops.linear_dgrad(dz, self.w(p + "enc_attn.fc.weight"))
-                if isinstance(lse2, tuple):                                           # MFMA path (see forward)
-                    lse2, ctx2 = lse2                                                 # padded rows: finite outputs, zero dO -> delta = 0
-                    dq2, dkvm = EB.cross_attn_bwd(kvm, ctx2, lse2, da2, B, T, nh, hk, sc, drop=ds["cattn"])   # kvm = the fused q|k|v buffer
-                else:
-                    dq2 = torch.empty_like(q2)
-                    dkvm = torch.empty_like(kvm)
-                    L.call("dig_seq_attn_bwd_hd", L.ptr(q2), hk, L.ptr(kvm), 2 * hk, L.ptr(kvm[:, hk:]), 2 * hk, L.ptr(da2), hk, L.ptr(lse2),
-                           L.ptr(dq2), hk, L.ptr(dkvm), 2 * hk, L.ptr(dkvm[:, hk:]), 2 * hk, B, nh, T, N, cf(sc), 0, None, _ref(ds["cattn"]),
-                           dk, L.stream())
-                side(lambda: ops.linear_wgrad(dq2, h2, self.g(p + "enc_attn.linear_q.weight")), dq2, h2)
-                dh2 = ops.linear_dgrad(dq2, self.w(p + "enc_attn.linear_q.weight"))
-                side(lambda: ops.wgrad(dkvm, mem, self.g_of(M._w[p]["kv2"]), 2 * hk, hk, B * N), dkvm, mem)
-                # the gradient w.r.t. the encoder memory is needed only after the decoder loop: its GEMMs run on the second stream too
-                def mem_grad(dkvm=dkvm, wkv=M._w[p]["kv2"]):
-                    dm = ops.gemm(dkvm, wkv, B * N, hk, 2 * hk, tb=True)
-                    if self._dmem is None:
-                        self._dmem = dm
-                    else:
-                        ops.add_bf16(self._dmem, dm, self._dmem)
-                side(mem_grad, dkvm)
-            dx1 = ops.layernorm_bwd(dh2, x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), m2, r2, dx2, self.g(p + "norm2.weight"),
+            side(lambda: ops.linear_wgrad(dz, s.a2, self.g(p + "enc_attn.fc.weight")), dz, s.a2)
+            dh2 = M.cross.backward(self, p, dz, s.cross)
+            dx1 = ops.layernorm_bwd(dh2, s.x1, self.p(p + "norm2.weight"), self.p(p + "norm2.bias"), s.m2, s.r2, dx2, self.g(p + "norm2.weight"),
                                     self.g(p + "norm2.bias"))
             # masked self-attention
             dz = ops.dropout_apply(dx1, ds["sproj"])
-            side(lambda: ops.linear_wgrad(dz, a, self.g(p + "self_attn.fc.weight")), dz, a)
+            side(lambda: ops.linear_wgrad(dz, s.a, self.g(p + "self_attn.fc.weight")), dz, s.a)
             da = ops.linear_dgrad(dz, self.w(p + "self_attn.fc.weight"))
-            dqkv = torch.empty_like(qkv)
-            L.call("dig_seq_attn_bwd_hd", L.ptr(qkv), 3 * hk, L.ptr(qkv[:, hk:]), 3 * hk, L.ptr(qkv[:, 2 * hk:]), 3 * hk, L.ptr(da), hk,
-                   L.ptr(lse1), L.ptr(dqkv), 3 * hk, L.ptr(dqkv[:, hk:]), 3 * hk, L.ptr(dqkv[:, 2 * hk:]), 3 * hk, B, nh, T, T, cf(sc), 1,
-                   L.ptr(self.lens), _ref(ds["sattn"]), dk, L.stream())
-            side(lambda: ops.linear_wgrad(dqkv, h1, self.g_of(M._w[p]["qkv"])), dqkv, h1)
+            qkv, dqkv = s.qkv, torch.empty_like(s.qkv)
+            ops.seq_attn_bwd(qkv, qkv[:, hk:], qkv[:, 2 * hk:], da, s.lse1, dqkv, dqkv[:, hk:], dqkv[:, 2 * hk:], B, nh, T, T, dk, sc, True, self.lens,
+                             ds["sattn"])
+            side(lambda: ops.linear_wgrad(dqkv, s.h1, self.g_of(M._w[p]["qkv"])), dqkv, s.h1)
             dh1 = ops.linear_dgrad(dqkv, M._w[p]["qkv"])
-            dx = ops.layernorm_bwd(dh1, x0, self.p(p + "norm1.weight"), self.p(p + "norm1.bias"), m1, r1, dx1, self.g(p + "norm1.weight"),
+            dx = ops.layernorm_bwd(dh1, s.x, self.p(p + "norm1.weight"), self.p(p + "norm1.bias"), s.m1, s.r1, dx1, self.g(p + "norm1.weight"),
                                    self.g(p + "norm1.bias"))
         dx = ops.dropout_apply(dx, self.ds_tgt, out=dx)
         L.call("dig_seq_embed_bwd_lens", L.ptr(self.query), L.ptr(dx), L.ptr(self.g("decoder.trg_word_emb.weight")), rows, d, C + 1, T,

@@ -750,6 +750,23 @@ def attn_fwd(qkv, n_img, heads, D, drop=None, q_rows=256):
     return ctx, lse
 
 
+def seq_attn_fwd(q, k, v, B, heads, Lq, Lk, dk, scale, causal=False, lens=None, drop=None):
+    """The sequence attention kernels (csrc/seq_attn.hip) at head dim dk: q [B*Lq, heads*dk], k / v [B*Lk, heads*dk], bf16 views whose row
+    strides are their own (columns of a fused projection).  Returns (out [B*Lq, heads*dk] bf16, lse [B, heads, Lq] fp32)."""
+    out = torch.empty((B * Lq, heads * dk), device=q.device, dtype=BF16)
+    lse = torch.empty((B, heads, Lq), device=q.device, dtype=F32)
+    L.call("dig_seq_attn_fwd_hd", L.ptr(q), q.stride(0), L.ptr(k), k.stride(0), L.ptr(v), v.stride(0), L.ptr(out), heads * dk, L.ptr(lse), B, heads,
+           Lq, Lk, cf(scale), int(causal), L.ptr(lens), ctypes.byref(drop) if drop is not None else None, dk, L.stream())
+    return out, lse
+
+
+def seq_attn_bwd(q, k, v, dout, lse, dq, dk_, dv, B, heads, Lq, Lk, dk, scale, causal=False, lens=None, drop=None):
+    """Gradient of seq_attn_fwd into the views dq / dk_ / dv (laid out like q / k / v)."""
+    L.call("dig_seq_attn_bwd_hd", L.ptr(q), q.stride(0), L.ptr(k), k.stride(0), L.ptr(v), v.stride(0), L.ptr(dout), dout.stride(0), L.ptr(lse),
+           L.ptr(dq), dq.stride(0), L.ptr(dk_), dk_.stride(0), L.ptr(dv), dv.stride(0), B, heads, Lq, Lk, cf(scale), int(causal), L.ptr(lens),
+           ctypes.byref(drop) if drop is not None else None, dk, L.stream())
+
+
 def tcv_attn_fwd(film, u, vk, mem, lnc_g, lnc_b, S, Lq, N, heads, slots_per_mem=1, drop=None, wmean=None, eps=1e-5):
     """The folded text-conditional cross-attention (csrc/text_cond_attn.hip): film [S*Lq, 2d], u [S*Lq, heads*d], vk / mem [S/slots*N, d]
     -> c [S*Lq, heads*d] bf16, lse [S*Lq, heads] fp32; wmean ([S*Lq, N] fp32, optional) receives the head-mean weights before dropout."""

@@ -8,9 +8,8 @@ models/decoder.py:224-252; encoder factory `simmim_vit_small_patch4_32x128`, mod
 
 What differs from the reference: the decoder keeps a K/V cache (one token per step instead of re-running all 26 positions 25
 times -- same result, position t only depends on tokens <= t) and the cross-attention keys/values of the encoder memory are
-projected once per layer.  With `--text_cond_vis` (TextConditionalMultiHeadAttention, models/transformer_layer.py:284-383) every query
-modulates the memory before linear_k / linear_v; neither has a bias, so both fold across the attention and the per-query memory is never
-built (csrc/text_cond_attn.hip): what is cached per layer is LN_vis(vis_proj(memory)).  The encoder front and the memory projection are written once here for evaluation and for the fine-tune training
+projected once per layer -- or whatever else the decoder's cross-attention form caches of it: the forms, their extra parameters and their parts
+of training and evaluation live in dig_amd/decoder_cross.py, and the constructor picks one.  The encoder front and the memory projection are written once here for evaluation and for the fine-tune training
 step (dig_amd/finetune.py), which passes its own plan and dropout keys; the sequence losses at the end carry their gradient.  There is no
 CPU fallback."""
 import ctypes
@@ -23,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import arena
+from . import decoder_cross
 from . import encoder_blocks as EB
 from . import ops
 
@@ -74,11 +74,10 @@ class RecModel(torch.nn.Module):
         # token grid instead of all gh*gw tokens
         self.use_1d_attdec = bool(use_1d_attdec)
         self.n_mem = self.gw if self.use_1d_attdec else self.N
-        # --text_cond_vis (run_class_finetuning.py, models/decoder.py:13-73): the decoder's cross-attention is the text-conditional one
+        # --text_cond_vis (run_class_finetuning.py, models/decoder.py:13-73): the decoder's cross-attention is the text-conditional one.
+        # Which form of the cross-attention runs (dig_amd/decoder_cross.py) is decided here and nowhere else
         self.text_cond_vis = bool(text_cond_vis)
-        if self.text_cond_vis and (d_k != 64 or n_head * d_k != d_model or d_model not in (128, 384, 512)):
-            raise NotImplementedError(f"text-conditional attention is built for d_model = 64 * n_head in {{128, 384, 512}} (the fold kernels are 64-wide "
-                                      f"per head), not for head dimension {d_k} with d_model {d_model}")
+        self.cross = decoder_cross.choose(self.text_cond_vis, self.n_mem, d_model, n_head, d_k)
         self.n_layers, self.d, self.nh, self.dk, self.d_inner = n_layers, d_model, n_head, d_k, d_inner
         self.nb_classes, self.max_len, self.n_position = nb_classes, max_len, n_position
         self.start_idx = nb_classes                                         # decoder.py:149
@@ -106,12 +105,7 @@ class RecModel(torch.nn.Module):
                 for w in ("linear_q", "linear_k", "linear_v"):
                     o[p + a + "." + w + ".weight"] = (hk, hk)
                 o[p + a + ".fc.weight"] = (d, hk)
-            if self.text_cond_vis:                      # TextConditionalMultiHeadAttention.__init__ (transformer_layer.py:320-323), in its order
-                a = p + "enc_attn."
-                o[a + "gamma_decode.weight"] = (2 * hk, hk); o[a + "gamma_decode.bias"] = (2 * hk,)
-                o[a + "vis_proj.weight"] = (hk, hk); o[a + "vis_proj.bias"] = (hk,)
-                o[a + "vis_norm.weight"] = (hk,); o[a + "vis_norm.bias"] = (hk,)
-                o[a + "vis_cond_norm.weight"] = (hk,); o[a + "vis_cond_norm.bias"] = (hk,)
+            o.update(self.cross.extra_shapes(p + "enc_attn."))
             o[p + "mlp.w_1.weight"] = (self.d_inner, d); o[p + "mlp.w_1.bias"] = (self.d_inner,)
             o[p + "mlp.w_2.weight"] = (d, self.d_inner); o[p + "mlp.w_2.bias"] = (d,)
         o["decoder.layer_norm.weight"] = (d,); o["decoder.layer_norm.bias"] = (d,)
@@ -205,11 +199,7 @@ class RecModel(torch.nn.Module):
                             fc=s(l + "self_attn.fc.weight"), q2=s(l + "enc_attn.linear_q.weight"),
                             kv2=fused(S, l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
                             w1=s(l + "mlp.w_1.weight"), b1=p(l + "mlp.w_1.bias"), w2=s(l + "mlp.w_2.weight"), b2=p(l + "mlp.w_2.bias"))
-                if self.text_cond_vis:
-                    a = l + "enc_attn."
-                    w[l].update(k2=s(a + "linear_k.weight"), v2=s(a + "linear_v.weight"), gd=s(a + "gamma_decode.weight"), gdb=p(a + "gamma_decode.bias"),
-                                vp=s(a + "vis_proj.weight"), vpb=p(a + "vis_proj.bias"), vnw=p(a + "vis_norm.weight"), vnb=p(a + "vis_norm.bias"),
-                                cnw=p(a + "vis_cond_norm.weight"), cnb=p(a + "vis_cond_norm.bias"))
+                w[l].update(self.cross.views(l + "enc_attn.", p, s))
             w["fnw"], w["fnb"] = p("decoder.layer_norm.weight"), p("decoder.layer_norm.bias")
             w["Cp"] = (self.nb_classes + 7) // 8 * 8
             w["cls_w"], w["cls_b"] = torch.zeros((w["Cp"], self.d), device=dev, dtype=BF16), torch.zeros(w["Cp"], device=dev, dtype=F32)
@@ -284,29 +274,6 @@ class RecModel(torch.nn.Module):
     def memory(self, enc):
         return self.linear_norm(enc)[0]
 
-    # ------------------------------------------------------------------ text-conditional cross-attention, folded (csrc/text_cond_attn.hip)
-    def tcv_memory(self, mem, p):
-        """vk = LN_vis(vis_proj(mem)) of one layer (p: its views) and what the backward reads: (the Linear's output, mean, rstd)."""
-        h = ops.linear_fwd(mem, p["vp"], bias=p["vpb"])
-        vk, mu, rs = ops.layernorm_fwd(h, p["vnw"], p["vnb"], 1e-5)
-        return vk, (h, mu, rs)
-
-    def tcv_fold_queries(self, q2s, wk):
-        """u[r, h, :] = Wk_h^T q2s[r, h] per head ([rows, 64] x [64, d] on strided views; q2s carries the scale): bf16 [rows, heads * d]."""
-        rows, d, dk = q2s.shape[0], self.d, self.dk
-        u = torch.empty((rows, self.nh * d), device=q2s.device, dtype=BF16)
-        for h in range(self.nh):
-            ops.gemm(q2s[:, h * dk:(h + 1) * dk], wk[h * dk:(h + 1) * dk], rows, d, dk, tb=True, out=u[:, h * d:(h + 1) * d])
-        return u
-
-    def tcv_fold_values(self, c, wv, out=None):
-        """a[r, h] = Wv_h c[r, h] per head ([rows, d] x [64, d]^T): bf16 [rows, heads * 64]."""
-        rows, d, dk = c.shape[0], self.d, self.dk
-        a = torch.empty((rows, self.nh * dk), device=c.device, dtype=BF16) if out is None else out
-        for h in range(self.nh):
-            ops.gemm(c[:, h * d:(h + 1) * d], wv[h * dk:(h + 1) * dk], rows, dk, d, out=a[:, h * dk:(h + 1) * dk])
-        return a
-
     def _decode_state(self, mem, n_mem, slots_per_mem=1):
         """Buffers of a K/V-cached decode over S = B * slots_per_mem sequences (greedy: 1 slot per sample; beam search: beam_width
         slots that share their sample's projected memory)."""
@@ -315,22 +282,16 @@ class RecModel(torch.nn.Module):
         dev = mem.device
         S = (mem.shape[0] // n_mem) * slots_per_mem
         st = types.SimpleNamespace(S=S, n_mem=n_mem, spm=slots_per_mem)
-        if self.text_cond_vis:
-            st.mem = mem
-            st.vk = [self.tcv_memory(mem, w[f"decoder.layer_stack.{i}."])[0] for i in range(self.n_layers)]         # [B*n_mem, d]
-            st.maps = torch.empty((S, n_mem), device=dev, dtype=F32)
-        else:
-            st.kv_mem = [ops.linear_fwd(mem, w[f"decoder.layer_stack.{i}."]["kv2"]) for i in range(self.n_layers)]  # [B*n_mem, 2hk]
+        self.cross.decode_state(st, mem, [w[f"decoder.layer_stack.{i}."] for i in range(self.n_layers)])    # the memory as its form caches it
         st.cache = [torch.zeros((S, T, 3 * hk), device=dev, dtype=BF16) for _ in range(self.n_layers)]
         st.x = torch.empty((S, d), device=dev, dtype=BF16)
         st.a = torch.empty((S, hk), device=dev, dtype=BF16)
-        st.wts = torch.empty((S, nh, n_mem), device=dev, dtype=F32)
         st.logits = torch.empty((S, w["Cp"]), device=dev, dtype=F32)
         return st
 
     def _decode_step(self, st, t, tok):
         """Feed token `tok` [S] at position t through the decoder stack; leaves the classifier logits in st.logits [S, Cp] and the
-        last layer's cross-attention weights in st.wts."""
+        last layer's cross-attention weights where self.cross.attn_map finds them."""
         w, d, nh, dk, T, C = self._w, self.d, self.nh, self.dk, self.max_len, self.nb_classes
         hk = nh * dk
         S = st.S
@@ -340,22 +301,13 @@ class RecModel(torch.nn.Module):
         L.call("dig_decode_embed", L.ptr(tok), L.ptr(w["emb"]), L.ptr(w["pos"][t]), L.ptr(x), S, d, C + 1, s_)
         for i in range(self.n_layers):
             p = w[f"decoder.layer_stack.{i}."]
-            last = i == self.n_layers - 1
             h, _, _ = ops.layernorm_fwd(x, p["n1w"], p["n1b"], 1e-5)
             row = st.cache[i][:, t]                                                # [S, 3hk] view, row stride T*3hk
             ops.gemm(h, p["qkv"], S, 3 * hk, d, out=row, ldc=T * 3 * hk)
             L.call("dig_decode_self_attn", L.ptr(st.cache[i]), L.ptr(st.a), S, T, nh, dk, t, cf(scale), s_)
             x = ops.linear_fwd(st.a, p["fc"], resid=x)
             h, _, _ = ops.layernorm_fwd(x, p["n2w"], p["n2b"], 1e-5)
-            if self.text_cond_vis:
-                film = ops.linear_fwd(h, p["gd"], bias=p["gdb"])
-                u2 = self.tcv_fold_queries(ops.linear_fwd(h, p["q2"], alpha=scale, alpha_cols=hk), p["k2"])
-                c2, _ = ops.tcv_attn_fwd(film, u2, st.vk[i], st.mem, p["cnw"], p["cnb"], S, 1, st.n_mem, nh, st.spm, None, st.maps if last else None)
-                self.tcv_fold_values(c2, p["v2"], out=st.a)
-            else:
-                q2 = ops.linear_fwd(h, p["q2"])
-                L.call("dig_decode_cross_attn", L.ptr(q2), L.ptr(st.kv_mem[i]), L.ptr(st.a), L.ptr(st.wts) if last else None, S, st.n_mem, nh, dk,
-                       cf(scale), st.spm, s_)
+            self.cross.decode_step(st, i, p, h, i == self.n_layers - 1)             # -> st.a
             x = ops.linear_fwd(st.a, p["fc2"], resid=x)
             h, _, _ = ops.layernorm_fwd(x, p["n3w"], p["n3b"], 1e-5)
             u = ops.linear_fwd(h, p["w1"], bias=p["b1"], act=1)
@@ -380,7 +332,7 @@ class RecModel(torch.nn.Module):
             self._decode_step(st, t, tok)
             L.call("dig_softmax_argmax", L.ptr(st.logits), w["Cp"], L.ptr(step_probs), L.ptr(tok), B, C, L.stream())
             probs[:, t] = step_probs
-            maps[:, t] = st.maps if self.text_cond_vis else st.wts.mean(1)
+            maps[:, t] = self.cross.attn_map(st)
             toks[:, t] = tok
             if force_tokens is not None:
                 tok = force_tokens[:, t].contiguous()

@@ -427,6 +427,34 @@ def test_recognizer_state_dict_round_trip_on_cpu():
         RecModel(**kw).eval()(torch.zeros(1, 3, 32, 128))
 
 
+def test_decoder_cross_attention_form_is_chosen_once_from_the_shape_facts():
+    """RecModel picks its decoder cross-attention form (dig_amd/decoder_cross.py) from text_cond_vis, the number of memory tokens and the head
+    dim; the text-conditional form adds its eight parameters per layer directly behind that layer's enc_attn.fc.weight and moves no other name."""
+    import types
+    from dig_amd import decoder_cross as DC
+    from dig_amd.recognizer import RecModel
+
+    def model(decoder_name, **flags):
+        return RecModel(types.SimpleNamespace(model="simmim_vit_tiny_patch4_32x128", decoder_name=decoder_name, nb_classes=97, max_len=25, **flags))
+    for decoder_name, flags, n_mem, d_k, form in (("tf_decoder", {}, 256, 64, DC.MfmaFewQuery),
+                                                  ("tf_decoder", dict(use_1d_attdec=True), 32, 64, DC.SequenceKernel),
+                                                  ("corres_tiny_tf_decoder", {}, 256, 24, DC.SequenceKernel),
+                                                  ("corres_small_tf_decoder", {}, 256, 48, DC.SequenceKernel),
+                                                  ("tf_decoder", dict(text_cond_vis=True), 256, 64, DC.TextConditional),
+                                                  ("tf_decoder", dict(text_cond_vis=True, use_1d_attdec=True), 32, 64, DC.TextConditional)):
+        m = model(decoder_name, **flags)
+        assert (m.n_mem, m.dk) == (n_mem, d_k) and type(m.cross) is form, (decoder_name, flags, type(m.cross))
+    plain, tcv = list(model("tf_decoder").param_shapes()), list(model("tf_decoder", text_cond_vis=True).param_shapes())
+    extra = ("gamma_decode.weight", "gamma_decode.bias", "vis_proj.weight", "vis_proj.bias", "vis_norm.weight", "vis_norm.bias",
+             "vis_cond_norm.weight", "vis_cond_norm.bias")
+    want = []
+    for n in plain:
+        want.append(n)
+        if n.endswith("enc_attn.fc.weight"):
+            want += [n[:-len("fc.weight")] + e for e in extra]
+    assert tcv == want and len(tcv) == len(plain) + 8 * 6
+
+
 @pytest.mark.parametrize("D", [192, 64])
 def test_place_bundles_q_and_v_bias(D):
     """arena.place at the smallest shapes where the q_bias | zeros | v_bias bundle can go wrong: D = 192 (576 elements padded to 768, v_bias at

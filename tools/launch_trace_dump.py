@@ -218,7 +218,8 @@ def _batch(B, T, lens):
 
 def _tf_model(dev, cls=None, **kw):
     from dig_amd.finetune import RecModelTrain
-    m = (cls or RecModelTrain)(embed_dim=128, depth=2, num_heads=2, n_layers=2, d_model=128, n_head=2, d_k=64, d_inner=64, nb_classes=97, max_len=8, **kw)
+    kw = {**dict(embed_dim=128, depth=2, num_heads=2, n_layers=2, d_model=128, n_head=2, d_k=64, d_inner=64, nb_classes=97, max_len=8), **kw}
+    m = (cls or RecModelTrain)(**kw)
     m._loaded = True
     m._bind(dev)
     return m
@@ -279,9 +280,9 @@ def finetune(dev, make, lens_on_host=None, smoothing=None, steps=1, optimizer=Fa
     return run
 
 
-def decode(dev, beam):
+def decode(dev, beam, **kw):
     def run():
-        m = _tf_model(dev).eval()
+        m = _tf_model(dev, **kw).eval()
         m._prepare(dev)
         images = _batch(3, m.max_len, [8, 3, 5])[0]
         with torch.no_grad():
@@ -337,6 +338,9 @@ def losses(dev):
     return run
 
 
+HD24, HD48 = dict(d_model=192, n_head=8, d_k=24), dict(d_model=192, n_head=4, d_k=48)      # (the GEMM refuses width 128 with d_k = 24)
+
+
 def main():
     with backend() as dev:
         case("pretrain_single", pretrain())
@@ -360,8 +364,16 @@ def main():
         case("finetune_gru_drop", finetune(dev, lambda d: _gru_model(d, drop_rate=0.1, attn_drop_rate=0.1, drop_path_rate=0.1, drop_seed=3), lens_on_host=True))
         case("finetune_tf_smoothing", finetune(dev, _tf_model, smoothing=0.1))
         case("finetune_adamw_two_steps_reload", finetune(dev, _tf_model, steps=2, optimizer=True))
+        case("finetune_tf_tcv", finetune(dev, lambda d: _tf_model(d, text_cond_vis=True)))
+        case("finetune_tf_tcv_nodrop", finetune(dev, lambda d: _tf_model(d, text_cond_vis=True, decoder_dropout=0.0)))
+        case("finetune_tf_tcv_1d", finetune(dev, lambda d: _tf_model(d, text_cond_vis=True, use_1d_attdec=True)))
+        case("finetune_tf_hd24", finetune(dev, lambda d: _tf_model(d, **HD24)))
+        case("finetune_tf_hd48", finetune(dev, lambda d: _tf_model(d, **HD48)))
         case("eval_greedy", decode(dev, 0))
         case("eval_beam3", decode(dev, 3))
+        case("eval_greedy_tcv", decode(dev, 0, text_cond_vis=True))
+        case("eval_beam3_tcv", decode(dev, 3, text_cond_vis=True))
+        case("eval_greedy_hd24", decode(dev, 0, **HD24))
         case("gru_sample", sample(dev))
         case("losses", losses(dev))
 
