@@ -17,49 +17,15 @@
 #include <cstring>
 #include <vector>
 
-typedef void* hipStream_t;
-#include "../include/dig_block_types.h"          // dig_wgrad_prob_t, dig_block_fwd_t, dig_block_bwd_t
-enum { DIG_OK = 0, DIG_ERR_ARG = -1, DIG_ERR_ALIGN = -2, DIG_ERR_LAUNCH = -3, DIG_ERR_UNSUPPORTED = -4 };
-typedef uint16_t bf16_t;
-
-struct dig_dropout_t {
-  unsigned k0, k1, thr;
-  float scale;
-  unsigned pk0, pk1, pthr;
-  float pscale;
-  int rows_per_sample;
-};
+#include "dig_cpu_common.h"
 
 namespace {
 
-inline float bf2f(bf16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-inline bf16_t f2bf(float f) {                       // round to nearest even, as v_cvt_pk_bf16_f32
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline float gelu_f(float x) { return 0.5f * x * (1.0f + std::erf(x * 0.70710678118654752f)); }
 inline float dgelu_f(float x) {
   const float cdf = 0.5f * (1.0f + std::erf(x * 0.70710678118654752f));
   return cdf + x * 0.39894228040143268f * std::exp(-0.5f * x * x);
 }
-inline unsigned drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
-  unsigned x = a ^ k0;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x += k1 + b * 0x9e3779b9u;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-inline bool drop_keep(unsigned k0, unsigned k1, unsigned a, unsigned b, unsigned thr) { return drop_hash(k0, k1, a, b) >= thr; }
 // element (i, j) of a [rows, cols] tensor under element dropout + drop-path (common.h dig_drop_apply8; a dropped element is +0)
 inline float drop_apply(float v, const dig_dropout_t& d, long long i, int j, int cols) {
   float s = 1.f;
@@ -207,12 +173,8 @@ int dig_reduce_partials(const float* partials, int splits, long long n, float* o
   return DIG_OK;
 }
 
-struct dig_reduce_seg_t { const float* partials; float* out; long long n; int splits; int reserved; };
-struct dig_colsum_seg_t { const float* partials; float* out; long long stride; int n_parts; int C; };
-static const int DIG_COLSUM_MAX_SEGS = 112;      // include/dig_hip.h
-
 int dig_reduce_partials_multi(const dig_reduce_seg_t* segs, int n_segs, hipStream_t stream) {
-  if (!segs || n_segs < 1 || n_segs > 8) return DIG_ERR_ARG;
+  if (!segs || n_segs < 1 || n_segs > DIG_REDUCE_MAX_SEGS) return DIG_ERR_ARG;
   for (int k = 0; k < n_segs; ++k) {
     const int rc = dig_reduce_partials(segs[k].partials, segs[k].splits, segs[k].n, segs[k].out, 1, stream);
     if (rc) return rc;
@@ -1559,7 +1521,6 @@ int dig_dropout_apply(const void* in_, void* out_, long long rows, int cols, con
 
 // ---- grouped weight gradients (csrc/wgrad.hip): same host-side planning and the same two-call protocol (partial slabs now, their
 // sum folded into the gradients by the next call); the slab layout is this build's own ([tile][split][128][128 fn], row-major)
-#define DIG_WGRAD_MAX_PROBS 6
 int dig_wgrad_group_supported(int I, int J, int R) {
   return (I > 0 && J > 0 && R >= 64 && I % 128 == 0 && (J % 384 == 0 || J % 256 == 0) && R % 64 == 0) ? 1 : 0;
 }

@@ -5,10 +5,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "dig_cpu_common.h"
 #include "../dig_amd/csrc/abiaug.inc"
-
-typedef void* hipStream_t;
-enum { DIG_OK = 0, DIG_ERR_ARG = -1, DIG_ERR_UNSUPPORTED = -4 };
 
 namespace {
 

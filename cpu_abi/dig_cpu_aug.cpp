@@ -6,10 +6,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "dig_cpu_common.h"
 #include "../dig_amd/csrc/keyview.inc"
-
-typedef void* hipStream_t;
-enum { DIG_OK = 0, DIG_ERR_ARG = -1, DIG_ERR_UNSUPPORTED = -4 };
 
 extern "C" {
 

@@ -10,43 +10,10 @@
 #include <limits>
 #include <vector>
 
-typedef void* hipStream_t;
-enum { DIG_OK = 0, DIG_ERR_ARG = -1, DIG_ERR_ALIGN = -2, DIG_ERR_LAUNCH = -3, DIG_ERR_UNSUPPORTED = -4 };
-typedef uint16_t bf16_t;
-
-struct dig_dropout_t {
-  unsigned k0, k1, thr;
-  float scale;
-  unsigned pk0, pk1, pthr;
-  float pscale;
-  int rows_per_sample;
-};
+#include "dig_cpu_common.h"
 
 namespace {
 
-inline float bf2f(bf16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-inline bf16_t f2bf(float f) {                       // round to nearest even, as v_cvt_pk_bf16_f32
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-inline unsigned drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
-  unsigned x = a ^ k0;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x += k1 + b * 0x9e3779b9u;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-inline bool drop_keep(unsigned k0, unsigned k1, unsigned a, unsigned b, unsigned thr) { return drop_hash(k0, k1, a, b) >= thr; }
 constexpr float NEG_INF = -std::numeric_limits<float>::infinity();
 
 // ---------------------------------------------------------------------------------------------------------------- input transform (N3)
@@ -392,7 +359,7 @@ int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const
                       int n, int* dist, hipStream_t) {
   if (!a || !a_len || !b || !b_len || !dist || lda <= 0 || ldb <= 0 || n <= 0 || a_rows <= 0) return DIG_ERR_ARG;
   if (!a_index && a_rows < n) return DIG_ERR_ARG;
-  if (lda > 128 || ldb > 128) return DIG_ERR_UNSUPPORTED;
+  if (lda > DIG_LEV_MAX_LEN || ldb > DIG_LEV_MAX_LEN) return DIG_ERR_UNSUPPORTED;
   for (int i = 0; i < n; ++i) {
     const int r = a_index ? a_index[i] : i;
     const bool have = r >= 0 && r < a_rows;
@@ -404,7 +371,7 @@ int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const
 
 long long dig_lexicon_search_workspace_bytes(int B, int max_count) {
   if (B <= 0 || max_count < 0) return 0;
-  return (long long)B * std::max(1LL, ((long long)max_count + 63) / 64) * 8;
+  return (long long)B * std::max(1LL, ((long long)max_count + DIG_LEXICON_CHUNK - 1) / DIG_LEXICON_CHUNK) * 8;
 }
 
 int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, const int* words, const int* word_len, int ldw, int W,
@@ -412,7 +379,7 @@ int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, c
                        long long workspace_bytes, hipStream_t) {
   if (!query || !query_len || !words || !word_len || !lex_begin || !lex_count || !best_index || !best_dist || !workspace) return DIG_ERR_ARG;
   if (ldq <= 0 || ldw <= 0 || B <= 0 || W <= 0 || max_count < 0) return DIG_ERR_ARG;
-  if (ldq > 128 || ldw > 128 || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if (ldq > DIG_LEV_MAX_LEN || ldw > DIG_LEV_MAX_LEN || B > 65535) return DIG_ERR_UNSUPPORTED;
   if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
   if (workspace_bytes < dig_lexicon_search_workspace_bytes(B, max_count)) return DIG_ERR_ARG;
   for (int q = 0; q < B; ++q) {

@@ -7,42 +7,10 @@
 #include <cstring>
 #include <vector>
 
-typedef void* hipStream_t;
-enum { DIG_OK = 0, DIG_ERR_ARG = -1, DIG_ERR_ALIGN = -2, DIG_ERR_LAUNCH = -3, DIG_ERR_UNSUPPORTED = -4 };
-typedef uint16_t bf16_t;
-
-struct dig_dropout_t {
-  unsigned k0, k1, thr;
-  float scale;
-  unsigned pk0, pk1, pthr;
-  float pscale;
-  int rows_per_sample;
-};
+#include "dig_cpu_common.h"
 
 namespace {
 
-inline float bf2f(bf16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-inline bf16_t f2bf(float f) {                       // round to nearest even, as v_cvt_pk_bf16_f32
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-inline unsigned drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
-  unsigned x = a ^ k0;
-  x ^= x >> 16; x *= 0x7feb352du;
-  x += k1 + b * 0x9e3779b9u;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 inline float keep(const dig_dropout_t* d, int t, int k, int sh) {
   if (!d || !d->thr) return 1.f;
   return drop_hash(d->k0, d->k1, ((unsigned)t << 16) | (unsigned)k, (unsigned)sh) >= d->thr ? d->scale : 0.f;

@@ -60,6 +60,8 @@ def stream():
 
 _fns = {}
 _protos = None
+_returns = {}
+_consts = {}
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "dig_hip.h")
 _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "float": ctypes.c_float,
             "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_ulonglong, "hipStream_t": ctypes.c_void_p}
@@ -68,19 +70,27 @@ _SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctyp
 def _prototypes():
     """{function name: [ctypes argument types]} parsed from include/dig_hip.h -- the header IS the contract, so the binding takes its
     argument types from it: every `long long` parameter is passed as 64 bits whatever the call site wrapped it in, floats are converted,
-    a wrong argument count fails in Python instead of reading garbage off the stack."""
+    a wrong argument count fails in Python instead of reading garbage off the stack.  The same parse fills _returns ({function name:
+    ctypes return type}, `int` or `long long`) and _consts ({name: value} of the header's integer #defines)."""
     global _protos
     if _protos is None:
         import re
         _protos = {}
         try:
             with open(_HEADER) as f:
-                text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+                text = f.read()
+            for inc in re.findall(r'#include "(\w+\.h)"', text):                  # dig_aug_types.h, dig_block_types.h: their constants
+                with open(os.path.join(os.path.dirname(_HEADER), inc)) as f:
+                    text += f.read()
+            text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
         except OSError:
             return _protos                                    # header not shipped next to the package: untyped calls, as before
-        for m in re.finditer(r"\b(?:int|long long)\s+(dig_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(DIG_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M):
+            _consts[m.group(1)] = int(m.group(2))
+        for m in re.finditer(r"\b(int|long long)\s+(dig_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+            _returns[m.group(2)] = _SCALARS[m.group(1)]
             types = []
-            for prm in m.group(2).split(","):
+            for prm in m.group(3).split(","):
                 prm = " ".join(prm.split())
                 if "*" in prm:
                     types.append(ctypes.c_void_p)
@@ -91,8 +101,32 @@ def _prototypes():
                     break
                 types.append(_SCALARS[ty])
             if types is not None:
-                _protos[m.group(1)] = types
+                _protos[m.group(2)] = types
     return _protos
+
+
+def const(name):
+    """The value of an integer #define of include/dig_hip.h or a header it includes (DIG_COLSUM_MAX_SEGS, DIG_KV_WORDS, ...)."""
+    _prototypes()
+    if name not in _consts:
+        raise DigHipError(f"{name} is not a constant of {_HEADER}")
+    return _consts[name]
+
+
+def query(name, *args):
+    """The value a host-side query returns (dig_*_workspace_bytes, dig_*_supported, the plan sizes ...): argument types AND return type
+    (`int` or `long long`) from the header, so a byte count above 2^31 arrives whole.  Launches go through call(); queries never do."""
+    f = _fns.get(name)
+    if f is None:
+        at = _prototypes().get(name)
+        if at is None:
+            raise DigHipError(f"{name} is not declared in {_HEADER}: a query cannot be typed without its prototype")
+        f = getattr(lib(), name)
+        f.restype, f.argtypes = _returns[name], at
+        _fns[name] = f
+    if len(args) != len(f.argtypes):                          # (ctypes itself refuses too few arguments only)
+        raise TypeError(f"{name} takes {len(f.argtypes)} arguments, {len(args)} given")
+    return f(*args)
 
 
 def call(name, *args):

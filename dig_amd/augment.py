@@ -27,7 +27,7 @@ PARAMS_DTYPE = np.dtype([
     ("blur_radius", "<i4"), ("blur_taps", "<f4", 11), ("sharpen_k", "<f4", 9), ("crop_y", "<i4", 2), ("crop_x", "<i4", 2),
     ("rot", "<f4", 6), ("homog", "<f4", 9),
     ("jitter", "<i4"), ("jit_order", "<i4", 4), ("jit_factor", "<f4", 4), ("hue_shift", "<i4"), ("gray", "<i4"), ("pad", "<i4", 17)])
-PARAMS_WORDS = 128
+PARAMS_WORDS = L.const("DIG_KV_WORDS")
 assert PARAMS_DTYPE.itemsize == 4 * PARAMS_WORDS
 
 OP_NAMES = ("LinearContrast", "GaussianBlur", "CropRows", "CropCols", "Sharpen", "Rotate", "PiecewiseAffine", "PerspectiveTransform",
@@ -115,10 +115,7 @@ class KeyViewAugment:
 
 
 def _workspace_bytes(packed_bytes, n_img):
-    f = L.lib().dig_keyview_workspace_bytes
-    f.restype = ctypes.c_longlong
-    f.argtypes = [ctypes.c_longlong, ctypes.c_int]
-    ws = f(packed_bytes, n_img)
+    ws = L.query("dig_keyview_workspace_bytes", packed_bytes, n_img)
     if ws <= 0:
         L.check(int(ws), "dig_keyview_workspace_bytes")
     return ws
@@ -133,7 +130,7 @@ ABI_PARAMS_DTYPE = np.dtype([
     ("persp_ow", "<i4", 4), ("persp_oh", "<i4", 4), ("h", "<i4"), ("w", "<i4"), ("wh", "<i4"), ("ww", "<i4"), ("minv", "<f4", 9),
     ("rs_interp", "<i4", 2), ("mb_k", "<f4", 25), ("jit_order", "<i4", 4), ("jit_factor", "<f4", 4), ("hue_shift", "<i4"),
     ("noise_key", "<u4", 2), ("noise_step", "<u4"), ("final_buf", "<i4"), ("pad0", "<i4"), ("ws_off", "<i8"), ("pad", "<i4", 24)])
-ABI_PARAMS_WORDS = 96
+ABI_PARAMS_WORDS = L.const("DIG_ABI_WORDS")
 assert ABI_PARAMS_DTYPE.itemsize == 4 * ABI_PARAMS_WORDS
 ABI_RUN_DTYPE = np.dtype([("geom_type", "<i4"), ("noise_var", "<i4"), ("mb_size", "<i4"), ("mb_angle", "<f4"), ("rescale_factor", "<i4"),
                           ("det_order", "<i4", 3)])
@@ -244,11 +241,8 @@ class AbiAugment:
 
 def workspace_bytes(geom, det, wh, ww, run):
     """Workspace bytes of one image (dig_abiaug_workspace_bytes)."""
-    f = L.lib().dig_abiaug_workspace_bytes
-    f.restype = ctypes.c_longlong
-    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     buf = np.ascontiguousarray(np.asarray(run, dtype=ABI_RUN_DTYPE).reshape(1))
-    b = f(int(geom), int(det), int(wh), int(ww), ctypes.c_void_p(buf.ctypes.data))
+    b = L.query("dig_abiaug_workspace_bytes", int(geom), int(det), int(wh), int(ww), ctypes.c_void_p(buf.ctypes.data))
     if b < 0:
         L.check(int(b), "dig_abiaug_workspace_bytes")
     return b

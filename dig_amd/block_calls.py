@@ -147,7 +147,7 @@ def backward(plan, blocks, saved, dx, wT, wplan, n_img, heads, Fh, side, keep, b
     off, n16, n32 = ops.block_bwd_layout(R, D, Fh, n_img)
     grp = wplan.group
     stream, key = ops.L.stream(), ("bwd_call", R, n_img)
-    n_b, n_l2 = ops.L.lib().dig_mlp_chain_colsum_rows(R), ops.L.lib().dig_mlp_chain_ln_parts(R)
+    n_b, n_l2 = ops.L.query("dig_mlp_chain_colsum_rows", R), ops.L.query("dig_mlp_chain_ln_parts", R)
     red = ops.GradReduceBatch() if plan.red_defer else None
 
     def block(i, dy_ptr, probs, fold=None):

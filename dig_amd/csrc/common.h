@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
+#include "../../include/dig_hip.h"   // the ABI's types, limits and error codes; every entry point is compiled against its declaration
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -14,12 +15,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef unsigned dig_u32x4 __attribute__((ext_vector_type(4)));
-
-#define DIG_OK 0
-#define DIG_ERR_ARG (-1)
-#define DIG_ERR_ALIGN (-2)
-#define DIG_ERR_LAUNCH (-3)
-#define DIG_ERR_UNSUPPORTED (-4)
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
@@ -155,21 +150,7 @@ __device__ __forceinline__ void dgelu2(float xa, float xb, float& ga, float& gb)
 // backward (and the CPU oracle, oracle/finetune_oracle.py `keep_mask`) regenerate the same mask from (key, coordinates)
 // and no mask tensor is ever stored.  ~9 integer ops per element; coordinates: elementwise tensors a = row * cols + col,
 // b = 0; attention probabilities a = (query << 16) | key, b = sample * heads + head; drop-path a = sample, b = 0.
-// multi-segment reduction descriptors (include/dig_hip.h: dig_reduce_seg_t, dig_colsum_seg_t)
-#define DIG_REDUCE_MAX_SEGS 8
-#define DIG_COLSUM_MAX_SEGS 112
-struct dig_reduce_seg_t { const float* partials; float* out; long long n; int splits; int reserved; };
-struct dig_colsum_seg_t { const float* partials; float* out; long long stride; int n_parts; int C; };
-
-struct dig_dropout_t {
-  unsigned k0, k1;        // site key
-  unsigned thr;           // 0: no element dropout
-  float scale;            // 1 / (1 - p)
-  unsigned pk0, pk1;      // drop-path key
-  unsigned pthr;          // 0: no drop-path
-  float pscale;           // 1 / (1 - drop_path)
-  int rows_per_sample;    // drop-path: sample = row / rows_per_sample
-};
+// A site's keys, thresholds and scales travel as dig_dropout_t (include/dig_hip.h).
 __device__ __forceinline__ unsigned dig_drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
   unsigned x = a ^ k0;
   x ^= x >> 16; x *= 0x7feb352du;

@@ -5,8 +5,8 @@
 
 namespace {
 
-constexpr int LEV_MAX = 128;                             // DIG_LEV_MAX_LEN of include/dig_hip.h: longest string either side
-constexpr int LEX_CHUNK = 64;                            // DIG_LEXICON_CHUNK: words per workgroup of the search = one wave, one word per lane
+constexpr int LEV_MAX = DIG_LEV_MAX_LEN;                 // longest string either side
+constexpr int LEX_CHUNK = DIG_LEXICON_CHUNK;             // words per workgroup of the search = one wave, one word per lane
 
 // Levenshtein distance (unit costs) of x[0..xlen) and y[0..ylen), one pair per lane.  The DP row runs over y: cell j = distance of the
 // prefix of x read so far to y[0..j).  Cell 0 is the number of x characters read and stays in a register; cells 1..ylen live in LDS as

@@ -36,16 +36,9 @@
 #define DIG_WG_TS_END()
 #endif
 
-#define DIG_WGRAD_MAX_PROBS 6
-struct dig_wgrad_prob_t {
-  const void* A;      // [R, lda] bf16: the wide operand (I columns, I % 128 == 0)
-  const void* B;      // [R, ldb] bf16: the narrow operand (J columns, J % (128 FN) == 0)
-  float* out;         // fp32 gradient: [I, ldo] (trans_out 0) or [J, ldo] (trans_out 1), accumulated into
-  int lda, ldb, ldo;
-  int I, J;
-  int trans_out;
-};
-
+// One problem is a dig_wgrad_prob_t (include/dig_block_types.h): A [R, lda] bf16, the wide operand (I columns, I % 128 == 0); B [R, ldb]
+// bf16, the narrow operand (J columns, J % (128 FN) == 0); out the fp32 gradient, [I, ldo] (trans_out 0) or [J, ldo] (trans_out 1),
+// accumulated into.
 namespace {
 
 constexpr int WG_BK = 16;                 // token rows per ring stage

@@ -26,8 +26,8 @@ import torch
 from . import _lib as L
 from . import recognizer
 
-MAX_WORD_LEN = 128                      # DIG_LEV_MAX_LEN
-CHUNK = 64                              # DIG_LEXICON_CHUNK: words per workgroup of the search
+MAX_WORD_LEN = L.const("DIG_LEV_MAX_LEN")
+CHUNK = L.const("DIG_LEXICON_CHUNK")    # words per workgroup of the search
 _KEEP = string.digits + string.ascii_letters
 
 
@@ -58,10 +58,7 @@ def edit_distance(a, a_len, b, b_len, a_index=None):
 
 
 def lexicon_search_workspace_bytes(B, max_count):
-    import ctypes
-    f = L.lib().dig_lexicon_search_workspace_bytes
-    f.restype, f.argtypes = ctypes.c_longlong, [ctypes.c_int, ctypes.c_int]
-    return int(f(B, max_count))
+    return L.query("dig_lexicon_search_workspace_bytes", B, max_count)
 
 
 def lexicon_search(query, query_len, words, word_len, lex_begin, lex_count):

@@ -99,7 +99,7 @@ def narrow_splits(rows, out_cols, K):
     gradients: 1024 x 256 outputs are 32 workgroups walking 64 K-steps; eight slices of 512 make them 256 workgroups + a 1 MB combine:
     67-73 us in the step -> ~20), or 1."""
     if NARROW_SPLIT and rows <= 2048 and out_cols <= 512 and K >= 2048 and K % 512 == 0 and (rows * out_cols) % 4 == 0:
-        return L.lib().dig_gemm_effective_splits(int(K), K // 512)
+        return L.query("dig_gemm_effective_splits", int(K), K // 512)
     return 1
 
 
@@ -138,7 +138,7 @@ MLP_CHAIN_LN = os.environ.get("DIG_MLP_CHAIN_LN", "1") != "0"
 def mlp_chain_supported(D, F, rows=None):
     """rows: the token rows of the call (the fused kernels address the [rows, F] side tensors with 32-bit byte offsets: beyond 2^32 bytes
     the entry points return "unsupported", and the caller takes the two-GEMM path instead)."""
-    return MLP_CHAIN and bool(L.lib().dig_mlp_chain_supported(int(D), int(F))) and (rows is None or rows * F * 2 < (1 << 32))
+    return MLP_CHAIN and bool(L.query("dig_mlp_chain_supported", int(D), int(F))) and (rows is None or rows * F * 2 < (1 << 32))
 
 
 def mlp_chain_fwd(x, w1, b1, w2, b2, resid, save=False):
@@ -193,7 +193,7 @@ def mlp_chain_bwd(dy, w2t, pre, w1t, colsum=True, out=None):
     Fh = w2t.shape[0]
     dx = torch.empty((rows, D), device=dy.device, dtype=BF16) if out is None else out
     dpre = torch.empty((rows, Fh), device=dy.device, dtype=BF16)
-    parts = torch.empty((L.lib().dig_mlp_chain_colsum_rows(rows), Fh), device=dy.device, dtype=F32) if colsum else None
+    parts = torch.empty((L.query("dig_mlp_chain_colsum_rows", rows), Fh), device=dy.device, dtype=F32) if colsum else None
     L.call("dig_mlp_chain_bwd", L.ptr(dy), L.ptr(w2t), L.ptr(pre), L.ptr(w1t), L.ptr(dpre), L.ptr(dx), L.ptr(parts), rows, D, Fh, L.stream())
     return dx, dpre, parts
 
@@ -214,9 +214,9 @@ def mlp_chain_bwd_ln(dy, w2t, pre, w1t, x_mid, ln_g, ln_mean, ln_rstd, colsum=Tr
     Fh = w2t.shape[0]
     dx = torch.empty((rows, D), device=dy.device, dtype=BF16) if out is None else out
     dpre = torch.empty((rows, Fh), device=dy.device, dtype=BF16)
-    n = L.lib().dig_mlp_chain_colsum_rows(rows)
+    n = L.query("dig_mlp_chain_colsum_rows", rows)
     parts = torch.empty((n, Fh), device=dy.device, dtype=F32) if colsum else None
-    ln_parts = torch.empty((L.lib().dig_mlp_chain_ln_parts(rows), 3, D), device=dy.device, dtype=F32)
+    ln_parts = torch.empty((L.query("dig_mlp_chain_ln_parts", rows), 3, D), device=dy.device, dtype=F32)
     if projt is not None:
         dctx = torch.empty((rows, D), device=dy.device, dtype=BF16) if dctx is None else dctx
         L.call("dig_mlp_chain_bwd_ln_proj", L.ptr(dy), L.ptr(w2t), L.ptr(pre), L.ptr(w1t), L.ptr(dpre), L.ptr(x_mid), L.ptr(ln_g), L.ptr(ln_mean),
@@ -354,7 +354,7 @@ def wgrad_splits(rows, tiles):
     cap = max(1, rows // 512)
     if cap < want:
         want = max(1, (cap // 8) * 8 or cap)
-    return L.lib().dig_gemm_effective_splits(rows, want), bk
+    return L.query("dig_gemm_effective_splits", rows, want), bk
 
 
 def wgrad(dy, x, dw, I, J, rows):
@@ -379,7 +379,7 @@ def _batch_workspace(dev, numel):
     return w
 
 
-COLSUM_MAX_SEGS = 112                                               # include/dig_hip.h DIG_COLSUM_MAX_SEGS
+COLSUM_MAX_SEGS = L.const("DIG_COLSUM_MAX_SEGS")
 
 
 class _ReduceSeg(ctypes.Structure):
@@ -426,7 +426,7 @@ class GradReduceBatch:
 
     def layernorm_finalize(self, ws, rows, D, dgamma, dbeta, dcolsum):
         """dig_layernorm_bwd_finalize of a deferred layernorm_bwd(..., defer=True) workspace at flush()."""
-        n = L.lib().dig_layernorm_bwd_parts(rows)
+        n = L.query("dig_layernorm_bwd_parts", rows)
         for k, out in enumerate((dgamma, dbeta, dcolsum)):
             if out is not None:
                 self._vec(ws[k * D:], out, 3 * D, n, D)
@@ -494,13 +494,12 @@ class _WgProb(ctypes.Structure):
 def wgrad_group_route(out_dim, in_dim, rows, fn=None):
     """How dW[out_dim, in_dim] = dy^T x joins a group: (trans_out, fn) -- the narrow operand is x (fc1, qkv, proj) or dy (fc2) -- or None.
     fn: the tile width code of the group it has to match (None: any)."""
-    lib = L.lib()
     cands = ((0, out_dim, in_dim), (1, in_dim, out_dim))
     if out_dim < in_dim:                                             # the narrow operand is the model width: the smaller dimension first
         cands = cands[::-1]
     for trans, wide, narrow in cands:
-        if narrow <= 512 and lib.dig_wgrad_group_supported(int(wide), int(narrow), int(rows)):
-            f = lib.dig_wgrad_group_fn(int(narrow))
+        if narrow <= 512 and L.query("dig_wgrad_group_supported", int(wide), int(narrow), int(rows)):
+            f = L.query("dig_wgrad_group_fn", int(narrow))
             if fn is None or f == fn:
                 return trans, f
     return None
@@ -536,7 +535,7 @@ class WgradGroup:
             cap = 8 * max(WGRAD_GROUP_SLOTS, sum(tiles))
             buf = (ctypes.c_uint * cap)()
             sp = ctypes.c_int(0)
-            n = L.lib().dig_wgrad_group_plan(tp, len(tiles), int(self.rows), WGRAD_GROUP_SLOTS, ctypes.byref(sp), buf, cap)
+            n = L.query("dig_wgrad_group_plan", tp, len(tiles), int(self.rows), WGRAD_GROUP_SLOTS, ctypes.byref(sp), buf, cap)
             if n <= 0:
                 L.check(n or -1, "dig_wgrad_group_plan")
             import numpy as np
@@ -581,7 +580,7 @@ class WgradGroup:
         if not self.cur and self.pending is None:
             return
         fn, wa = self.fn, WGRAD_GROUP_WA
-        tiles = [L.lib().dig_wgrad_group_tiles(int(dw.shape[1] if t else dw.shape[0]), int(dw.shape[0] if t else dw.shape[1]), fn, wa)
+        tiles = [L.query("dig_wgrad_group_tiles", int(dw.shape[1] if t else dw.shape[0]), int(dw.shape[0] if t else dw.shape[1]), fn, wa)
                  for _, _, dw, t in self.cur]
         if self.cur:
             splits, n_wg, wmap = self._plan(tiles)
@@ -659,10 +658,9 @@ def block_bwd_layout(rows, D, Fh, n_img):
         for name, cols in (("dln2", D), ("dpre", Fh), ("dctx", D), ("dqkv", 3 * D)):
             off[name] = n16
             n16 += _round_up(rows * cols * 2, 256)
-        lib = L.lib()
-        parts = lib.dig_layernorm_bwd_parts(rows) * 3 * D
-        parts2 = max(parts, lib.dig_mlp_chain_ln_parts(rows) * 3 * D)                 # (ws2 with fuse_ln2: one partial row per 128 tokens)
-        for name, n in (("bparts", lib.dig_mlp_chain_colsum_rows(rows) * Fh), ("ws1", parts), ("ws2", parts2), ("qs", n_img * D), ("vs", n_img * D)):
+        parts = L.query("dig_layernorm_bwd_parts", rows) * 3 * D
+        parts2 = max(parts, L.query("dig_mlp_chain_ln_parts", rows) * 3 * D)                 # (ws2 with fuse_ln2: one partial row per 128 tokens)
+        for name, n in (("bparts", L.query("dig_mlp_chain_colsum_rows", rows) * Fh), ("ws1", parts), ("ws2", parts2), ("qs", n_img * D), ("vs", n_img * D)):
             off[name] = n32
             n32 += _round_up(n * 4, 256)
         lay = _block_layouts[key] = (off, n16, n32)
@@ -685,7 +683,7 @@ def wgrad_block_plan(dev, rows, D, Fh):
             return None
         t, grp.fn = r
         trans.append(t)
-        tiles.append(L.lib().dig_wgrad_group_tiles(int(in_dim if t else out_dim), int(out_dim if t else in_dim), grp.fn, WGRAD_GROUP_WA))
+        tiles.append(L.query("dig_wgrad_group_tiles", int(in_dim if t else out_dim), int(out_dim if t else in_dim), grp.fn, WGRAD_GROUP_WA))
     splits, n_wg, wmap = grp._plan(tiles)
     return WgradBlockPlan(grp.fn, WGRAD_GROUP_WA, splits, n_wg, wmap, trans, grp, sum(tiles) * splits * 128 * WGRAD_GROUP_WA * 128 * grp.fn * 4)
 
@@ -732,7 +730,7 @@ def layernorm_bwd(dy, x, gamma, beta, mean, rstd, dres, dgamma, dbeta, gelu=Fals
         L.call("dig_layernorm_bwd", L.ptr(dy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx),
                L.ptr(dgamma), L.ptr(dbeta), L.ptr(dres_colsum), L.ptr(ws), rows, D, int(gelu), L.stream())
         return dx
-    ws = torch.empty(L.lib().dig_layernorm_bwd_parts(rows) * 3 * D, device=x.device, dtype=F32)
+    ws = torch.empty(L.query("dig_layernorm_bwd_parts", rows) * 3 * D, device=x.device, dtype=F32)
     L.call("dig_layernorm_bwd_partials", L.ptr(dy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd), L.ptr(dres),
            L.ptr(dx), L.ptr(ws), rows, D, int(gelu), L.stream())
 
@@ -801,7 +799,7 @@ ATTN_BLOCK_MIN_IMG = int(os.environ.get("DIG_ATTN_BLOCK_MIN_IMG", "160"))
 
 def attn_block_supported(heads, D, n_img=None):
     return (ATTN_BLOCK and (n_img is None or n_img >= ATTN_BLOCK_MIN_IMG or n_img < 32)
-            and bool(L.lib().dig_attn_block_supported(int(heads), int(D))))
+            and bool(L.query("dig_attn_block_supported", int(heads), int(D))))
 
 
 def attn_block_fwd(ln1, x, qkv_w, qkv_b, proj_w, proj_b, n_img, heads, D, scale, save=False):
@@ -818,7 +816,7 @@ def attn_block_fwd(ln1, x, qkv_w, qkv_b, proj_w, proj_b, n_img, heads, D, scale,
 
 def attn_bwd_mode(single_pass=None):
     """Select (True / False) or query (None) the kernel behind attn_bwd for full self-attention: single pass or two phases.  Returns the previous setting."""
-    return bool(L.lib().dig_attn_bwd_mode(-1 if single_pass is None else int(bool(single_pass))))
+    return bool(L.query("dig_attn_bwd_mode", -1 if single_pass is None else int(bool(single_pass))))
 
 
 if os.environ.get("DIG_ATTN_BWD_SP") in ("0", "1"):
@@ -830,7 +828,7 @@ def attn_bwd_store(mode=None):
     128-byte lines through LDS, non-temporal (the default).  Bit-identical results.  Returns the previous setting."""
     if mode is not None and mode not in (0, 1, 3):
         raise ValueError(f"attn_bwd_store: mode {mode!r} (one of 0, 1, 3)")
-    return int(L.lib().dig_attn_bwd_store(-1 if mode is None else int(mode)))
+    return int(L.query("dig_attn_bwd_store", -1 if mode is None else int(mode)))
 
 
 if os.environ.get("DIG_ATTN_BWD_STORE") is not None:
@@ -991,9 +989,7 @@ def gelu_bwd(dact, pre, out):
 
 
 def _bn_ws_floats(rows, C):
-    f = L.lib().dig_bn_stats_workspace_bytes
-    f.restype = ctypes.c_longlong
-    return int(f(int(rows), int(C))) // 4
+    return L.query("dig_bn_stats_workspace_bytes", int(rows), int(C)) // 4
 
 
 def bn_stats(x, sums):
@@ -1018,7 +1014,7 @@ BN_FUSED = os.environ.get("DIG_BN_FUSED", "1") != "0"      # few-row BatchNorm l
 
 
 def bn_fused_supported(rows, C):
-    return BN_FUSED and bool(L.lib().dig_bn_fused_supported(int(rows), int(C)))
+    return BN_FUSED and bool(L.query("dig_bn_fused_supported", int(rows), int(C)))
 
 
 def bn_fwd_fused(x, eps, gamma, beta, relu, running=None):

@@ -1,5 +1,5 @@
 /* dig_block_types.h -- argument tables of dig_encoder_block_fwd / dig_encoder_block_bwd (declared in dig_hip.h, which includes this file
- * after its hipStream_t typedef; the host-only build under cpu_abi/ includes it after its own).  Plain C, device pointers unless stated.
+ * after its hipStream_t typedef; both builds get it through dig_hip.h).  Plain C, device pointers unless stated.
  *
  * One call = one encoder block of the DiG ViT (Block.forward, modeling_finetune.py:150-158, called from
  * PretrainVisionTransformerEncoder.forward_features :312-334) or its gradient: the launch sequence that dig_amd/engine_core.py otherwise

@@ -30,6 +30,13 @@ typedef struct ihipStream_t* hipStream_t;
 
 #include "dig_aug_types.h"
 
+/* the return values of every entry point (conventions above) */
+#define DIG_OK 0
+#define DIG_ERR_ARG (-1)
+#define DIG_ERR_ALIGN (-2)
+#define DIG_ERR_LAUNCH (-3)
+#define DIG_ERR_UNSUPPORTED (-4)
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Matrix-core GEMM.  Replaces F.linear / nn.Linear and its autograd (modeling_finetune.py:53-60,91-93,119;
  * modeling_pretrain_moco_mim_ori.py:414-426,463-482).

@@ -14,6 +14,14 @@ def test_exports_every_entry_point_of_the_header():
     """dig_cpu.cpp (the pre-training step) + dig_cpu_rec.cpp (the recognition rows N1 / N3 / N4): the whole header, nothing else."""
     exp, decl = set(exported()), set(declared_symbols())
     assert exp == decl, (sorted(exp - decl), sorted(decl - exp))
+    # "its prototypes are the header's" is the compiler's check: both builds define their entry points with the header's declarations in
+    # scope.  Deleting the include would turn that check off without failing a build, so the include itself is pinned here.
+    import glob, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    units = sorted(glob.glob(os.path.join(root, "cpu_abi", "*.cpp")))
+    assert len(units) >= 5 and all('#include "dig_cpu_common.h"' in open(u).read() for u in units), units
+    assert '#include "../include/dig_hip.h"' in open(os.path.join(root, "cpu_abi", "dig_cpu_common.h")).read()
+    assert '#include "../../include/dig_hip.h"' in open(os.path.join(root, "dig_amd", "csrc", "common.h")).read()
 
 
 def test_product_never_loads_the_cpu_build():
@@ -44,6 +52,28 @@ def test_error_codes_match_the_abi():
         y = torch.zeros(64, 100, dtype=torch.bfloat16)                     # LayerNorm width outside {64..512}: -4 unsupported
         with pytest.raises(_lib.DigHipError, match="unsupported"):
             ops.layernorm_fwd(y, torch.ones(100), torch.zeros(100), 1e-6)
+
+
+def test_queries_are_typed_from_the_header():
+    """_lib.query: argument types and return type (`int` or `long long`) from the header's prototype; _lib.const: its #defines."""
+    with cpu_abi_backend():
+        from dig_amd import _lib as L
+        assert L.query("dig_layernorm_bwd_workspace_bytes", 65536, 384) == 1024 * 3 * 384 * 4
+        assert L.query("dig_gemm_effective_splits", 716, 8) == 6
+        raw = ctypes.CDLL(build()).dig_keyview_workspace_bytes           # a handle of its own, typed by hand: 64-bit argument and result
+        raw.restype, raw.argtypes = ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int]
+        want = raw(3 << 30, 1)
+        assert want == 6 << 30 and want > 1 << 31
+        assert L.query("dig_keyview_workspace_bytes", 3 << 30, 1) == want
+        with pytest.raises((TypeError, ctypes.ArgumentError)):
+            L.query("dig_keyview_workspace_bytes", 3 << 30)
+        with pytest.raises((TypeError, ctypes.ArgumentError)):
+            L.query("dig_gemm_effective_splits", 716, 8, 1)
+        with pytest.raises(L.DigHipError):
+            L.query("dig_no_such_query", 1)
+        assert L.const("DIG_COLSUM_MAX_SEGS") == 112 and L.const("DIG_ERR_UNSUPPORTED") == -4 and L.const("DIG_KV_WORDS") == 128
+        with pytest.raises(L.DigHipError):
+            L.const("DIG_NO_SUCH_CONSTANT")
 
 
 @pytest.mark.gpu
