@@ -355,6 +355,29 @@ int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int 
   return DIG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- labels (csrc/labels.hip)
+int dig_encode_labels(const int* chars, const int* offsets, const int* class_of, int eos, int padding, int unknown, int max_len, int B,
+                      long long* labels, long long* lens, hipStream_t) {
+  if (!chars || !offsets || !class_of || !labels || !lens || max_len < 1 || B < 0) return DIG_ERR_ARG;
+  if (B == 0) return DIG_OK;
+  if ((long long)B * max_len > 0x7fffffffLL) return DIG_ERR_UNSUPPORTED;
+  for (int b = 0; b < B; ++b) {
+    const int begin = offsets[b], n = std::clamp(offsets[b + 1] - begin, 0, max_len - 1);
+    long long* row = labels + (size_t)b * max_len;
+    for (int t = 0; t < max_len; ++t) {
+      if (t < n) {
+        const int c = chars[begin + t];
+        const int k = (c >= 0 && c < 128) ? class_of[c] : -1;
+        row[t] = k >= 0 ? k : unknown;
+      } else {
+        row[t] = t == n ? eos : padding;
+      }
+    }
+    lens[b] = n + 1;
+  }
+  return DIG_OK;
+}
+
 int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const int* a_index, const int* b, const int* b_len, int ldb,
                       int n, int* dist, hipStream_t) {
   if (!a || !a_len || !b || !b_len || !dist || lda <= 0 || ldb <= 0 || n <= 0 || a_rows <= 0) return DIG_ERR_ARG;

@@ -12,8 +12,12 @@ per view produces the normalised fp32 batch bit-exactly as Pillow + torchvision 
 
 With `key_view_aug="seqclr"` and no `aug_crops`, the second view is the reference's augmented key view (seqCLR ops + ColorJitter +
 RandomGrayscale), drawn and applied on the device from the first view's upload (dig_amd/augment.py).
+
+For fine-tuning, `FinetuneBatchTransform` is the image side and `LabelEncoder` the label side: words -> target rows and lengths, on the device
+(`dig_encode_labels`); dig_amd/rec_datasets.py puts both behind a loader.
 """
 import ctypes
+import string
 
 import numpy as np
 import torch
@@ -111,3 +115,84 @@ class FinetuneBatchTransform:
         if self.aug is None:
             return resize_normalize(packed, self.h, self.w)
         return self.aug(packed)
+
+
+VOC_TYPES = ("LOWERCASE", "ALLCASES", "ALLCASES_SYMBOLS")
+
+
+def find_classes(voc_type, EOS="EOS", PADDING="PADDING", UNKNOWN="UNKNOWN"):
+    """ImageLmdb._find_classes (dataset/dataset_lmdb.py:75-97): the character list of a vocabulary type plus the three special classes."""
+    if voc_type == "LOWERCASE":
+        voc = list(string.digits + string.ascii_lowercase + '!"#$%&\'()*+,-./:;<=>?@[\\]^_`{|}~')
+    elif voc_type == "ALLCASES":
+        voc = list(string.digits + string.ascii_letters)
+    elif voc_type == "ALLCASES_SYMBOLS":
+        voc = list(string.printable[:-6])
+    else:
+        raise KeyError('voc_type must be one of "LOWERCASE", "ALLCASES", "ALLCASES_SYMBOLS"')
+    return voc + [EOS, PADDING, UNKNOWN]
+
+
+def encode_code_points(rows, class_of, eos, padding, unknown, max_len, device):
+    """`dig_encode_labels` on a batch of words given as sequences of code points: (labels int64 [B, max_len], lens int64 [B]) on `device`.
+    class_of: int32 [128] on `device`.  chars and offsets travel in one (pinned) buffer, offsets first.  Every row must fit:
+    len(row) + 1 <= max_len (the callers check; the kernel clamps)."""
+    B = len(rows)
+    dev = torch.device(device)
+    labels = torch.empty((B, max_len), device=dev, dtype=torch.int64)
+    lens = torch.empty(B, device=dev, dtype=torch.int64)
+    if B == 0:                                                                    # (empty tensors have no address to hand over)
+        return labels, lens
+    offs = np.zeros(B + 1, dtype=np.int32)
+    np.cumsum([len(r) for r in rows], out=offs[1:])
+    host = torch.empty(B + 1 + max(int(offs[-1]), 1), dtype=torch.int32)           # (one spare cell: `chars` is never a null pointer)
+    if dev.type == "cuda":
+        host = host.pin_memory()
+    flat = host.numpy()
+    flat[:B + 1] = offs
+    flat[B + 1:B + 1 + int(offs[-1])] = np.fromiter((c for r in rows for c in r), dtype=np.int32, count=int(offs[-1]))
+    up = host.to(dev, non_blocking=True)
+    L.call("dig_encode_labels", L.ptr(up[B + 1:]), L.ptr(up), L.ptr(class_of), eos, padding, unknown, max_len, B, L.ptr(labels), L.ptr(lens), L.stream())
+    return labels, lens
+
+
+class LabelEncoder:
+    """Words -> the `[B, max_len]` target rows and lengths of the fine-tune step, on the device: what ImageLmdb.__getitem__ does per sample
+    in a dataloader worker (dataset/dataset_lmdb.py:181-204), for a whole batch in one launch.  Owns the vocabulary of `voc_type`
+    (`classes`, `class_to_idx`, `idx_to_class`, :70-72).  `LOWERCASE` folds on the host -- `str.lower()` can change a word's length -- the
+    rest (class lookup, UNKNOWN for anything else, EOS, PADDING, length) happens in `dig_encode_labels`."""
+
+    def __init__(self, voc_type="ALLCASES_SYMBOLS", max_len=25, device="cuda"):
+        if voc_type not in VOC_TYPES:
+            raise ValueError(f"voc_type must be one of {VOC_TYPES}, not {voc_type!r}")
+        if max_len < 1:
+            raise ValueError("max_len must be at least 1")
+        self.voc_type, self.max_len, self.device = voc_type, int(max_len), torch.device(device)
+        self.classes = find_classes(voc_type)
+        self.class_to_idx = dict(zip(self.classes, range(len(self.classes))))
+        self.idx_to_class = dict(zip(range(len(self.classes)), self.classes))
+        self.use_lowercase = voc_type == "LOWERCASE"
+        self.eos, self.padding, self.unknown = (self.class_to_idx[k] for k in ("EOS", "PADDING", "UNKNOWN"))
+        self.class_of_host = torch.tensor([self.class_to_idx.get(chr(c), -1) for c in range(128)], dtype=torch.int32)
+        self._class_of = None
+
+    @property
+    def nb_classes(self):
+        return len(self.classes)
+
+    def class_of(self):
+        if self._class_of is None:
+            self._class_of = self.class_of_host.to(self.device)
+        return self._class_of
+
+    def normalize(self, word):
+        """The word as the datasets label it (dataset_lmdb.py:182-183)."""
+        return word.lower() if self.use_lowercase else word
+
+    def __call__(self, words):
+        words = [self.normalize(w) for w in words]
+        for w in words:
+            if len(w) + 1 > self.max_len:
+                raise ValueError(f"word {w!r} has {len(w)} characters: with EOS it does not fit max_len = {self.max_len}")
+        return encode_code_points([[ord(c) for c in w] for w in words], self.class_of(), self.eos, self.padding, self.unknown, self.max_len,
+                                  self.device)

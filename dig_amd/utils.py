@@ -327,6 +327,8 @@ def save_model(args, epoch, model, model_without_ddp, optimizer, loss_scaler, mo
     if hasattr(model_without_ddp, "drop_step") and not (hasattr(model_without_ddp, "dpr") and not getattr(model_without_ddp, "drop_path_rate", 0.0)
                                                        and hasattr(model_without_ddp, "use_moco_target")):
         ck['dig_amd'] = {'drop_seed': int(model_without_ddp.drop_seed), 'drop_step': int(model_without_ddp.drop_step)}   # reference ignores it)
+    if model_ema is not None:                                                   # --model_ema: the averaged weights (utils/utils.py:563-564)
+        ck['model_ema'] = dict(model_ema.ema.state_dict())
     torch.save(ck, path)
 
 
@@ -349,7 +351,10 @@ def auto_load_model(args, model, model_without_ddp, optimizer, loss_scaler, mode
         print("Resume checkpoint %s" % args.resume)
         if 'optimizer' in ck and 'epoch' in ck:
             optimizer.load_state_dict(ck['optimizer'])
-            args.start_epoch = ck['epoch'] + 1
+            if isinstance(ck['epoch'], int):                                    # (checkpoint-best.pth carries "best", utils/utils.py:641-643)
+                args.start_epoch = ck['epoch'] + 1
+            if model_ema is not None and 'model_ema' in ck:                     # (utils/utils.py:645-646)
+                model_ema.ema.load_state_dict(ck['model_ema'])
             if 'scaler' in ck:
                 loss_scaler.load_state_dict(ck['scaler'])
             print("With optim & sched!")

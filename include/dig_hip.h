@@ -501,6 +501,16 @@ int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long long* offs
 int dig_abiaug_tail(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                     const struct dig_abi_params* params, const struct dig_abi_run* run, const unsigned char* work, long long work_bytes,
                     float* out, int out_h, int out_w, float mean, float std_, int max_wh, int max_ww, hipStream_t stream);
+/* ---- label encoder: the words of a batch -> the target rows and lengths of the fine-tune step (ImageLmdb.__getitem__,
+ * dataset/dataset_lmdb.py:189-204), the inverse of dig_tokens_to_text.  chars: the code points (one per Python `str` element) of all B
+ * words packed end to end; offsets: [B + 1], word b is chars[offsets[b] .. offsets[b + 1]); class_of: [128], ASCII code point -> class id,
+ * -1 where the vocabulary has no such character.  labels [B][max_len] int64: one label per code point -- class_of[c], or `unknown` for
+ * c outside [0, 128) or mapped to -1 -- then `eos`, then `padding` to max_len; lens [B] int64 = word length + 1.  One lane per (b, t) cell,
+ * no workspace.  The caller keeps every word within max_len - 1 code points (dig_amd.datasets.LabelEncoder raises otherwise); a longer
+ * (or negative) range is clamped to [0, max_len - 1] in the kernel, so a row always ends in `eos` and no cell outside labels is touched.
+ * Null pointer, max_len < 1 or B < 0: DIG_ERR_ARG; B == 0: DIG_OK without a launch; B * max_len above 2^31 - 1: DIG_ERR_UNSUPPORTED. */
+int dig_encode_labels(const int* chars, const int* offsets, const int* class_of, int eos, int padding, int unknown, int max_len, int B,
+                      long long* labels, long long* lens, hipStream_t stream);
 
 /* ---- greedy decode with a K/V cache (models/decoder.py:173-252, models/transformer_layer.py:238-281)
  * One decode step of TFDecoder.forward_test per call sequence: dig_decode_embed (token embedding + position row t), then per
