@@ -1,9 +1,9 @@
 """Benchmark of the fine-tune training step (BASELINE config 5) in the format of bench.py.
 
-    python bench_finetune.py --gpus 1 --steps K --warmup W [--decoder tf_decoder|attention] [--no-drop]
+    python bench_finetune.py --gpus 1 --steps K --warmup W [--decoder tf_decoder|attention|ctc] [--no-drop]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench_finetune.py --gpus N ...
 
-One "step" = forward (teacher forcing) + SeqCrossEntropyLoss + backward + gradient all-reduce + AdamW with layer-wise lr decay 0.75 of
+One "step" = forward (teacher forcing) + SeqCrossEntropyLoss (SeqCTCLoss for `ctc`) + backward + gradient all-reduce + AdamW with layer-wise lr decay 0.75 of
 `simmim_vit_small_patch4_32x128` + the recognition decoder on a synthetic batch of 256 crops per GPU (97 classes, 25 positions), with
 the README regularisers (`--drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1`, decoder dropout 0.1) unless --no-drop; inputs resident in
 HBM.  Prints ONE JSON line (rank 0) with the same `roofline` / `cpu_baseline` objects as bench.py (the headline benchmark of the
@@ -54,6 +54,18 @@ def cpu_baseline(decoder, budget_s):
         def step(i):
             _, grads, _ = F.loss_and_grads(P, ecfg, c, images, tg, lens)
             F.adamw_step(P, grads, state, i + 1, 1e-4, groups)
+    elif decoder == "ctc":
+        # the CTC head's specification in plain torch (the head on the oracle's encoder, F.ctc_loss summed / B) lives with the tests
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import ctc_model as S
+        import finetune_oracle as F
+        P = S.state(ecfg, 97, 1, 2)
+        groups = F.param_groups(P, ecfg.depth, 0.75, 0.05)
+        state = {}
+
+        def step(i):
+            _, grads, _ = S.loss_and_grads(P, ecfg, images, tg, lens, 97)
+            F.adamw_step(P, grads, state, i + 1, 1e-4, groups)
     else:
         import attn_decoder_oracle as A
         import finetune_oracle as F
@@ -84,7 +96,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="crops per GPU")
-    ap.add_argument("--decoder", default="tf_decoder", choices=["tf_decoder", "attention"])
+    ap.add_argument("--decoder", default="tf_decoder", choices=["tf_decoder", "attention", "ctc"])
     ap.add_argument("--no-drop", action="store_true", help="every drop rate 0 (the deterministic step)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
@@ -93,6 +105,7 @@ def main():
     import dig_amd.utils as U
     from dig_amd.finetune import RecModelTrain, SeqCrossEntropyLoss, LayerDecayValueAssigner, create_optimizer, FlatGradComm
     from dig_amd.attn_recognizer import AttnRecModelTrain
+    from dig_amd.ctc_recognizer import CTCRecModelTrain, SeqCTCLoss
 
     sys.stdout.flush()
     saved_fd1 = os.dup(1)
@@ -112,7 +125,8 @@ def main():
     margs = types.SimpleNamespace(model="simmim_vit_small_patch4_32x128", decoder_name="tf_decoder", nb_classes=97, max_len=25, drop=p,
                                   attn_drop_rate=p, drop_path=p, opt="adamw", lr=1e-4 * B * world / 256, weight_decay=0.05, opt_eps=1e-8,
                                   opt_betas=[0.9, 0.999])
-    model = RecModelTrain(margs, decoder_dropout=p) if a.decoder == "tf_decoder" else AttnRecModelTrain(margs)
+    model = (RecModelTrain(margs, decoder_dropout=p) if a.decoder == "tf_decoder" else
+             AttnRecModelTrain(margs) if a.decoder == "attention" else CTCRecModelTrain(margs))
     model.to(dev)
     model.train()
     if world > 1:
@@ -122,7 +136,7 @@ def main():
     opt = create_optimizer(margs, model, get_num_layer=asg.get_layer_id, get_layer_scale=asg.get_scale)
     for grp in opt.param_groups:
         grp["lr"] = margs.lr * grp["lr_scale"]
-    crit, scaler = SeqCrossEntropyLoss(), U.NativeScalerWithGradNormCount()
+    crit, scaler = (SeqCTCLoss(model.blank) if a.decoder == "ctc" else SeqCrossEntropyLoss()), U.NativeScalerWithGradNormCount()
     batches = [synth(B, 25, dev, 1234 + rank + 100 * i) for i in range(4)]
 
     def run(n, start):
@@ -180,12 +194,14 @@ def main():
         torch.distributed.destroy_process_group()
     if rank != 0:
         return
-    head = "tf_decoder (6 layers, d 512, 8 heads)" if a.decoder == "tf_decoder" else "GRU attention head (sDim = attDim = 512)"
+    head = {"tf_decoder": "tf_decoder (6 layers, d 512, 8 heads)", "attention": "GRU attention head (sDim = attDim = 512)",
+            "ctc": "CTC head (32 column means, Linear 512, LayerNorm + GELU, Linear 98)"}[a.decoder]
+    crit_name = "SeqCTCLoss" if a.decoder == "ctc" else "SeqCrossEntropyLoss"
     regs = "all drop rates 0" if a.no_drop else "--drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1" + (", decoder dropout 0.1" if a.decoder == "tf_decoder" else "")
     line = {"metric": "fine-tune images/sec (32x128 crops, 97 classes, 25 positions) ViT-S/4 + recognition decoder", "value": a.steps * B * world / dt,
             "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": f"simmim_vit_small_patch4_32x128 + {head}: train_class_batch + SeqCrossEntropyLoss + backward + AdamW (layer decay "
+            "config": {"workload": f"simmim_vit_small_patch4_32x128 + {head}: train_class_batch + {crit_name} + backward + AdamW (layer decay "
                                    f"0.75), {regs}, {B} crops/GPU, random-init weights", "global_batch": B * world, "parallelism": f"dp{world}",
                        "loss": loss_value},
             "roofline": roof}

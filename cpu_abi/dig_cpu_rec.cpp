@@ -839,4 +839,145 @@ int dig_embed_rows(const long long* tokens, const float* table, void* out_, int 
   return DIG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- CTC head (csrc/ctc.hip)
+// The textbook recursions over the 2n + 1 states of the extended label sequence, in double and in log space (the device works in fp32
+// re-centred every step: fp32 round-off class).
+static int ctc_check(const void* logits, int ld, const void* target, int ldt, const void* target_len, int B, int T, int C, int blank) {
+  if (!logits || !target || !target_len || B < 0 || T <= 0 || C <= 0 || ldt <= 0 || ld < C || blank < 0 || blank >= C) return DIG_ERR_ARG;
+  if (T > 64 || C < 2 || C > 256 || ldt > 63) return DIG_ERR_UNSUPPORTED;
+  return DIG_OK;
+}
+
+static double ctc_lse(double a, double b) {
+  const double m = std::max(a, b);
+  if (m == -std::numeric_limits<double>::infinity()) return m;
+  return m + std::log(std::exp(a - m) + std::exp(b - m));
+}
+
+// Sample b: its extended sequence ext (2n + 1 states), the log-softmax lp [T][C] and alpha [T][S]; returns false for a sample that
+// counts as nll = 0 (no alignment, or a label that is no class / the blank).
+static bool ctc_forward(const float* x, int ld, const long long* tgt, long long tl, int ldt, int T, int C, int blank, std::vector<int>& ext,
+                        std::vector<double>& lp, std::vector<double>& alpha, double& logp) {
+  const double NINF = -std::numeric_limits<double>::infinity();
+  const int n = (int)std::clamp(tl, 0LL, (long long)ldt);
+  int rep = 0;
+  for (int i = 0; i < n; ++i) {
+    if (tgt[i] < 0 || tgt[i] >= C || tgt[i] == blank) return false;
+    if (i && tgt[i] == tgt[i - 1]) ++rep;
+  }
+  if (n + rep > T) return false;
+  const int S = 2 * n + 1;
+  ext.assign(S, blank);
+  for (int i = 0; i < n; ++i) ext[2 * i + 1] = (int)tgt[i];
+  lp.assign((size_t)T * C, 0.0);
+  for (int t = 0; t < T; ++t) {
+    const float* row = x + (size_t)t * ld;
+    double m = row[0], s = 0.0;
+    for (int c = 1; c < C; ++c) m = std::max(m, (double)row[c]);
+    for (int c = 0; c < C; ++c) s += std::exp((double)row[c] - m);
+    const double l = m + std::log(s);
+    for (int c = 0; c < C; ++c) lp[(size_t)t * C + c] = (double)row[c] - l;
+  }
+  alpha.assign((size_t)T * S, NINF);
+  alpha[0] = lp[blank];
+  if (n) alpha[1] = lp[ext[1]];
+  for (int t = 1; t < T; ++t)
+    for (int s = 0; s < S; ++s) {
+      double a = alpha[(size_t)(t - 1) * S + s];
+      if (s >= 1) a = ctc_lse(a, alpha[(size_t)(t - 1) * S + s - 1]);
+      if (s >= 2 && (s & 1) && ext[s] != ext[s - 2]) a = ctc_lse(a, alpha[(size_t)(t - 1) * S + s - 2]);
+      alpha[(size_t)t * S + s] = a + lp[(size_t)t * C + ext[s]];
+    }
+  logp = alpha[(size_t)(T - 1) * S + S - 1];
+  if (n) logp = ctc_lse(logp, alpha[(size_t)(T - 1) * S + S - 2]);
+  return logp > NINF && logp == logp;
+}
+
+int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
+                 int C, int blank, float* nll, float* loss, hipStream_t) {
+  if (!nll || !loss) return DIG_ERR_ARG;
+  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
+  if (rc != DIG_OK || B == 0) return rc;
+  std::vector<int> ext;
+  std::vector<double> lp, alpha;
+  double total = 0.0;
+  for (int b = 0; b < B; ++b) {
+    double logp = 0.0;
+    const bool ok = ctc_forward(logits + (size_t)b * T * ld, ld, target + (size_t)b * ldt, target_len[b] - (long long)len_offset, ldt, T, C, blank,
+                                ext, lp, alpha, logp);
+    nll[b] = ok ? (float)(-logp) : 0.f;
+    total += (double)nll[b];
+  }
+  loss[0] = (float)(total / (double)B);
+  return DIG_OK;
+}
+
+int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset,
+                     const float* gscalar, int B, int T, int C, int blank, void* dlogits, int ldd, int dlogits_is_f32, hipStream_t) {
+  if (!dlogits || ldd < C) return DIG_ERR_ARG;
+  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
+  if (rc != DIG_OK || B == 0) return rc;
+  const double NINF = -std::numeric_limits<double>::infinity();
+  const float sc = (gscalar ? gscalar[0] : 1.f) * (1.0f / (float)B);
+  std::vector<int> ext;
+  std::vector<double> lp, alpha, beta, occ;
+  for (int b = 0; b < B; ++b) {
+    float* d32 = (float*)dlogits + (size_t)b * T * ldd;
+    bf16_t* d16 = (bf16_t*)dlogits + (size_t)b * T * ldd;
+    double logp = 0.0;
+    const bool ok = ctc_forward(logits + (size_t)b * T * ld, ld, target + (size_t)b * ldt, target_len[b] - (long long)len_offset, ldt, T, C, blank,
+                                ext, lp, alpha, logp);
+    const int S = (int)ext.size();
+    if (ok) {
+      beta.assign((size_t)T * S, NINF);
+      beta[(size_t)(T - 1) * S + S - 1] = lp[(size_t)(T - 1) * C + blank];
+      if (S > 1) beta[(size_t)(T - 1) * S + S - 2] = lp[(size_t)(T - 1) * C + ext[S - 2]];
+      for (int t = T - 2; t >= 0; --t)
+        for (int s = 0; s < S; ++s) {
+          double a = beta[(size_t)(t + 1) * S + s];
+          if (s + 1 < S) a = ctc_lse(a, beta[(size_t)(t + 1) * S + s + 1]);
+          if (s + 2 < S && (s & 1) && ext[s] != ext[s + 2]) a = ctc_lse(a, beta[(size_t)(t + 1) * S + s + 2]);
+          beta[(size_t)t * S + s] = a + lp[(size_t)t * C + ext[s]];
+        }
+    }
+    for (int t = 0; t < T; ++t) {
+      occ.assign(C, 0.0);
+      if (ok)
+        for (int s = 0; s < S; ++s) {
+          const double v = alpha[(size_t)t * S + s] + beta[(size_t)t * S + s];
+          if (v > NINF) occ[ext[s]] += std::exp(v - lp[(size_t)t * C + ext[s]] - logp);
+        }
+      for (int c = 0; c < ldd; ++c) {
+        const float v = (ok && c < C) ? sc * (float)(std::exp(lp[(size_t)t * C + c]) - occ[c]) : 0.f;
+        if (dlogits_is_f32) d32[(size_t)t * ldd + c] = v; else d16[(size_t)t * ldd + c] = f2bf(v);
+      }
+    }
+  }
+  return DIG_OK;
+}
+
+int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids, float* score,
+                          int* n, hipStream_t) {
+  if (!logits || !ids || !score || !n || B < 0 || T <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
+  if (T > 64 || C < 2 || C > 256) return DIG_ERR_UNSUPPORTED;
+  for (int b = 0; b < B; ++b) {
+    long long* idr = ids + (size_t)b * (T + 1);
+    float* scr = score + (size_t)b * (T + 1);
+    int cnt = 0, prev = -1;
+    for (int t = 0; t < T; ++t) {
+      const float* row = logits + ((size_t)b * T + t) * ld;
+      int am = 0;
+      for (int c = 1; c < C; ++c)
+        if (row[c] > row[am]) am = c;                                  // (the first maximum: the lowest id on a tie)
+      float e = 0.f;
+      for (int c = 0; c < C; ++c) e += std::exp(row[c] - row[am]);
+      if (am != blank && am != eos && !(t > 0 && am == prev)) { idr[cnt] = am; scr[cnt] = 1.f / e; ++cnt; }
+      prev = am;
+    }
+    for (int j = cnt; j <= T; ++j) { idr[j] = j == cnt ? eos : padding; scr[j] = 1.f; }
+    n[b] = cnt;
+  }
+  return DIG_OK;
+}
+
 }  // extern "C"

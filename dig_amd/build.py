@@ -96,7 +96,9 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                # the lexicon search of the evaluation metrics (metrics.hip): its DP row is in LDS, the rest in registers
                "lexicon_search_kernel",
                # the folded text-conditional cross-attention (text_cond_attn.hip): u / dc / the accumulators of a query row stay in registers
-               "tcv_fwd_kernel", "tcv_bwd_q_kernel", "tcv_bwd_k_kernel")
+               "tcv_fwd_kernel", "tcv_bwd_q_kernel", "tcv_bwd_k_kernel",
+               # the CTC criterion and its gradient (ctc.hip): a lane's two states stay in registers, emissions / alphas / occupancies in LDS
+               "ctc_kernel<false>", "ctc_kernel<true>")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

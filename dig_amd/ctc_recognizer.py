@@ -1,0 +1,223 @@
+"""`CTCRecModel` on the MI355X -- SURVEY.md 8(f) row N1, the third recognition head (`--decoder_type ctc`): the fine-tune encoder, the
+mean over the 8 rows of the token grid, and a per-column classifier over nb_classes + 1 symbols (the last one the CTC blank).
+
+Mirrored from the reference: the model (models/model_builder.py:8-38: `encoder`, then `ctc_classifier` = Linear(D, 512), LayerNorm(512,
+eps 1e-6), GELU, Linear(512, nb_classes + 1) on `enc_x.view(B, 8, 32, D).mean(1)`; state-dict keys `encoder.*`,
+`ctc_classifier.{0,1,3}.{weight,bias}`; PyTorch's default initialisation; `no_weight_decay` / `get_num_layers`) and the string rule
+(`ctc_get_str_list`, evaluation_metric/metrics.py:205-244, blank = len(classes)).  The reference's `main` raises for this model and has no
+criterion for it, so these are this project's own definitions: the criterion is the standard CTC loss summed over the samples and divided
+by B (the `sample_normalize` convention of SeqCrossEntropyLoss), with `zero_infinity`; the labels of a target row are its cells in front of
+EOS (`len_offset` = 1 on the datasets' lengths, which count EOS); `decode` returns decoder-shaped rows (emitted classes, EOS, PADDING) with the
+emitting frames' softmax probabilities as scores.
+
+Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head is
+`dig_window_pool_*` (the `--use_1d_attdec` pooling), two GEMMs and the fused LayerNorm + GELU launch; loss, gradient and decode are
+csrc/ctc.hip.  There is no CPU fallback."""
+import torch
+
+from . import _lib as L
+from . import ops
+from .arena import encoder_shapes
+from .finetune import RecModelTrain, _TrainStep, CLS_PAD, encoder_plan
+from .recognizer import ENCODERS
+
+BF16, F32 = torch.bfloat16, torch.float32
+PRE = "ctc_classifier."
+D_EMBEDDING = 512                                       # model_builder.py:13
+
+
+# ---------------------------------------------------------------------------------------------- the three entry points
+def ctc_loss(logits, C, target, length, blank, len_offset=1):
+    """dig_ctc_loss on logits fp32 [B, T, ld >= C]: (nll [B], loss [1])."""
+    B, T, ld = logits.shape
+    nll = torch.empty(B, device=logits.device, dtype=F32)
+    loss = torch.empty(1, device=logits.device, dtype=F32)
+    L.call("dig_ctc_loss", L.ptr(logits), ld, L.ptr(target), target.shape[1], L.ptr(length), len_offset, B, T, C, blank, L.ptr(nll), L.ptr(loss),
+           L.stream())
+    return nll, loss
+
+
+def ctc_loss_bwd(logits, C, target, length, blank, len_offset=1, gscalar=None, ldd=None, f32=False, out=None):
+    """dig_ctc_loss_bwd: d loss / d logits * gscalar as [B, T, ldd] rows (bf16, or fp32 with f32), pad columns zero."""
+    B, T, ld = logits.shape
+    ldd = C if ldd is None else ldd
+    dl = torch.empty((B, T, ldd), device=logits.device, dtype=F32 if f32 else BF16) if out is None else out
+    L.call("dig_ctc_loss_bwd", L.ptr(logits), ld, L.ptr(target), target.shape[1], L.ptr(length), len_offset, L.ptr(gscalar), B, T, C, blank,
+           L.ptr(dl), ldd, int(dl.dtype == F32), L.stream())
+    return dl
+
+
+def ctc_greedy_decode(logits, C, blank, eos, padding):
+    """dig_ctc_greedy_decode on logits fp32 [B, T, ld >= C]: (ids int64 [B, T + 1], score fp32 [B, T + 1], n int32 [B])."""
+    B, T, ld = logits.shape
+    dev = logits.device
+    ids = torch.empty((B, T + 1), device=dev, dtype=torch.int64)
+    score = torch.empty((B, T + 1), device=dev, dtype=F32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call("dig_ctc_greedy_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, L.ptr(ids), L.ptr(score), L.ptr(n), L.stream())
+    return ids, score, n
+
+
+def match_widths(pred, target, padding):
+    """Two [B, *] label tensors at one width (what dig_string_match and its kin compare): the narrower one padded with PADDING."""
+    target = target.to(pred.device).long()
+    wp, wt = pred.shape[1], target.shape[1]
+    if wp == wt:
+        return pred, target
+    wide = torch.full((pred.shape[0], max(wp, wt)), padding, device=pred.device, dtype=torch.int64)
+    if wp < wt:
+        wide[:, :wp] = pred
+        return wide, target
+    wide[:, :wt] = target
+    return pred, wide
+
+
+class _SeqCTCFn(torch.autograd.Function):
+    """The CTC launch and its gradient (fp32 rows, as wide as the logits)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, length, blank, len_offset):
+        x = logits.detach().float().contiguous()
+        _, loss = ctc_loss(x, x.shape[2], target, length, blank, len_offset)
+        ctx.save_for_backward(x, target, length)
+        ctx.cfg = (blank, len_offset)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, target, length = ctx.saved_tensors
+        gs = g.reshape(1).float().contiguous()                         # (named: a converted copy must outlive the call)
+        blank, len_offset = ctx.cfg
+        return ctc_loss_bwd(x, x.shape[2], target, length, blank, len_offset, gscalar=gs, f32=True), None, None, None, None
+
+
+class SeqCTCLoss(torch.nn.Module):
+    """The criterion of the CTC head: forward(logits [B, T, nb_classes + 1] fp32, target [B, max_len], length [B]) -> 0-dim loss =
+    sum_b -log p(labels_b | logits_b) / B with zero_infinity; the labels of row b are its first length[b] - len_offset cells (the datasets'
+    lengths count the closing EOS: len_offset = 1).  `blank` None: the last class of the logits."""
+
+    def __init__(self, blank=None, len_offset=1):
+        super().__init__()
+        self.blank, self.len_offset = blank, int(len_offset)
+
+    def forward(self, input, target, length):
+        blank = input.shape[-1] - 1 if self.blank is None else int(self.blank)
+        return _SeqCTCFn.apply(input, target.to(input.device).long().contiguous(), length.to(input.device).long().contiguous(), blank, self.len_offset)
+
+    def extra_repr(self):
+        return f"blank={self.blank}, len_offset={self.len_offset}"
+
+
+# ---------------------------------------------------------------------------------------------- the model
+class _CTCTrainStep(_TrainStep):
+    """Forward / backward of one CTCRecModel step."""
+
+    def head_forward(self, enc):
+        """ctc_classifier on the column means of the token grid: enc bf16 [B*256, D] -> logits fp32 [B*32, CLS_PAD] (columns past
+        nb_classes + 1: zero weights) and what the backward reads."""
+        M, p, w = self.m, self.p, self.w
+        B = enc.shape[0] // M.N
+        rows = B * M.gw
+        cols = torch.empty((rows, M.D), device=enc.device, dtype=BF16)
+        ops.window_pool_fwd(enc, cols, B, M.gh, M.gw, M.gw, M.D)
+        h = ops.linear_fwd(cols, w(PRE + "0.weight"), bias=p(PRE + "0.bias"))
+        a, mu, rs = ops.layernorm_fwd(h, p(PRE + "1.weight"), p(PRE + "1.bias"), 1e-6, gelu=True)
+        self.cls_w, cb = M.padded_classifier(PRE + "3.weight", PRE + "3.bias", CLS_PAD)
+        logits = torch.empty((rows, CLS_PAD), device=enc.device, dtype=F32)
+        ops.gemm(a, self.cls_w, rows, CLS_PAD, D_EMBEDDING, out=logits, out_kind=ops.OUT_F32, bias=cb)
+        return logits, (cols, h, mu, rs, a)
+
+    def forward(self, images, targets, lens):
+        M = self.m
+        enc = self.encoder_forward(images)
+        logits, self.saved = self.head_forward(enc)
+        C1 = M.nb_classes + 1
+        return logits[:, :C1].reshape(self.B, M.gw, C1)
+
+    def backward(self, dlogits_btc):
+        M = self.m
+        dev = dlogits_btc.device
+        main, sd = self.begin_backward(dev)
+        side, p, w, g = self.side, self.p, self.w, self.g
+        B, C1 = self.B, M.nb_classes + 1
+        rows = B * M.gw
+        cols, h, mu, rs, a = self.saved
+        dl = torch.zeros((rows, CLS_PAD), device=dev, dtype=BF16)
+        dl[:, :C1] = dlogits_btc.reshape(rows, C1).to(BF16)
+        side(lambda: ops.wgrad(dl, a, g(PRE + "3.weight"), C1, D_EMBEDDING, rows), dl, a)
+        cs = torch.zeros(CLS_PAD, device=dev, dtype=F32)
+        side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), g(PRE + "3.bias").add_(cs[:C1])), dl, cs)
+        da = ops.gemm(dl, self.cls_w, rows, D_EMBEDDING, CLS_PAD, tb=True)
+        dh = ops.layernorm_bwd(da, h, p(PRE + "1.weight"), p(PRE + "1.bias"), mu, rs, None, g(PRE + "1.weight"), g(PRE + "1.bias"), gelu=True)
+        side(lambda: ops.linear_wgrad(dh, cols, g(PRE + "0.weight")), dh, cols)
+        side(lambda: ops.colsum(dh, g(PRE + "0.bias")), dh)
+        dcols = ops.linear_dgrad(dh, w(PRE + "0.weight"))
+        denc = torch.empty((B * M.N, M.D), device=dev, dtype=BF16)          # every token of a column gets 1/gh of the column's gradient
+        ops.window_pool_bwd(dcols, denc, B, M.gh, M.gw, M.gw, M.D, False)
+        self.encoder_backward(denc)
+        main.wait_stream(sd)
+
+
+class CTCRecModelTrain(RecModelTrain):
+    """models.model_builder.CTCRecModel: `.train()` forward = (logits [B, 32, nb_classes + 1] fp32, None, None, None) with autograd,
+    `.eval()` forward = the same logits from the walk without dropout; `decode(logits)` = the greedy CTC strings as decoder-shaped rows."""
+    _step_cls = _CTCTrainStep
+    is_ctc = True
+
+    def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, nb_classes=97, max_len=25, drop_rate=None, attn_drop_rate=None,
+                 drop_path_rate=None, drop_seed=None):
+        if args is not None:
+            embed_dim, num_heads = ENCODERS[args.model]
+            nb_classes, max_len = args.nb_classes, args.max_len
+            drop_rate = float(getattr(args, "drop", 0.0)) if drop_rate is None else drop_rate
+            attn_drop_rate = float(getattr(args, "attn_drop_rate", 0.0)) if attn_drop_rate is None else attn_drop_rate
+            drop_path_rate = float(getattr(args, "drop_path", 0.0)) if drop_path_rate is None else drop_path_rate
+        if nb_classes + 1 > CLS_PAD:
+            raise NotImplementedError(f"nb_classes + 1 above {CLS_PAD}: the classifier is padded to {CLS_PAD} rows")
+        if nb_classes < 3:
+            raise ValueError("nb_classes counts EOS, PADDING and UNKNOWN, the last three classes of a vocabulary")
+        super().__init__(None, embed_dim=embed_dim, depth=depth, num_heads=num_heads, n_layers=0, d_model=D_EMBEDDING, n_head=1, d_k=64, d_inner=0,
+                         nb_classes=nb_classes, max_len=max_len, drop_rate=drop_rate or 0.0, attn_drop_rate=attn_drop_rate or 0.0,
+                         drop_path_rate=drop_path_rate or 0.0, decoder_dropout=0.0, drop_seed=drop_seed)
+        self.blank = nb_classes                                             # blank_label = len(classes) (metrics.py:211)
+        self.eos, self.padding = nb_classes - 3, nb_classes - 2             # a vocabulary ends in EOS, PADDING, UNKNOWN (datasets.find_classes)
+        self.beam_width = 0
+
+    def param_shapes(self):
+        o = encoder_shapes("encoder.", self.D, self.F, self.depth, True)
+        o[PRE + "0.weight"] = (D_EMBEDDING, self.D); o[PRE + "0.bias"] = (D_EMBEDDING,)
+        o[PRE + "1.weight"] = (D_EMBEDDING,); o[PRE + "1.bias"] = (D_EMBEDDING,)
+        o[PRE + "3.weight"] = (self.nb_classes + 1, D_EMBEDDING); o[PRE + "3.bias"] = (self.nb_classes + 1,)
+        return o
+
+    def _init_tensor(self, k, shp):
+        """Head: PyTorch defaults (CTCRecModel applies no init of its own): nn.Linear U(+-1/sqrt(fan_in)), nn.LayerNorm (1, 0)."""
+        if k.startswith(PRE + "1."):
+            return torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
+        return super()._init_tensor(k, shp)
+
+    @torch.no_grad()
+    def logits(self, images):
+        """The eval forward: the training step's walk without dropout keys (and, like it, with the blocks' activations kept)."""
+        dev = images.device
+        if self._dev != dev or self._shadow is None:
+            self._bind(dev)
+        step = _CTCTrainStep(self)
+        self.refresh_shadow()
+        B = images.shape[0]
+        enc, _ = self.encoder_front(images, encoder_plan(self, B * self.N), True, frozen=self.frozen_blocks)
+        C1 = self.nb_classes + 1
+        return step.head_forward(enc)[0][:, :C1].reshape(B, self.gw, C1)
+
+    def decode(self, logits):
+        """(ids int64 [B, 33], score fp32 [B, 33], n int32 [B]) of logits [B, 32, nb_classes + 1]: csrc/ctc.hip's greedy rule."""
+        x = logits.detach().float().contiguous()
+        return ctc_greedy_decode(x, x.shape[2], self.blank, self.eos, self.padding)
+
+    def forward(self, x):
+        if self.training:
+            return super().forward(x)
+        images = x[0] if isinstance(x, (tuple, list)) else x
+        if not images.is_cuda:
+            raise RuntimeError("dig_amd.CTCRecModelTrain runs on an MI355X (cuda device) only; there is no CPU fallback")
+        return self.logits(images), None, None, None

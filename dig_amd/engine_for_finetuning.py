@@ -1,7 +1,8 @@
 """The reference's fine-tune engine (engine_for_finetuning.py) on the MI355X, same signatures, meter names and return values.
 
 `evaluate()` (:214-285): greedy decode through `dig_amd.recognizer.RecModel`, SeqCrossEntropyLoss, string accuracy and character
-F-measure all on the device; one host read per batch.
+F-measure all on the device; one host read per batch.  A CTC model (`is_ctc`, dig_amd/ctc_recognizer.py) is scored on `model.decode(logits)`
+-- the collapsed frames as decoder-shaped rows -- under SeqCTCLoss, in both functions; every other model takes the lines it always took.
 `train_one_epoch()` (:54-210) with `train_class_batch` (:26-46) for the torch.amp branch (`loss_scaler` given): per-step lr / weight
 decay from the schedules times each group's `lr_scale`, teacher-forced forward, SeqCrossEntropyLoss, backward + grad norm + fused
 AdamW through the scaler object, gradient accumulation (`update_freq`), class accuracy of the arg-max, evaluation every
@@ -15,6 +16,7 @@ import torch
 
 from . import utils
 from .evaluation_metric import edit_distances
+from .ctc_recognizer import SeqCTCLoss, match_widths
 from .recognizer import SeqCrossEntropyLoss, accuracy, recognition_f_measure
 
 
@@ -98,7 +100,12 @@ def train_one_epoch(model: torch.nn.Module, criterion: torch.nn.Module, data_loa
             if model_ema is not None:
                 model_ema.update(core)                                          # engine_for_finetuning.py:136-139
         loss_scale_value = loss_scaler.state_dict()["scale"]
-        acc = accuracy(output.detach().argmax(-1), targets, voc) if voc is not None else None
+        if voc is None:
+            acc = None
+        elif getattr(core, "is_ctc", False):                                    # the CTC head: frames -> collapsed rows, targets at their width
+            acc = accuracy(*match_widths(core.decode(output)[0], targets, core.padding), voc)
+        else:
+            acc = accuracy(output.detach().argmax(-1), targets, voc)
         dev_vals = torch.stack([loss_report.reshape(()).float(), acc.float() if acc is not None else torch.zeros((), device=loss_report.device),
                                 grad_norm.detach().reshape(()).float() if isinstance(grad_norm, torch.Tensor)
                                 else torch.zeros((), device=loss_report.device)])
@@ -143,7 +150,8 @@ def _vocabulary(dataset):
 @torch.no_grad()
 def evaluate(data_loader, model, device, args=None):
     beam = int(getattr(args, "beam_width", 0) or 0)                                  # engine_for_finetuning.py:246-256: with beam search the model
-    criterion = SeqCrossEntropyLoss()                                               # returns token ids, the loss meter reads 0
+    ctc = bool(getattr(model, "is_ctc", False))                                      # returns token ids, the loss meter reads 0
+    criterion = SeqCTCLoss(model.blank) if ctc else SeqCrossEntropyLoss()
     metric_logger = utils.MetricLogger(delimiter="  ")
     header = 'Test:'
     model.eval()
@@ -158,6 +166,9 @@ def evaluate(data_loader, model, device, args=None):
             if getattr(model, "beam_width", 0) != beam:
                 raise RuntimeError(f"args.beam_width={beam} but the model was built with beam_width={getattr(model, 'beam_width', 0)}")
             loss, pred_ids = torch.zeros((), device=output.device), output
+        elif ctc:
+            loss = criterion(output, target, lens)                               # (on the frames' logits)
+            pred_ids, target = match_widths(model.decode(output)[0], target, model.padding)
         else:
             loss = criterion(output, target, lens)                               # (on probabilities, as the reference does: :249)
             pred_ids = output.argmax(-1)

@@ -16,8 +16,12 @@ word; accuracy then tests raw word == normalised target (a lexicon word with an 
 the edit distance is taken between the raw word and the normalised target; a lexicon level reports 0 when `file_names` is empty or the
 lexicon of `file_names[0]` is empty -- only the first file name is looked at, and an empty lexicon further down raises as np.argmin does.
 
-Two keys of the reference's factory are left out: `ctc_accuracy` and `multi_label_fmeasure`.  Neither can be reached there (no model of the
-reference emits CTC frames or multi-label outputs for them), and CTC / multi-label metrics are not built here."""
+`ctc_get_str_list` and `CTCAccuracy` (metrics.py:205-251) are module functions with the reference's signatures: `output` is the per-frame
+arg-max [B, T] of the CTC head (dig_amd/ctc_recognizer.py), collapsed by the device rule of `dig_ctc_greedy_decode` into decoder-shaped rows,
+which `dig_string_match` / `dig_tokens_to_text` then read like any other prediction; a target narrower than T + 1 is padded with PADDING.
+
+Two keys of the reference's factory are left out of `factory()`: `ctc_accuracy` (the function is here, as `CTCAccuracy`; the five keys are what
+the reference's fine-tune path can reach) and `multi_label_fmeasure` (no model emits multi-label outputs; not built)."""
 import string
 
 import numpy as np
@@ -242,6 +246,47 @@ def RecPostProcess(output, target, score, dataset=None):
     p, pl, t, tl, c = host[:B * T], host[B * T:B * T + B], host[B * T + B:2 * B * T + B], host[2 * B * T + B:2 * B * T + 2 * B], host[2 * B * T + 2 * B:]
     strs = lambda cells, lens: ["".join(chr(int(v)) for v in cells[b * T:b * T + int(lens[b])]) for b in range(B)]
     return strs(p, pl), strs(t, tl), c
+
+
+def _ctc_rows(output, target, dataset):
+    """The per-frame arg-max [B, T] of a CTC head as decoder-shaped rows: the device rule of dig_ctc_greedy_decode (csrc/ctc.hip) on
+    one-hot logits over len(voc) + 1 classes (blank = len(voc), metrics.py:211), and the targets at the same width (padded with PADDING on
+    the host side).  Returns (ids, targets, voc)."""
+    from .ctc_recognizer import ctc_greedy_decode, match_widths
+    assert output.dim() == 2 and target.dim() == 2 and output.shape[0] == target.shape[0]
+    voc = _voc(dataset)
+    C = len(voc) + 1
+    frames = output.long()
+    if bool(((frames < 0) | (frames >= C)).any()):
+        raise ValueError(f"frame classes outside [0, {C}): the blank is class {C - 1}")
+    onehot = torch.zeros(frames.shape + (C,), device=frames.device, dtype=torch.float32)
+    onehot.scatter_(2, frames.unsqueeze(-1), 1.0)
+    ids, _, _ = ctc_greedy_decode(onehot, C, C - 1, voc.index("EOS"), voc.index("PADDING"))
+    ids, targ = match_widths(ids, target, voc.index("PADDING"))
+    return ids, targ, voc
+
+
+def ctc_get_str_list(output, target, dataset=None):
+    """metrics.py:205-244: (pred_list, targ_list) of normalised strings; `output` = the per-frame arg-max [B, T] of a CTC head."""
+    ids, targ, voc = _ctc_rows(output, target, dataset)
+    pred, pred_len = tokens_to_text(ids, voc)
+    t, t_len = tokens_to_text(targ, voc)
+    B, T = pred.shape
+    host = torch.cat([pred.reshape(-1), pred_len, t.reshape(-1), t_len]).tolist()                      # the one host read
+    p, pl, tt, tl = host[:B * T], host[B * T:B * T + B], host[B * T + B:2 * B * T + B], host[2 * B * T + B:]
+    strs = lambda cells, lens: ["".join(chr(int(v)) for v in cells[b * T:b * T + int(lens[b])]) for b in range(B)]
+    return strs(p, pl), strs(tt, tl)
+
+
+def CTCAccuracy(output, target, dataset=None):
+    """metrics.py:246-251."""
+    ids, targ, voc = _ctc_rows(output, target, dataset)
+    B, T = ids.shape
+    canon = recognizer.class_canon(voc).to(ids.device)
+    match = torch.empty(B, device=ids.device, dtype=torch.uint8)
+    ids, targ = ids.contiguous(), targ.contiguous()
+    L.call("dig_string_match", L.ptr(ids), L.ptr(targ), L.ptr(canon), len(voc), voc.index("EOS"), B, T, L.ptr(match), L.stream())
+    return 1.0 * int(match.sum().item()) / B                                   # (the count divided on the host, in double as the reference does)
 
 
 __factory = {

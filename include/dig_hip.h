@@ -612,6 +612,33 @@ int dig_seq_ls_cross_entropy(const float* input, const long long* target, const 
 int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar, int B,
                                  int T, int C, float smoothing, void* dlogits, int ldd, hipStream_t stream);
 
+/* ---- the CTC recognition head (`--decoder_type ctc`, models/model_builder.py:8-38; csrc/ctc.hip).  The reference has the model and the
+ * string rule (ctc_get_str_list, evaluation_metric/metrics.py:205-244) but no criterion: the loss is the standard CTC loss, defined here.
+ * Logits: fp32 rows (b, t) of ld >= C columns, columns [C, ld) never read; C counts the blank, 0 <= blank < C.  target: [B][ldt] int64,
+ * target_len: [B] int64; the label count of sample b is n_b = target_len[b] - len_offset clamped to [0, ldt] (the recognition datasets'
+ * rows end in EOS, which is no CTC label: the model passes len_offset = 1).
+ *   dig_ctc_loss: nll[b] = -log p(labels_b | frames 0..T-1) over the log-softmax of each frame's C logits (the alpha recursion),
+ *     loss[0] = sum_b nll[b] / B (the sample_normalize convention of dig_seq_cross_entropy, not torch's per-label mean).  zero_infinity:
+ *     a sample without a valid alignment (n_b + the number of adjacent equal labels > T) has nll = 0, and so has a sample holding a label
+ *     outside [0, C) or equal to `blank`; no index is formed from such a label.
+ *   dig_ctc_loss_bwd: dlogits = d loss / d logits * gscalar[0] (device scalar, null = 1) = gscalar / B * (softmax - posterior occupancy of
+ *     the class), alpha and beta recomputed in the launch; zero rows for the nll = 0 samples; columns [C, ldd) written as zeros; bf16
+ *     rows, or fp32 with dlogits_is_f32 (the bf16 form is the fp32 one rounded to nearest even).  No floating-point atomics: two launches
+ *     on the same inputs give the same bits.
+ *   dig_ctc_greedy_decode: per frame the arg-max class (lowest id on a tie); a frame emits its class when it is not `blank`, differs from
+ *     the previous frame's arg-max and is not `eos` (metrics.py:220-227).  ids [B][T+1] int64 = the emitted classes, then `eos`, then
+ *     `padding`: a row reads like a decoder's output (dig_string_match, dig_tokens_to_text, ... take it unchanged).  score [B][T+1] fp32 =
+ *     the softmax probability of the emitting frame's class, then 1.0 (RecPostProcess multiplies score[:len+1]); n [B] int32 = the
+ *     number of emitted classes.
+ * Null pointer, non-positive dimension, B < 0, ld or ldd < C, blank outside [0, C): DIG_ERR_ARG.  Outside 1 <= T <= 64, 2 <= C <= 256,
+ * ldt <= 63: DIG_ERR_UNSUPPORTED.  B == 0: DIG_OK without a launch. */
+int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
+                 int C, int blank, float* nll, float* loss, hipStream_t stream);
+int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset,
+                     const float* gscalar, int B, int T, int C, int blank, void* dlogits, int ldd, int dlogits_is_f32, hipStream_t stream);
+int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids, float* score,
+                          int* n, hipStream_t stream);
+
 /* ---- dropout / stochastic depth of the fine-tune step (README.md:100-118: --drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1; the
  * recognition decoder's hard-wired dropout = 0.1, models/decoder.py:141).  Replaces nn.Dropout (modeling_finetune.py:51,83-85,271;
  * models/transformer_layer.py:236-237,394; models/decoder.py:160) and timm drop_path (modeling_finetune.py:37).

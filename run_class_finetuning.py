@@ -9,7 +9,7 @@ this file, with `--data_path` / `--eval_data_path` pointed at `synthetic` or a d
 
 What it keeps of run_class_finetuning.py:258-640 (`main`): distributed init from the launcher's environment, per-rank seeding (:271-274),
 the train / evaluation datasets, samplers and loaders (:285-334: DistributedSampler(shuffle=True) + drop_last for training, batches of
-int(1.5 * batch_size) in order or sharded by --dist_eval for evaluation), `RecModel` or `AttnRecModel` by --decoder_type (:350-355),
+int(1.5 * batch_size) in order or sharded by --dist_eval for evaluation), `RecModel`, `AttnRecModel` or `CTCRecModel` by --decoder_type (:350-355),
 args.window_size / args.patch_size (:357-360), the --finetune load (:362-440: --model_key search, `head.*` removal, `backbone.` strip,
 non-strict load under --model_prefix with the missing / unexpected report), --model_ema (:446-454), lr = lr * total batch / 256 (:462-464),
 layer-wise lr decay, the no-weight-decay list and --fixed_encoder_layers (:471-521), the step-level cosine lr / weight-decay schedules
@@ -33,6 +33,10 @@ What is different, on purpose:
   * flags whose code path the reference never reaches are accepted and reported; flags that select what is not built (deepspeed, the
     sequential cls token, semantic insertion, w2v targets, the contrastive centre loss, the decoupled decoder, the ImageNet / CIFAR / folder
     datasets, inputs other than 32 x 128) say so and stop;
+  * `--decoder_type ctc`: the reference's help text promises it and models/model_builder.py has `CTCRecModel`, but its `main` raises for it and
+    has no criterion.  Here it builds `CTCRecModelTrain` under `SeqCTCLoss` whatever --smoothing says (reported once when --smoothing > 0 is
+    ignored); --beam_width > 0, --text_cond_vis and --use_1d_attdec stop with it (dig_amd/ctc_recognizer.py says what is mirrored and what is
+    this project's own definition);
   * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`).
 
 Multi-rank runs are wired (samplers, FlatGradComm, the meters' all-reduce) but only the single-rank path is tested."""
@@ -76,7 +80,7 @@ def get_args(argv=None):
     # model
     a("--model", default="deit_base_patch16_224", type=str, help="one of " + ", ".join(MODELS))
     a("--decoder_name", default="tf_decoder", type=str)
-    a("--decoder_type", default="tf_decoder", type=str, help="tf_decoder (RecModel) or attention (AttnRecModel)")
+    a("--decoder_type", default="tf_decoder", type=str, help="tf_decoder (RecModel), attention (AttnRecModel) or ctc (CTCRecModel)")
     a("--insert_sem", action="store_true", default=False)
     a("--text_cond_vis", action="store_true", default=False)
     a("--input_h", default=32, type=int)
@@ -184,8 +188,16 @@ def refuse_unbuilt(args):
         raise SystemExit("--use_contrastive_center_loss: the reference names a class ContrastiveCenterLoss (:547) that it never imports; not built")
     if args.decoder_name == "decoupled_tf_decoder":
         raise SystemExit("--decoder_name decoupled_tf_decoder: the decoupled decoder (models/decoder.py) is not built")
-    if args.decoder_type not in ("tf_decoder", "attention"):
-        raise SystemExit(f"--decoder_type {args.decoder_type}: tf_decoder or attention (the reference raises NotImplementedError, :355)")
+    if args.decoder_type not in ("tf_decoder", "attention", "ctc"):
+        raise SystemExit(f"--decoder_type {args.decoder_type}: tf_decoder, attention or ctc (the reference raises NotImplementedError, :355)")
+    if args.decoder_type == "ctc":
+        if args.beam_width > 0:
+            raise SystemExit("--beam_width with --decoder_type ctc: the CTC head decodes greedily (frame arg-max, collapsed); beam search is built for tf_decoder")
+        if args.text_cond_vis:
+            raise SystemExit("--text_cond_vis with --decoder_type ctc: the text-conditional cross-attention belongs to the transformer decoder; the CTC head has none")
+        if args.use_1d_attdec:
+            raise SystemExit("--use_1d_attdec with --decoder_type ctc: the CTC head always classifies the 32 column means of the token grid; the flag selects "
+                             "the attention decoders' memory")
     if (args.input_h, args.input_w) != (32, 128):
         raise SystemExit(f"--input_h {args.input_h} --input_w {args.input_w}: the encoders are built for 32 x 128 crops")
     paths = [args.data_path] if isinstance(args.data_path, str) else list(args.data_path)
@@ -218,8 +230,9 @@ def save_ckpt_freq(args):
 
 def build_model(args):
     from dig_amd.attn_recognizer import AttnRecModelTrain
+    from dig_amd.ctc_recognizer import CTCRecModelTrain
     from dig_amd.finetune import RecModelTrain
-    return RecModelTrain(args) if args.decoder_type == "tf_decoder" else AttnRecModelTrain(args)
+    return {"tf_decoder": RecModelTrain, "attention": AttnRecModelTrain, "ctc": CTCRecModelTrain}[args.decoder_type](args)
 
 
 def load_finetune_checkpoint(model, args):
@@ -322,7 +335,12 @@ def main(args):
     lr_schedule_values, wd_schedule_values = plan["lr_schedule_values"], plan["wd_schedule_values"]
     print("Max WD = %.7f, Min WD = %.7f" % (max(wd_schedule_values, default=args.weight_decay), min(wd_schedule_values, default=args.weight_decay)))
 
-    if args.smoothing > 0.:
+    if args.decoder_type == "ctc":
+        from dig_amd.ctc_recognizer import SeqCTCLoss
+        if args.smoothing > 0.:
+            print(f"--smoothing {args.smoothing} is ignored with --decoder_type ctc: the criterion is the CTC loss")
+        criterion = SeqCTCLoss(blank=model.blank)
+    elif args.smoothing > 0.:
         criterion = SeqLabelSmoothingCrossEntropyLoss(smoothing=args.smoothing)
         criterion.ignore_index = dataset_train.class_to_idx["PADDING"]
     else:

@@ -1,0 +1,57 @@
+"""Throughput of the CTCRecModel training step and evaluation (`--decoder_type ctc`) beside the tf_decoder's in the same run on the same box:
+simmim_vit_small_patch4_32x128 encoder, 97 classes, max_len 25, batch 256, README drop rates (--drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1;
+the tf_decoder's own dropout 0.1), AdamW with layer decay 0.75; random weights and labels.  Training: forward + criterion + backward + AdamW.
+Evaluation: the eval forward and, for the CTC head, `decode` (for the tf_decoder the forward IS the greedy decode, replayed from its HIP graph).
+Prints the figures stamped with build.source_hash().  No time gate: there is no earlier CTC path to compare with."""
+import os, sys, time, types
+import numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dig_amd import build
+from dig_amd.ctc_recognizer import CTCRecModelTrain, SeqCTCLoss
+from dig_amd.finetune import RecModelTrain, SeqCrossEntropyLoss, LayerDecayValueAssigner, create_optimizer
+from dig_amd.utils import NativeScalerWithGradNormCount
+dev = torch.device("cuda:0")
+B = 256
+g = torch.Generator().manual_seed(0)
+images = (torch.rand(B, 3, 32, 128, generator=g) * 2 - 1).to(dev)
+rng = np.random.RandomState(0)
+lens = torch.from_numpy(rng.randint(3, 26, size=B)); tg = torch.from_numpy(rng.randint(0, 94, size=(B, 25)))
+for b in range(B): tg[b, int(lens[b]) - 1] = 94; tg[b, int(lens[b]):] = 95
+
+
+def measure(name):
+    args = types.SimpleNamespace(model="simmim_vit_small_patch4_32x128", decoder_name="tf_decoder", nb_classes=97, max_len=25, drop=0.1, attn_drop_rate=0.1,
+                                 drop_path=0.1, opt="adamw", lr=1e-4, weight_decay=0.05, opt_eps=1e-8, opt_betas=[0.9, 0.999])
+    torch.manual_seed(0)
+    m = CTCRecModelTrain(args) if name == "ctc" else RecModelTrain(args, decoder_dropout=0.1)
+    m.to(dev); m.train()
+    nl = m.get_num_layers()
+    asg = LayerDecayValueAssigner([0.75 ** (nl + 1 - i) for i in range(nl + 2)])
+    opt = create_optimizer(args, m, get_num_layer=asg.get_layer_id, get_layer_scale=asg.get_scale)
+    for grp in opt.param_groups: grp["lr"] = args.lr * grp["lr_scale"]
+    crit, scaler = (SeqCTCLoss(m.blank) if name == "ctc" else SeqCrossEntropyLoss()), NativeScalerWithGradNormCount()
+    def step():
+        opt.zero_grad()
+        loss = crit(m((images, tg, lens))[0], tg, lens)
+        return loss, scaler(loss, opt, clip_grad=None, parameters=None)
+    for _ in range(3): loss, gn = step()
+    torch.cuda.synchronize(); t = time.perf_counter(); n = 10
+    for _ in range(n): loss, gn = step()
+    torch.cuda.synchronize(); train = (time.perf_counter() - t) / n
+    m.eval()
+    def evaluate():
+        out = m((images, None, None))[0]
+        return m.decode(out)[0] if name == "ctc" else out.argmax(-1)
+    for _ in range(3): ids = evaluate()
+    torch.cuda.synchronize(); t = time.perf_counter(); n = 10
+    for _ in range(n): ids = evaluate()
+    torch.cuda.synchronize(); ev = (time.perf_counter() - t) / n
+    print(f"{name}: training step B={B}: {train*1e3:.2f} ms = {B/train:.0f} images/s (loss {loss.item():.3f}, grad norm {gn.item():.3f}); "
+          f"evaluation forward + decode: {ev*1e3:.2f} ms = {B/ev:.0f} images/s (ids {tuple(ids.shape)})", flush=True)
+    return train, ev
+
+
+print(f"source hash {build.source_hash()}, {torch.cuda.get_device_name(0)}")
+ctc = measure("ctc")
+tfd = measure("tf_decoder")
+print(f"ctc / tf_decoder: training step {ctc[0] / tfd[0]:.3f}x the time, evaluation {ctc[1] / tfd[1]:.3f}x the time")
