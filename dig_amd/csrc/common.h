@@ -59,7 +59,7 @@ __device__ __forceinline__ float erf_fast(float x) {
   return copysignf(r, x);
 }
 // erf(z) for GELU epilogues whose result is rounded to bf16: odd degree-15 polynomial on |z| <= 3 (clamped; minimax fit,
-// |abs err| <= 8.8e-5 including the clamp, i.e. <= 4.4e-5 relative on gelu -- 1/90 of a bf16 ulp) -- 8 FMAs and no
+// |abs err| <= 9.7e-5 including the clamp: erf_poly(3) = 0.99990284 stands for 1 beyond it) -- 8 FMAs and no
 // transcendental, about half the issue cost of erf_fast inside a GEMM epilogue.
 __device__ __forceinline__ float erf_poly(float z) {
   const float zc = fminf(fmaxf(z, -3.0f), 3.0f);
@@ -74,7 +74,10 @@ __device__ __forceinline__ float erf_poly(float z) {
   p = fmaf(p, z2, 1.127895713e+00f);
   return p * zc;
 }
-// erf-GELU (nn.GELU()) and its derivative, fp32 in / out, for bf16-rounded results
+// erf-GELU (nn.GELU()) and its derivative, fp32 in / out, for bf16-rounded results.  Both GELU forms are within 5e-5 |x| of erf-GELU --
+// relative to |x|, not to gelu(x): 4.9e-5 |x| (gelu_f) and 4.7e-5 |x| (gelu_fast_f / gelu_fast2) beyond the clamp, |x| > 4.24, and 4.4e-5 |x|
+// / 4.6e-5 |x| inside it.  For large negative x the result is therefore about -4.9e-5 |x| where erf-GELU is -0 (-3e-3 at x = -64), and
+// x - 4.9e-5 x for large positive x: at most 1/80 of a bf16 ulp of |x|.  tests/test_gelu_sites.py holds every fused site to these bounds.
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf_poly(x * 0.70710678118654752f)); }
 // The same GELU with the constants folded into the polynomial (x erf_poly(x / sqrt 2) / 2 = x xc Q(xc^2), xc = x clamped to
 // +-3 sqrt 2): 11 VALU ops instead of 13.5, same error bound -- for code whose VALU stream is placed between MFMAs by hand.
