@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <string>
 #include <vector>
 
 #include "dig_cpu_common.h"
@@ -975,6 +977,65 @@ int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int 
       prev = am;
     }
     for (int j = cnt; j <= T; ++j) { idr[j] = j == cnt ? eos : padding; scr[j] = 1.f; }
+    n[b] = cnt;
+  }
+  return DIG_OK;
+}
+
+// Prefix beam search, the rule of include/dig_hip.h as written: a candidate table keyed by the prefix (an ordered map from the prefix's
+// bytes to its row; rows in creation order), double recursions, a stable sort by tot for the selection.
+int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width, long long* ids,
+                        float* score, float* logp, int* n, hipStream_t) {
+  if (!logits || !ids || !score || !logp || !n || B < 0 || T <= 0 || C <= 0 || ld < C || blank < 0 || blank >= C || beam_width <= 0) return DIG_ERR_ARG;
+  if (T > 64 || C < 2 || C > 256 || beam_width > 32) return DIG_ERR_UNSUPPORTED;
+  const double NINF = -std::numeric_limits<double>::infinity();
+  struct Hyp { std::string p; double lb, ln, tot; };
+  std::vector<double> lp(C);
+  for (int b = 0; b < B; ++b) {
+    std::vector<Hyp> beam{{std::string(), 0.0, NINF, 0.0}};
+    for (int t = 0; t < T; ++t) {
+      const float* row = logits + ((size_t)b * T + t) * ld;
+      double m = row[0], s = 0.0;
+      for (int c = 1; c < C; ++c) m = std::max(m, (double)row[c]);
+      for (int c = 0; c < C; ++c) s += std::exp((double)row[c] - m);
+      const double l = m + std::log(s);
+      for (int c = 0; c < C; ++c) lp[c] = (double)row[c] - l;
+      std::vector<Hyp> cand;
+      std::map<std::string, int> at;
+      auto cell = [&](const std::string& p) -> Hyp& {
+        auto it = at.find(p);
+        if (it == at.end()) {
+          it = at.emplace(p, (int)cand.size()).first;
+          cand.push_back({p, NINF, NINF, NINF});
+        }
+        return cand[it->second];
+      };
+      for (const Hyp& h : beam) {
+        const int last = h.p.empty() ? -1 : (int)(unsigned char)h.p.back();
+        {
+          Hyp& k = cell(h.p);
+          k.lb = ctc_lse(k.lb, h.tot + lp[blank]);
+          if (last >= 0) k.ln = ctc_lse(k.ln, h.ln + lp[last]);
+        }
+        for (int c = 0; c < C; ++c) {
+          if (c == blank) continue;
+          Hyp& k = cell(h.p + (char)(unsigned char)c);
+          k.ln = ctc_lse(k.ln, (c == last ? h.lb : h.tot) + lp[c]);
+        }
+      }
+      for (Hyp& k : cand) k.tot = ctc_lse(k.lb, k.ln);
+      std::stable_sort(cand.begin(), cand.end(), [](const Hyp& a, const Hyp& b_) { return a.tot > b_.tot; });
+      if ((int)cand.size() > beam_width) cand.resize(beam_width);
+      beam.swap(cand);
+    }
+    long long* idr = ids + (size_t)b * (T + 1);
+    float* scr = score + (size_t)b * (T + 1);
+    int cnt = 0;
+    for (unsigned char ch : beam[0].p)
+      if ((int)ch != eos) idr[cnt++] = ch;
+    for (int j = cnt; j <= T; ++j) idr[j] = j == cnt ? eos : padding;
+    logp[b] = (float)beam[0].tot;
+    for (int j = 0; j <= T; ++j) scr[j] = j == 0 ? (float)std::exp((double)logp[b]) : 1.f;
     n[b] = cnt;
   }
   return DIG_OK;

@@ -98,7 +98,9 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                # the folded text-conditional cross-attention (text_cond_attn.hip): u / dc / the accumulators of a query row stay in registers
                "tcv_fwd_kernel", "tcv_bwd_q_kernel", "tcv_bwd_k_kernel",
                # the CTC criterion and its gradient (ctc.hip): a lane's two states stay in registers, emissions / alphas / occupancies in LDS
-               "ctc_kernel<false>", "ctc_kernel<true>")
+               "ctc_kernel<false>", "ctc_kernel<true>",
+               # the CTC prefix beam search (ctc.hip): a lane's hypothesis in registers, prefixes and the candidate table in LDS
+               "ctc_beam_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 

@@ -3,6 +3,7 @@
 //   dig_ctc_loss           nll[b] = -log p(labels_b | frames 0..T-1), loss = sum_b nll[b] / B     (the alpha recursion)
 //   dig_ctc_loss_bwd       d loss / d logits * gscalar = gscalar / B * (softmax - posterior occupancy of the class)
 //   dig_ctc_greedy_decode  the string rule of ctc_get_str_list (evaluation_metric/metrics.py:220-227) as decoder-shaped rows
+//   dig_ctc_beam_decode    prefix beam search (`--ctc_beam_width`): the best collapsed string over all its alignments, as the same rows
 //
 // One wave per sample.  The extended label sequence blank, l_0, blank, l_1, ..., l_{n-1}, blank has 2n + 1 <= 127 states: lane i owns
 // state 2i (the blank in front of label i; lane n: the final blank) and state 2i + 1 (label i), so a time step moves ONE value between
@@ -247,6 +248,223 @@ __global__ __launch_bounds__(64) void ctc_greedy_kernel(const float* __restrict_
   if (lane == 0) n_out[b] = n;
 }
 
+// CTC prefix beam search (the rule: include/dig_hip.h), one wave per sample.  Lane j owns the hypothesis of rank j: lb, ln, the length and
+// the last symbol of its prefix in registers, the prefix bytes in an LDS row (two sets of rows: a frame reads one and writes the other).  A
+// frame fills the candidate table cs (dynamic LDS, W rows of CP = C rounded up to 64 floats) with every candidate's tot, laid out in the
+// order in which the rule touches the prefixes: row i = hypothesis i, column 0 = "i stays", then "i extended by c" for the classes other
+// than the blank in ascending order; the columns past C hold NaN, which no comparison selects.  An extension that lands on a live prefix is
+// found by the lane of that prefix, which compares lengths, then the last symbols, then the bytes: the two are one candidate, kept in
+// whichever of the two cells comes first (where the prefix was first touched), the other cell struck out with NaN.  The W best are taken one
+// per round by a maximum of (tot, lowest cell index): lane l owns the cells 4 l .. 4 l + 3 of every block of 256 and keeps its best, a DPP
+// reduction and a ballot pick among the lanes, and the wave together finds the winning lane's next best.  A candidate at -inf (probability
+// 0) is never taken: neither it nor a descendant can become the result.  After the selection every state is re-centred on the best tot,
+// whose sum is kept in double, as the alpha recursion above does.  The next frame's logits are loaded before the search of the current
+// one.  LDS at W = 32, C = 256: 32 KB table + 1 KB log-softmax + 4.3 KB prefixes.
+constexpr int CTC_MAX_W = 32, CTC_PFX_WORDS = 17;                          // 64 prefix bytes and a pad word: row j starts on bank 17 j
+
+// The value of lane l (wave-uniform l) as a scalar: v_readlane, where __shfl would go through the LDS crossbar.
+__device__ __forceinline__ int lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// The wave's maximum as a scalar, through the DPP network (row shifts 1, 2, 4, 8 leave a row's maximum in its lane 15; the two row
+// broadcasts carry it on: lane 63 ends with the maximum of all 64) where a __shfl_xor butterfly would make six trips through the LDS crossbar.
+__device__ __forceinline__ float wave_max_dpp(float v) {
+  const int ninf = __float_as_int(-INFINITY);
+#define CTC_DPP_MAX(ctrl, rows) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(ninf, __float_as_int(v), ctrl, rows, 0xf, false)))
+  CTC_DPP_MAX(0x111, 0xf);                                                 // row_shr:1
+  CTC_DPP_MAX(0x112, 0xf);                                                 // row_shr:2
+  CTC_DPP_MAX(0x114, 0xf);                                                 // row_shr:4
+  CTC_DPP_MAX(0x118, 0xf);                                                 // row_shr:8
+  CTC_DPP_MAX(0x142, 0xa);                                                 // row_bcast:15 into rows 1 and 3
+  CTC_DPP_MAX(0x143, 0xc);                                                 // row_bcast:31 into rows 2 and 3
+#undef CTC_DPP_MAX
+  return lane_f(v, 63);
+}
+
+__device__ __forceinline__ void ctc_load_row(const float* __restrict__ row, int C, int lane, float (&v)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = lane + 64 * k < C ? row[lane + 64 * k] : -INFINITY;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ logits, int ld, int T, int C, int blank, int eos, int padding, int W,
+                                                      long long* __restrict__ ids, float* __restrict__ score, float* __restrict__ logp_out,
+                                                      int* __restrict__ n_out) {
+  extern __shared__ float4 beam_dyn[];                                     // (float4: the table is read 16 bytes at a time)
+  __shared__ float lpv[CTC_MAX_C], selv[CTC_MAX_W];
+  __shared__ unsigned pfx[2][CTC_MAX_W * CTC_PFX_WORDS];
+  __shared__ int sel[CTC_MAX_W], srow[CTC_MAX_W];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* x = logits + (size_t)b * T * ld;
+  float* cs = (float*)beam_dyn;
+  const int CJ = (C + 63) >> 6, CP = CJ * 64;
+  for (int i = lane; i < ((W * CP + 255) & ~255); i += 64) cs[i] = NAN;
+  float lb = lane == 0 ? 0.f : -INFINITY, ln = -INFINITY;
+  int len = 0, last = -1, nl = 1, cur = 0;                                 // last = -1: the empty prefix (equal to no class)
+  double off = 0.0;
+  float xn[4];
+  ctc_load_row(x, C, lane, xn);
+  for (int t = 0; t < T; ++t) {
+    float xr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xr[k] = xn[k];
+    if (t + 1 < T) ctc_load_row(x + (size_t)(t + 1) * ld, C, lane, xn);
+    // ---- the frame's log-softmax, as ctc_emissions takes it
+    const float m = wave_max_dpp(fmaxf(fmaxf(xr[0], xr[1]), fmaxf(xr[2], xr[3])));
+    double e = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (lane + 64 * k < C) e += (double)expf((float)((double)xr[k] - (double)m));
+    const double ls = log(wave_sum_f64(e));
+    float lpr[4];                                                           // lp of the classes lane, lane + 64, ...: kept for the extensions
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      lpr[k] = (float)((double)xr[k] - (double)m - ls);
+      if (lane + 64 * k < C) lpv[lane + 64 * k] = lpr[k];
+    }
+    // ---- par = the live hypothesis whose prefix is this lane's without its last symbol (at most one), or -1
+    const unsigned* P = pfx[cur];
+    int par = -1;
+    for (int i = 0; i < nl; ++i) {
+      const int li = lane_i(len, i), lasti = lane_i(last, i);
+      if (lane < nl && par < 0 && len == li + 1) {
+        const unsigned* a = P + i * CTC_PFX_WORDS;
+        const unsigned* q = P + lane * CTC_PFX_WORDS;
+        bool same = li == 0 || lasti == (int)((q[(li - 1) >> 2] >> (8 * ((li - 1) & 3))) & 255u);
+        const int fw = li >> 2, rem = li & 3;
+        for (int k = 0; k < fw && same; ++k) same = a[k] == q[k];
+        if (same && rem) same = ((a[fw] ^ q[fw]) & ((1u << (8 * rem)) - 1u)) == 0u;
+        if (same) par = i;
+      }
+    }
+    __syncthreads();
+    // ---- extensions: cell (i, 1 + c or c, the blank's column skipped) = (lb_i when c repeats the prefix's last symbol, else tot_i) + lp[c]
+    const float tot = lse2(lb, ln);
+    for (int i = 0; i < nl; ++i) {
+      const float ti = lane_f(tot, i), lbi = lane_f(lb, i);
+      const int lasti = lane_i(last, i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int c = lane + 64 * k;
+        if (c < C && c != blank) cs[i * CP + c + (c < blank ? 1 : 0)] = (c == lasti ? lbi : ti) + lpr[k];
+      }
+    }
+    __syncthreads();
+    // ---- stay, with the parent's extension merged in: one candidate in the earlier of the two cells (mc), the later one struck out
+    const int sp = par < 0 ? 0 : par;
+    const float plb = __shfl(lb, sp, 64), ptot = __shfl(tot, sp, 64);
+    const int plast = __shfl(last, sp, 64);
+    float nlb = -INFINITY, nln = -INFINITY;
+    int mc = -1;
+    if (lane < nl) {
+      nlb = tot + lpv[blank];
+      if (len > 0) nln = ln + lpv[last];
+      mc = lane * CP;
+      if (par >= 0) {
+        nln = lse2(nln, (plast == last ? plb : ptot) + lpv[last]);
+        const int xc = par * CP + last + (last < blank ? 1 : 0);
+        cs[max(mc, xc)] = NAN;
+        mc = min(mc, xc);
+      }
+      cs[mc] = lse2(nlb, nln);
+    }
+    __syncthreads();
+    // ---- the W best by (tot, cell index), one per round.  Lane l scans its own cells (4 l .. 4 l + 3 of every block of 256) once and keeps
+    // its best; a round picks among the lanes, strikes the winner's cell, and all 64 lanes together look through the winner's cells (one or
+    // two each) for its next best.  A round that finds nothing ends the selection (fewer than W candidates)
+    const int nq = (nl * CP + 255) >> 8;                                    // blocks; rows past nl in the last one hold NaN
+    float bv = -INFINITY;
+    int bi = -1;
+    {
+      const float4* cs4 = (const float4*)cs + lane;
+      int be = -1;
+      for (int q = 0; q < nq; q += 2) {
+        const float4 a = cs4[q * 64];
+        const float4 c4 = q + 1 < nq ? cs4[(q + 1) * 64] : make_float4(NAN, NAN, NAN, NAN);
+        const float v[8] = {a.x, a.y, a.z, a.w, c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {                                        // (strict: the first of equal values)
+          const bool take = v[u] > bv;
+          bv = take ? v[u] : bv;
+          be = take ? q * 4 + u : be;
+        }
+      }
+      if (be >= 0) bi = (be >> 2) * 256 + lane * 4 + (be & 3);
+    }
+    int nn = 0;
+    for (int r = 0; r < W; ++r) {
+      const float gv = wave_max_dpp(bv);
+      unsigned long long tie = __ballot(bi >= 0 && bv == gv);              // the lanes holding the largest tot: nearly always one
+      if (tie == 0ull) break;                                               // (wave-uniform)
+      int gi = 0x7fffffff;
+      for (; tie; tie &= tie - 1ull) gi = min(gi, lane_i(bi, __ffsll((long long)tie) - 1));
+      const int wl = (gi & 255) >> 2;                                       // the winner's lane
+      if (lane == wl) { cs[gi] = NAN; sel[r] = gi; selv[r] = gv; }
+      nn = r + 1;
+      __syncthreads();
+      // the winner's remaining cells in ascending order: k = 4 q + sub, lane l reads k = l and k = 64 + l
+      const int k0 = lane, k1 = 64 + lane;
+      const float v0 = (k0 >> 2) < nq ? cs[(k0 >> 2) * 256 + wl * 4 + (k0 & 3)] : NAN;
+      const float v1 = (k1 >> 2) < nq ? cs[(k1 >> 2) * 256 + wl * 4 + (k1 & 3)] : NAN;
+      const float nv = wave_max_dpp(fmaxf(fmaxf(v0, v1), -INFINITY));       // (fmaxf drops a NaN operand)
+      int nk = -1;
+      if (nv > -INFINITY) {
+        const unsigned long long t0 = __ballot(v0 == nv);
+        nk = t0 ? __ffsll((long long)t0) - 1 : 64 + __ffsll((long long)__ballot(v1 == nv)) - 1;
+      }
+      if (lane == wl) {
+        bv = nv;
+        bi = nk < 0 ? -1 : (nk >> 2) * 256 + wl * 4 + (nk & 3);
+      }
+    }
+    // ---- the next frame's hypotheses: lane r takes the candidate of cell sel[r], which is "src stays" when it is the cell of a live
+    // prefix and an extension otherwise; prefixes are copied row to row, then the new symbol is appended
+    const int s = lane < nn ? sel[lane] : -2;
+    int src = -1;
+    for (int i = 0; i < nl; ++i)
+      if (lane_i(mc, i) == s) src = i;
+    const bool live = lane < nn, stay = src >= 0;
+    const int row = live ? s / CP : 0, col = live ? s - row * CP : 0;
+    const int pi = stay ? src : row, c = col - (col <= blank ? 1 : 0);       // (c: read for an extension only, col >= 1)
+    const float v = live ? selv[lane] : -INFINITY;
+    const float snlb = __shfl(nlb, pi, 64), snln = __shfl(nln, pi, 64);
+    const int slen = __shfl(len, pi, 64), slast = __shfl(last, pi, 64);
+    if (live) srow[lane] = pi;
+    __syncthreads();
+    unsigned* Q = pfx[cur ^ 1];
+    for (int idx = lane; idx < nn * 16; idx += 64) Q[(idx >> 4) * CTC_PFX_WORDS + (idx & 15)] = P[srow[idx >> 4] * CTC_PFX_WORDS + (idx & 15)];
+    __syncthreads();
+    if (live && !stay) ((unsigned char*)(Q + lane * CTC_PFX_WORDS))[slen] = (unsigned char)c;   // slen <= t <= 63
+    lb = live && stay ? snlb : -INFINITY;
+    ln = live ? (stay ? snln : v) : -INFINITY;
+    len = live ? slen + (stay ? 0 : 1) : 0;
+    last = live ? (stay ? slast : c) : -1;
+    const float m0 = lane_f(lse2(lb, ln), 0);                                // rank 0: the largest tot
+    if (m0 > -INFINITY && m0 < INFINITY) { lb -= m0; ln -= m0; off += (double)m0; }
+    nn = __builtin_amdgcn_readfirstlane(nn);
+    if (nn < nl)                                                            // (a shrinking beam: its abandoned rows must not be scanned again)
+      for (int i = nn * CP + lane; i < nl * CP; i += 64) cs[i] = NAN;
+    nl = nn;
+    cur ^= 1;
+    __syncthreads();
+  }
+  // ---- the row of rank 0 without EOS, compacted with one ballot
+  const unsigned char* best = (const unsigned char*)pfx[cur];
+  const int n0 = lane_i(len, 0);
+  const float lp0 = (float)(off + (double)lane_f(lse2(lb, ln), 0));
+  const int sym = lane < n0 ? (int)best[lane] : -1;
+  const bool emit = lane < n0 && sym != eos;
+  const unsigned long long mask = __ballot(emit);
+  const int pos = __popcll(mask & ((1ull << lane) - 1ull)), n = __popcll(mask);
+  long long* idr = ids + (size_t)b * (T + 1);
+  float* scr = score + (size_t)b * (T + 1);
+  if (emit) idr[pos] = sym;
+  for (int j = lane; j <= T; j += 64) {
+    if (j >= n) idr[j] = j == n ? eos : padding;
+    scr[j] = j == 0 ? (float)exp((double)lp0) : 1.f;                        // (expf loses |logp| * 2^-24 of relative accuracy)
+  }
+  if (lane == 0) { n_out[b] = n; logp_out[b] = lp0; }
+}
+
 int ctc_check(const void* logits, int ld, const void* target, int ldt, const void* target_len, int B, int T, int C, int blank) {
   if (!logits || !target || !target_len || B < 0 || T <= 0 || C <= 0 || ldt <= 0 || ld < C || blank < 0 || blank >= C) return DIG_ERR_ARG;
   if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || ldt > CTC_MAX_LDT) return DIG_ERR_UNSUPPORTED;
@@ -283,5 +501,15 @@ extern "C" int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, 
   if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C) return DIG_ERR_UNSUPPORTED;
   if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64), 0, stream, logits, ld, T, C, blank, eos, padding, ids, score, n);
+  return dig_check_launch();
+}
+
+extern "C" int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width,
+                                   long long* ids, float* score, float* logp, int* n, hipStream_t stream) {
+  if (!logits || !ids || !score || !logp || !n || B < 0 || T <= 0 || C <= 0 || ld < C || blank < 0 || blank >= C || beam_width <= 0) return DIG_ERR_ARG;
+  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || beam_width > CTC_MAX_W) return DIG_ERR_UNSUPPORTED;
+  if (B == 0) return DIG_OK;
+  hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), (size_t)((beam_width * ((C + 63) / 64 * 64) + 255) & ~255) * sizeof(float), stream, logits, ld, T, C, blank, eos, padding,
+                     beam_width, ids, score, logp, n);
   return dig_check_launch();
 }

@@ -8,7 +8,10 @@ eps 1e-6), GELU, Linear(512, nb_classes + 1) on `enc_x.view(B, 8, 32, D).mean(1)
 criterion for it, so these are this project's own definitions: the criterion is the standard CTC loss summed over the samples and divided
 by B (the `sample_normalize` convention of SeqCrossEntropyLoss), with `zero_infinity`; the labels of a target row are its cells in front of
 EOS (`len_offset` = 1 on the datasets' lengths, which count EOS); `decode` returns decoder-shaped rows (emitted classes, EOS, PADDING) with the
-emitting frames' softmax probabilities as scores.
+emitting frames' softmax probabilities as scores.  `--ctc_beam_width K` (own flag, 1..32; `ctc_beam_width` here) makes the evaluation decode a
+prefix beam search of width K, which scores a string by the sum over all its alignments where greedy decoding scores the single best
+alignment; the rule is this project's (the reference has no CTC beam search) and stands in include/dig_hip.h at `dig_ctc_beam_decode`; its
+rows carry the string's probability in score[:, 0] and 1 elsewhere.  Training-mode decodes (the loop's class accuracy) stay greedy.
 
 Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head is
 `dig_window_pool_*` (the `--use_1d_attdec` pooling), two GEMMs and the fused LayerNorm + GELU launch; loss, gradient and decode are
@@ -26,7 +29,7 @@ PRE = "ctc_classifier."
 D_EMBEDDING = 512                                       # model_builder.py:13
 
 
-# ---------------------------------------------------------------------------------------------- the three entry points
+# ---------------------------------------------------------------------------------------------- the four entry points
 def ctc_loss(logits, C, target, length, blank, len_offset=1):
     """dig_ctc_loss on logits fp32 [B, T, ld >= C]: (nll [B], loss [1])."""
     B, T, ld = logits.shape
@@ -56,6 +59,23 @@ def ctc_greedy_decode(logits, C, blank, eos, padding):
     n = torch.empty(B, device=dev, dtype=torch.int32)
     L.call("dig_ctc_greedy_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, L.ptr(ids), L.ptr(score), L.ptr(n), L.stream())
     return ids, score, n
+
+
+MAX_BEAM_WIDTH = 32                                     # csrc/ctc.hip: one lane per hypothesis, the candidate table in LDS
+
+
+def ctc_beam_decode(logits, C, blank, eos, padding, beam_width):
+    """dig_ctc_beam_decode (prefix beam search, the rule in include/dig_hip.h) on logits fp32 [B, T, ld >= C]: (ids int64 [B, T + 1],
+    score fp32 [B, T + 1] = exp(logp) then 1, logp fp32 [B], n int32 [B])."""
+    B, T, ld = logits.shape
+    dev = logits.device
+    ids = torch.empty((B, T + 1), device=dev, dtype=torch.int64)
+    score = torch.empty((B, T + 1), device=dev, dtype=F32)
+    logp = torch.empty(B, device=dev, dtype=F32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    L.call("dig_ctc_beam_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, int(beam_width), L.ptr(ids), L.ptr(score), L.ptr(logp), L.ptr(n),
+           L.stream())
+    return ids, score, logp, n
 
 
 def match_widths(pred, target, padding):
@@ -160,12 +180,17 @@ class _CTCTrainStep(_TrainStep):
 
 class CTCRecModelTrain(RecModelTrain):
     """models.model_builder.CTCRecModel: `.train()` forward = (logits [B, 32, nb_classes + 1] fp32, None, None, None) with autograd,
-    `.eval()` forward = the same logits from the walk without dropout; `decode(logits)` = the greedy CTC strings as decoder-shaped rows."""
+    `.eval()` forward = the same logits from the walk without dropout; `decode(logits)` = the CTC strings as decoder-shaped rows, greedy or,
+    with `ctc_beam_width` K > 0 (args.ctc_beam_width) in eval mode, by prefix beam search of width K."""
     _step_cls = _CTCTrainStep
     is_ctc = True
 
     def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, nb_classes=97, max_len=25, drop_rate=None, attn_drop_rate=None,
-                 drop_path_rate=None, drop_seed=None):
+                 drop_path_rate=None, drop_seed=None, ctc_beam_width=None):
+        if ctc_beam_width is None:
+            ctc_beam_width = getattr(args, "ctc_beam_width", 0) or 0
+        if not 0 <= int(ctc_beam_width) <= MAX_BEAM_WIDTH:
+            raise ValueError(f"ctc_beam_width {ctc_beam_width}: 0 (greedy) or a prefix beam search of width 1..{MAX_BEAM_WIDTH}")
         if args is not None:
             embed_dim, num_heads = ENCODERS[args.model]
             nb_classes, max_len = args.nb_classes, args.max_len
@@ -181,7 +206,8 @@ class CTCRecModelTrain(RecModelTrain):
                          drop_path_rate=drop_path_rate or 0.0, decoder_dropout=0.0, drop_seed=drop_seed)
         self.blank = nb_classes                                             # blank_label = len(classes) (metrics.py:211)
         self.eos, self.padding = nb_classes - 3, nb_classes - 2             # a vocabulary ends in EOS, PADDING, UNKNOWN (datasets.find_classes)
-        self.beam_width = 0
+        self.beam_width = 0                                                 # (the autoregressive --beam_width: this head has no such decoder)
+        self.ctc_beam_width = int(ctc_beam_width)                           # what `decode` runs in eval mode: 0 = greedy
 
     def param_shapes(self):
         o = encoder_shapes("encoder.", self.D, self.F, self.depth, True)
@@ -209,10 +235,18 @@ class CTCRecModelTrain(RecModelTrain):
         C1 = self.nb_classes + 1
         return step.head_forward(enc)[0][:, :C1].reshape(B, self.gw, C1)
 
-    def decode(self, logits):
-        """(ids int64 [B, 33], score fp32 [B, 33], n int32 [B]) of logits [B, 32, nb_classes + 1]: csrc/ctc.hip's greedy rule."""
+    def decode(self, logits, beam_width=None):
+        """(ids int64 [B, 33], score fp32 [B, 33], n int32 [B]) of logits [B, 32, nb_classes + 1].  beam_width 0: csrc/ctc.hip's greedy
+        rule (scores: the emitting frames' probabilities); K > 0: its prefix beam search of width K (score[:, 0]: the probability of the
+        string over all its alignments).  None: `ctc_beam_width` in eval mode and 0 while training (the class accuracy of the training loop
+        stays the greedy one)."""
+        if beam_width is None:
+            beam_width = 0 if self.training else self.ctc_beam_width
         x = logits.detach().float().contiguous()
-        return ctc_greedy_decode(x, x.shape[2], self.blank, self.eos, self.padding)
+        if beam_width == 0:
+            return ctc_greedy_decode(x, x.shape[2], self.blank, self.eos, self.padding)
+        ids, score, _, n = ctc_beam_decode(x, x.shape[2], self.blank, self.eos, self.padding, beam_width)
+        return ids, score, n
 
     def forward(self, x):
         if self.training:

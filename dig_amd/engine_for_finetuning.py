@@ -2,7 +2,8 @@
 
 `evaluate()` (:214-285): greedy decode through `dig_amd.recognizer.RecModel`, SeqCrossEntropyLoss, string accuracy and character
 F-measure all on the device; one host read per batch.  A CTC model (`is_ctc`, dig_amd/ctc_recognizer.py) is scored on `model.decode(logits)`
--- the collapsed frames as decoder-shaped rows -- under SeqCTCLoss, in both functions; every other model takes the lines it always took.
+-- the collapsed frames as decoder-shaped rows -- under SeqCTCLoss, in both functions (a model in training mode decodes greedily; in
+`evaluate` its `ctc_beam_width` chooses between the greedy rule and the prefix beam search); every other model takes the lines it always took.
 `train_one_epoch()` (:54-210) with `train_class_batch` (:26-46) for the torch.amp branch (`loss_scaler` given): per-step lr / weight
 decay from the schedules times each group's `lr_scale`, teacher-forced forward, SeqCrossEntropyLoss, backward + grad norm + fused
 AdamW through the scaler object, gradient accumulation (`update_freq`), class accuracy of the arg-max, evaluation every

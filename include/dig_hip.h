@@ -630,14 +630,29 @@ int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* t
  *     `padding`: a row reads like a decoder's output (dig_string_match, dig_tokens_to_text, ... take it unchanged).  score [B][T+1] fp32 =
  *     the softmax probability of the emitting frame's class, then 1.0 (RecPostProcess multiplies score[:len+1]); n [B] int32 = the
  *     number of emitted classes.
- * Null pointer, non-positive dimension, B < 0, ld or ldd < C, blank outside [0, C): DIG_ERR_ARG.  Outside 1 <= T <= 64, 2 <= C <= 256,
- * ldt <= 63: DIG_ERR_UNSUPPORTED.  B == 0: DIG_OK without a launch. */
+ *   dig_ctc_beam_decode: CTC prefix beam search of width beam_width (`--ctc_beam_width`; this project's own rule, the reference has none),
+ *     over lp[t][c] = the log-softmax of frame t.  A hypothesis is (prefix of non-blank classes, lb, ln): the log-probability of all
+ *     alignments of frames 0..t that collapse to the prefix and end in blank / in the prefix's last class; tot = logaddexp(lb, ln).  Start:
+ *     the empty prefix with lb = 0, ln = -inf.  Frame t visits the live hypotheses best first and adds (logaddexp, cells start at -inf) into
+ *     a candidate table keyed by prefix: cand[p].lb += tot + lp[t][blank]; when p is not empty cand[p].ln += ln + lp[t][last(p)]; for every
+ *     class c != blank in ascending order cand[p + c].ln += (lb if p is not empty and c == last(p), else tot) + lp[t][c], where p + c may be a
+ *     live prefix itself (one candidate: the contributions merge; identity is decided on the prefixes' bytes, never on a hash).  `eos` is an
+ *     ordinary class during the search.  The beam_width candidates of largest tot (all of them when fewer), ties broken by the order in
+ *     which the prefixes were first touched, sorted the same way, are the next frame's hypotheses.  After frame T - 1 the best hypothesis
+ *     gives logp[b] = its tot (fp32), ids [B][T+1] = its prefix without the symbols equal to `eos` (as the greedy rule: collapse, then do not
+ *     emit EOS; an `eos` outside [0, C) removes nothing), then `eos`, then `padding`; n [B] = the count after that removal; score [B][T+1]:
+ *     score[b][0] = exp(logp[b]), every other cell 1.0, so that RecPostProcess's product over score[:len+1] is the hypothesis probability.
+ *     fp32 recursions in log space, no floating-point atomics: two launches on the same input give the same bits.
+ * Null pointer, non-positive dimension, B < 0, ld or ldd < C, blank outside [0, C), beam_width <= 0: DIG_ERR_ARG.  Outside 1 <= T <= 64,
+ * 2 <= C <= 256, ldt <= 63, beam_width <= 32: DIG_ERR_UNSUPPORTED.  B == 0: DIG_OK without a launch.  A refused call writes nothing. */
 int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
                  int C, int blank, float* nll, float* loss, hipStream_t stream);
 int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset,
                      const float* gscalar, int B, int T, int C, int blank, void* dlogits, int ldd, int dlogits_is_f32, hipStream_t stream);
 int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids, float* score,
                           int* n, hipStream_t stream);
+int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width, long long* ids,
+                        float* score, float* logp, int* n, hipStream_t stream);
 
 /* ---- dropout / stochastic depth of the fine-tune step (README.md:100-118: --drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1; the
  * recognition decoder's hard-wired dropout = 0.1, models/decoder.py:141).  Replaces nn.Dropout (modeling_finetune.py:51,83-85,271;

@@ -35,9 +35,11 @@ What is different, on purpose:
     datasets, inputs other than 32 x 128) say so and stop;
   * `--decoder_type ctc`: the reference's help text promises it and models/model_builder.py has `CTCRecModel`, but its `main` raises for it and
     has no criterion.  Here it builds `CTCRecModelTrain` under `SeqCTCLoss` whatever --smoothing says (reported once when --smoothing > 0 is
-    ignored); --beam_width > 0, --text_cond_vis and --use_1d_attdec stop with it (dig_amd/ctc_recognizer.py says what is mirrored and what is
-    this project's own definition);
-  * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`).
+    ignored); --beam_width > 0 (the autoregressive beam), --text_cond_vis and --use_1d_attdec stop with it (dig_amd/ctc_recognizer.py says
+    what is mirrored and what is this project's own definition);
+  * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`), --ctc_beam_width K
+    (with --decoder_type ctc: `evaluate` decodes by CTC prefix beam search of width K <= 32, said once; 0, the default, is the greedy collapse;
+    the training loop's class accuracy stays greedy).
 
 Multi-rank runs are wired (samplers, FlatGradComm, the meters' all-reduce) but only the single-rank path is tested."""
 import argparse
@@ -108,6 +110,7 @@ def get_args(argv=None):
     a("--use_contrastive_center_loss", action="store_true", default=False)
     a("--smoothing", type=float, default=0.1)
     a("--beam_width", type=int, default=0)
+    a("--ctc_beam_width", type=int, default=0, help="with --decoder_type ctc: evaluate with a CTC prefix beam search of this width (1..32); 0 = greedy")
     # fine-tuning
     a("--finetune", default="", help="pre-training checkpoint to start from")
     a("--model_key", default="model|module", type=str)
@@ -192,12 +195,18 @@ def refuse_unbuilt(args):
         raise SystemExit(f"--decoder_type {args.decoder_type}: tf_decoder, attention or ctc (the reference raises NotImplementedError, :355)")
     if args.decoder_type == "ctc":
         if args.beam_width > 0:
-            raise SystemExit("--beam_width with --decoder_type ctc: the CTC head decodes greedily (frame arg-max, collapsed); beam search is built for tf_decoder")
+            raise SystemExit("--beam_width with --decoder_type ctc: the CTC head decodes greedily (frame arg-max, collapsed) unless --ctc_beam_width K asks "
+                             "for its prefix beam search; --beam_width is the autoregressive beam, built for tf_decoder")
         if args.text_cond_vis:
             raise SystemExit("--text_cond_vis with --decoder_type ctc: the text-conditional cross-attention belongs to the transformer decoder; the CTC head has none")
         if args.use_1d_attdec:
             raise SystemExit("--use_1d_attdec with --decoder_type ctc: the CTC head always classifies the 32 column means of the token grid; the flag selects "
                              "the attention decoders' memory")
+    if args.ctc_beam_width != 0 and args.decoder_type != "ctc":
+        raise SystemExit(f"--ctc_beam_width with --decoder_type {args.decoder_type}: the prefix beam search decodes the CTC head's frames "
+                         "(--decoder_type ctc); the transformer decoder's beam is --beam_width")
+    if not 0 <= args.ctc_beam_width <= 32:
+        raise SystemExit(f"--ctc_beam_width {args.ctc_beam_width}: 0 (greedy) or a width of 1..32")
     if (args.input_h, args.input_w) != (32, 128):
         raise SystemExit(f"--input_h {args.input_h} --input_w {args.input_w}: the encoders are built for 32 x 128 crops")
     paths = [args.data_path] if isinstance(args.data_path, str) else list(args.data_path)
@@ -340,6 +349,8 @@ def main(args):
         if args.smoothing > 0.:
             print(f"--smoothing {args.smoothing} is ignored with --decoder_type ctc: the criterion is the CTC loss")
         criterion = SeqCTCLoss(blank=model.blank)
+        if model.ctc_beam_width > 0:
+            print(f"evaluation decoder = CTC prefix beam search, width {model.ctc_beam_width} (--ctc_beam_width); the training loop's accuracy decodes greedily")
     elif args.smoothing > 0.:
         criterion = SeqLabelSmoothingCrossEntropyLoss(smoothing=args.smoothing)
         criterion.ignore_index = dataset_train.class_to_idx["PADDING"]

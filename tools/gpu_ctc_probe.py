@@ -1,7 +1,9 @@
 """Throughput of the CTCRecModel training step and evaluation (`--decoder_type ctc`) beside the tf_decoder's in the same run on the same box:
 simmim_vit_small_patch4_32x128 encoder, 97 classes, max_len 25, batch 256, README drop rates (--drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1;
 the tf_decoder's own dropout 0.1), AdamW with layer decay 0.75; random weights and labels.  Training: forward + criterion + backward + AdamW.
-Evaluation: the eval forward and, for the CTC head, `decode` (for the tf_decoder the forward IS the greedy decode, replayed from its HIP graph).
+Evaluation: the eval forward and, for the CTC head, `decode` (for the tf_decoder the forward IS the greedy decode, replayed from its HIP graph);
+for the CTC head also with the prefix beam search of widths 4, 8, 16 and 32 (`--ctc_beam_width`) in place of the greedy decode, beside the
+decode launch alone on the same logits and the share of rows that the search decodes differently (random weights: flat frames).
 Prints the figures stamped with build.source_hash().  No time gate: there is no earlier CTC path to compare with."""
 import os, sys, time, types
 import numpy as np, torch
@@ -48,6 +50,22 @@ def measure(name):
     torch.cuda.synchronize(); ev = (time.perf_counter() - t) / n
     print(f"{name}: training step B={B}: {train*1e3:.2f} ms = {B/train:.0f} images/s (loss {loss.item():.3f}, grad norm {gn.item():.3f}); "
           f"evaluation forward + decode: {ev*1e3:.2f} ms = {B/ev:.0f} images/s (ids {tuple(ids.shape)})", flush=True)
+    if name == "ctc":
+        def timed(fn, n=20):
+            for _ in range(3): fn()
+            torch.cuda.synchronize(); t = time.perf_counter()
+            for _ in range(n): fn()
+            torch.cuda.synchronize(); return (time.perf_counter() - t) / n
+        out = m((images, None, None))[0]
+        greedy_ids, dec0 = m.decode(out, beam_width=0)[0], timed(lambda: m.decode(out, beam_width=0))
+        print(f"ctc: greedy decode alone {dec0*1e3:.3f} ms", flush=True)
+        for width in (4, 8, 16, 32):
+            m.ctc_beam_width = width
+            evw, decw = timed(evaluate, 10), timed(lambda: m.decode(out))
+            differ = int((m.decode(out)[0] != greedy_ids).any(1).sum())
+            print(f"ctc: --ctc_beam_width {width}: evaluation forward + decode: {evw*1e3:.2f} ms = {B/evw:.0f} images/s ({evw/ev:.3f}x the greedy "
+                  f"evaluation); beam decode alone {decw*1e3:.3f} ms; {differ} of {B} rows differ from the greedy ones", flush=True)
+        m.ctc_beam_width = 0
     return train, ev
 
 
