@@ -6,7 +6,7 @@ models/attn_decoder.py:11-78,197-272 (`AttentionRecognitionHead.forward_train` -
 zero-padded to max_len -- and the greedy `sample`; `DecoderUnit` = additive attention + target embedding + one nn.GRU cell + classifier).
 Same state-dict keys as the reference (`decoder.decoder.attention_unit.{sEmbed,xEmbed,wEmbed}.*`, `decoder.decoder.tgt_embedding.weight`,
 `decoder.decoder.gru.{weight,bias}_{ih,hh}_l0`, `decoder.decoder.fc.*`).  Flat arenas, one autograd node, the encoder on the
-pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head's steps run on `dig_gemm_bf16` + `dig_addattn_*` +
+pre-training hot-path kernels (model and step on dig_amd.finetune.EncoderTrain / _EncoderStep); the head's steps run on `dig_gemm_bf16` + `dig_addattn_*` +
 `dig_gru_cell_*` (csrc/gru_attn.hip), weight gradients as ONE GEMM per weight over the stacked steps.  Beam search is not built."""
 import math
 import types
@@ -15,21 +15,18 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .arena import encoder_shapes
-from .finetune import RecModelTrain, _TrainStep, CLS_PAD, encoder_plan
-from .recognizer import ENCODERS
+from .finetune import EncoderTrain, _EncoderStep, CLS_PAD
 
 BF16, F32 = torch.bfloat16, torch.float32
 PRE = "decoder.decoder."
 
 
-class _AttnTrainStep(_TrainStep):
+class _AttnTrainStep(_EncoderStep):
     """Forward / backward of one AttnRecModel step (teacher forcing)."""
 
     def _w(self):
         M = self.m
-        A, S, X, E, C = M.attDim, M.sDim, M.D, M.attDim, M.nb_classes
-        return A, S, X, E, C
+        return M.attDim, M.sDim, M.D, M.attDim, M.nb_classes                 # A, S, X, E, C
 
     def head_inputs(self, x):
         """What every step of the head reads: the encoder tokens x [B*N, X], xEmbed(x) [B*N, A], the wEmbed vector [A], and the sEmbed / GRU
@@ -154,35 +151,25 @@ class _AttnTrainStep(_TrainStep):
         main.wait_stream(sd)
 
 
-class AttnRecModelTrain(RecModelTrain):
+class AttnRecModelTrain(EncoderTrain):
     """models.model_builder.AttnRecModel: `.train()` forward = teacher-forced logits [B, max_len, nb_classes] (+ three Nones),
     `.eval()` forward = greedy `sample` probabilities, both as the reference returns them."""
     _step_cls = _AttnTrainStep
 
-    def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, nb_classes=97, max_len=25, sDim=512, attDim=512, drop_rate=None,
-                 attn_drop_rate=None, drop_path_rate=None, drop_seed=None):
-        if args is not None:
-            embed_dim, num_heads = ENCODERS[args.model]
-            nb_classes, max_len = args.nb_classes, args.max_len
-            if getattr(args, "beam_width", 0):
-                # the reference never reaches AttentionRecognitionHead.beam_search: AttnRecModel.forward (model_builder.py:66-72) calls
-                # the head's __call__ (forward_train / sample) whatever args.beam_width says, and the method itself indexes with the float
-                # result of `candidates / num_classes` (attn_decoder.py:126-127).  Refused here rather than silently decoded greedily.
-                raise NotImplementedError("--beam_width with --decoder_type attention: the reference's AttnRecModel ignores it (greedy sample()); "
-                                          "beam search is built for tf_decoder")
-            drop_rate = float(getattr(args, "drop", 0.0)) if drop_rate is None else drop_rate
-            attn_drop_rate = float(getattr(args, "attn_drop_rate", 0.0)) if attn_drop_rate is None else attn_drop_rate
-            drop_path_rate = float(getattr(args, "drop_path", 0.0)) if drop_path_rate is None else drop_path_rate
-        if attDim % 8 or attDim > 1024 or sDim % 64 or (attDim + embed_dim) % 64:
-            raise NotImplementedError("attDim must be a multiple of 8 (<= 1024), sDim and attDim + embed_dim multiples of 64")
+    def __init__(self, args=None, *, sDim=512, attDim=512, **kw):
+        if getattr(args, "beam_width", 0):
+            # the reference never reaches AttentionRecognitionHead.beam_search: AttnRecModel.forward (model_builder.py:66-72) calls
+            # the head's __call__ (forward_train / sample) whatever args.beam_width says, and the method itself indexes with the float
+            # result of `candidates / num_classes` (attn_decoder.py:126-127).  Refused here rather than silently decoded greedily.
+            raise NotImplementedError("--beam_width with --decoder_type attention: the reference's AttnRecModel ignores it (greedy sample()); "
+                                      "beam search is built for tf_decoder")
         self.sDim, self.attDim = sDim, attDim
-        super().__init__(None, embed_dim=embed_dim, depth=depth, num_heads=num_heads, n_layers=0, d_model=attDim, n_head=1, d_k=64, d_inner=0,
-                         nb_classes=nb_classes, max_len=max_len, drop_rate=drop_rate or 0.0, attn_drop_rate=attn_drop_rate or 0.0,
-                         drop_path_rate=drop_path_rate or 0.0, decoder_dropout=0.0, drop_seed=drop_seed)
+        super().__init__(args, **kw)
+        if attDim % 8 or attDim > 1024 or sDim % 64 or (attDim + self.D) % 64:
+            raise NotImplementedError("attDim must be a multiple of 8 (<= 1024), sDim and attDim + embed_dim multiples of 64")
 
-    def param_shapes(self):
-        D, A, S, C = self.D, self.attDim, self.sDim, self.nb_classes
-        o = encoder_shapes("encoder.", D, self.F, self.depth, True)
+    def head_shapes(self):
+        D, A, S, C, o = self.D, self.attDim, self.sDim, self.nb_classes, {}
         o[PRE + "attention_unit.sEmbed.weight"] = (A, S); o[PRE + "attention_unit.sEmbed.bias"] = (A,)
         o[PRE + "attention_unit.xEmbed.weight"] = (A, D); o[PRE + "attention_unit.xEmbed.bias"] = (A,)
         o[PRE + "attention_unit.wEmbed.weight"] = (1, A); o[PRE + "attention_unit.wEmbed.bias"] = (1,)
@@ -207,14 +194,8 @@ class AttnRecModelTrain(RecModelTrain):
     # ------------------------------------------------------------------ eval: greedy sample (attn_decoder.py:58-78)
     @torch.no_grad()
     def sample(self, images):
-        dev = images.device
-        if self._dev != dev or self._shadow is None:
-            self._bind(dev)
-        step = _AttnTrainStep(self)
-        self.refresh_shadow()
-        B, N = images.shape[0], self.N
-        # eval mode: the training step's walk without dropout keys (and, like it, with the blocks' activations kept)
-        x, _ = self.encoder_front(images, encoder_plan(self, B * N), True, frozen=self.frozen_blocks)
+        dev, B, N = images.device, images.shape[0], self.N
+        step, x = self.eval_tokens(images)
         A, S, X, E, C = step._w()
         hd = step.head_inputs(x)
         cls_w, cb = self.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
@@ -245,7 +226,4 @@ class AttnRecModelTrain(RecModelTrain):
             lens = x[2]
             self._steps_hint = int(lens.max()) if (torch.is_tensor(lens) and not lens.is_cuda and lens.numel()) else None
             return super().forward(x)
-        images = x[0] if isinstance(x, (tuple, list)) else x
-        if not images.is_cuda:
-            raise RuntimeError("dig_amd.AttnRecModelTrain runs on an MI355X (cuda device) only; there is no CPU fallback")
-        return self.sample(images), None, None, None
+        return self.sample(self._device_images(x)), None, None, None

@@ -13,16 +13,14 @@ prefix beam search of width K, which scores a string by the sum over all its ali
 alignment; the rule is this project's (the reference has no CTC beam search) and stands in include/dig_hip.h at `dig_ctc_beam_decode`; its
 rows carry the string's probability in score[:, 0] and 1 elsewhere.  Training-mode decodes (the loop's class accuracy) stay greedy.
 
-Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (dig_amd.finetune._TrainStep); the head is
+Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (model and step on dig_amd.finetune.EncoderTrain / _EncoderStep); the head is
 `dig_window_pool_*` (the `--use_1d_attdec` pooling), two GEMMs and the fused LayerNorm + GELU launch; loss, gradient and decode are
 csrc/ctc.hip.  There is no CPU fallback."""
 import torch
 
 from . import _lib as L
 from . import ops
-from .arena import encoder_shapes
-from .finetune import RecModelTrain, _TrainStep, CLS_PAD, encoder_plan
-from .recognizer import ENCODERS
+from .finetune import EncoderTrain, _EncoderStep, CLS_PAD
 
 BF16, F32 = torch.bfloat16, torch.float32
 PRE = "ctc_classifier."
@@ -129,7 +127,7 @@ class SeqCTCLoss(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------- the model
-class _CTCTrainStep(_TrainStep):
+class _CTCTrainStep(_EncoderStep):
     """Forward / backward of one CTCRecModel step."""
 
     def head_forward(self, enc):
@@ -164,10 +162,7 @@ class _CTCTrainStep(_TrainStep):
         cols, h, mu, rs, a = self.saved
         dl = torch.zeros((rows, CLS_PAD), device=dev, dtype=BF16)
         dl[:, :C1] = dlogits_btc.reshape(rows, C1).to(BF16)
-        side(lambda: ops.wgrad(dl, a, g(PRE + "3.weight"), C1, D_EMBEDDING, rows), dl, a)
-        cs = torch.zeros(CLS_PAD, device=dev, dtype=F32)
-        side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), g(PRE + "3.bias").add_(cs[:C1])), dl, cs)
-        da = ops.gemm(dl, self.cls_w, rows, D_EMBEDDING, CLS_PAD, tb=True)
+        da = self.classifier_backward(dl, a, PRE + "3.weight", PRE + "3.bias", classes=C1)
         dh = ops.layernorm_bwd(da, h, p(PRE + "1.weight"), p(PRE + "1.bias"), mu, rs, None, g(PRE + "1.weight"), g(PRE + "1.bias"), gelu=True)
         side(lambda: ops.linear_wgrad(dh, cols, g(PRE + "0.weight")), dh, cols)
         side(lambda: ops.colsum(dh, g(PRE + "0.bias")), dh)
@@ -178,62 +173,40 @@ class _CTCTrainStep(_TrainStep):
         main.wait_stream(sd)
 
 
-class CTCRecModelTrain(RecModelTrain):
+class CTCRecModelTrain(EncoderTrain):
     """models.model_builder.CTCRecModel: `.train()` forward = (logits [B, 32, nb_classes + 1] fp32, None, None, None) with autograd,
     `.eval()` forward = the same logits from the walk without dropout; `decode(logits)` = the CTC strings as decoder-shaped rows, greedy or,
     with `ctc_beam_width` K > 0 (args.ctc_beam_width) in eval mode, by prefix beam search of width K."""
     _step_cls = _CTCTrainStep
     is_ctc = True
+    _LAYER_NORMS = (PRE + "1.",)                        # (the head keeps PyTorch's defaults: CTCRecModel applies no init of its own)
 
-    def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, nb_classes=97, max_len=25, drop_rate=None, attn_drop_rate=None,
-                 drop_path_rate=None, drop_seed=None, ctc_beam_width=None):
+    def __init__(self, args=None, *, ctc_beam_width=None, **kw):
         if ctc_beam_width is None:
             ctc_beam_width = getattr(args, "ctc_beam_width", 0) or 0
         if not 0 <= int(ctc_beam_width) <= MAX_BEAM_WIDTH:
             raise ValueError(f"ctc_beam_width {ctc_beam_width}: 0 (greedy) or a prefix beam search of width 1..{MAX_BEAM_WIDTH}")
-        if args is not None:
-            embed_dim, num_heads = ENCODERS[args.model]
-            nb_classes, max_len = args.nb_classes, args.max_len
-            drop_rate = float(getattr(args, "drop", 0.0)) if drop_rate is None else drop_rate
-            attn_drop_rate = float(getattr(args, "attn_drop_rate", 0.0)) if attn_drop_rate is None else attn_drop_rate
-            drop_path_rate = float(getattr(args, "drop_path", 0.0)) if drop_path_rate is None else drop_path_rate
+        super().__init__(args, **kw)
+        nb_classes = self.nb_classes
         if nb_classes + 1 > CLS_PAD:
             raise NotImplementedError(f"nb_classes + 1 above {CLS_PAD}: the classifier is padded to {CLS_PAD} rows")
         if nb_classes < 3:
             raise ValueError("nb_classes counts EOS, PADDING and UNKNOWN, the last three classes of a vocabulary")
-        super().__init__(None, embed_dim=embed_dim, depth=depth, num_heads=num_heads, n_layers=0, d_model=D_EMBEDDING, n_head=1, d_k=64, d_inner=0,
-                         nb_classes=nb_classes, max_len=max_len, drop_rate=drop_rate or 0.0, attn_drop_rate=attn_drop_rate or 0.0,
-                         drop_path_rate=drop_path_rate or 0.0, decoder_dropout=0.0, drop_seed=drop_seed)
         self.blank = nb_classes                                             # blank_label = len(classes) (metrics.py:211)
         self.eos, self.padding = nb_classes - 3, nb_classes - 2             # a vocabulary ends in EOS, PADDING, UNKNOWN (datasets.find_classes)
-        self.beam_width = 0                                                 # (the autoregressive --beam_width: this head has no such decoder)
         self.ctc_beam_width = int(ctc_beam_width)                           # what `decode` runs in eval mode: 0 = greedy
 
-    def param_shapes(self):
-        o = encoder_shapes("encoder.", self.D, self.F, self.depth, True)
-        o[PRE + "0.weight"] = (D_EMBEDDING, self.D); o[PRE + "0.bias"] = (D_EMBEDDING,)
-        o[PRE + "1.weight"] = (D_EMBEDDING,); o[PRE + "1.bias"] = (D_EMBEDDING,)
+    def head_shapes(self):
+        o = {PRE + "0.weight": (D_EMBEDDING, self.D), PRE + "0.bias": (D_EMBEDDING,), PRE + "1.weight": (D_EMBEDDING,), PRE + "1.bias": (D_EMBEDDING,)}
         o[PRE + "3.weight"] = (self.nb_classes + 1, D_EMBEDDING); o[PRE + "3.bias"] = (self.nb_classes + 1,)
         return o
-
-    def _init_tensor(self, k, shp):
-        """Head: PyTorch defaults (CTCRecModel applies no init of its own): nn.Linear U(+-1/sqrt(fan_in)), nn.LayerNorm (1, 0)."""
-        if k.startswith(PRE + "1."):
-            return torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
-        return super()._init_tensor(k, shp)
 
     @torch.no_grad()
     def logits(self, images):
         """The eval forward: the training step's walk without dropout keys (and, like it, with the blocks' activations kept)."""
-        dev = images.device
-        if self._dev != dev or self._shadow is None:
-            self._bind(dev)
-        step = _CTCTrainStep(self)
-        self.refresh_shadow()
-        B = images.shape[0]
-        enc, _ = self.encoder_front(images, encoder_plan(self, B * self.N), True, frozen=self.frozen_blocks)
+        step, enc = self.eval_tokens(images)
         C1 = self.nb_classes + 1
-        return step.head_forward(enc)[0][:, :C1].reshape(B, self.gw, C1)
+        return step.head_forward(enc)[0][:, :C1].reshape(images.shape[0], self.gw, C1)
 
     def decode(self, logits, beam_width=None):
         """(ids int64 [B, 33], score fp32 [B, 33], n int32 [B]) of logits [B, 32, nb_classes + 1].  beam_width 0: csrc/ctc.hip's greedy
@@ -251,7 +224,4 @@ class CTCRecModelTrain(RecModelTrain):
     def forward(self, x):
         if self.training:
             return super().forward(x)
-        images = x[0] if isinstance(x, (tuple, list)) else x
-        if not images.is_cuda:
-            raise RuntimeError("dig_amd.CTCRecModelTrain runs on an MI355X (cuda device) only; there is no CPU fallback")
-        return self.logits(images), None, None, None
+        return self.logits(self._device_images(x)), None, None, None

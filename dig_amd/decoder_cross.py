@@ -2,7 +2,7 @@
 model runs is decided once, by `choose`, from three shape facts; everything else the package knows about a form is on its class --
 
   * `extra_shapes` / `views`: the parameters it adds behind `enc_attn.fc.weight` and its entries of the layer's view dict (RecModel);
-  * training (`finetune._TrainStep`, passed in as `step`): `prepare`, the work that depends on the encoder memory alone -- the step issues it
+  * training (`finetune._DecoderStep`, passed in as `step`): `prepare`, the work that depends on the encoder memory alone -- the step issues it
     for all layers on the second stream before the layer loop, one event per layer, and `step.prepared(p)` waits for layer p's; `forward`
     (norm2's output, the layer's dropout spec) -> (attention output, saved state); `backward` (the gradient behind enc_attn.fc's proj_drop,
     that state) -> the gradient w.r.t. norm2's output, weight gradients through `step.side`, the memory gradient through `step.add_dmem`;

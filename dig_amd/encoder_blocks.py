@@ -1,5 +1,5 @@
 """The per-entry-point walk over the ViT encoder blocks -- norm1 -> qkv -> attention -> proj -> norm2 -> fc1 / GELU / fc2 and its explicit
-reverse -- for every caller: the pre-training step (engine_core._Step), the fine-tune step (finetune._TrainStep) and the recognition forward
+reverse -- for every caller: the pre-training step (engine_core._Step), the fine-tune step (finetune._EncoderStep) and the recognition forward
 (recognizer.RecModel).  One launch sequence, written once; what differs between the callers comes in as arguments:
 
   blocks   one dict per block under _EncWeights' key names ("norm1.weight", ..., "attn.qkv.weight", ..., "qkv_bias"; "g": the same names in the

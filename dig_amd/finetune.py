@@ -1,4 +1,8 @@
-"""Fine-tune TRAINING step of the recognition model on the MI355X -- SURVEY.md 8(f) row N1.
+"""Fine-tune TRAINING step of the recognition models on the MI355X -- SURVEY.md 8(f) row N1.  What every head shares is here once:
+`EncoderTrain`, the class between `recognizer.RecEncoder` and the three models (gradient arena, drop rates, initialisation, freezing, the
+`.train()` forward, the evaluation start of the heads without a decode graph), and `_EncoderStep` (arena lookups, the two streams, the encoder
+both ways, the classifier's backward).  `RecModelTrain` = `EncoderTrain` + `RecModel` and `_DecoderStep` are the transformer decoder's; the GRU
+attention head and the CTC head derive theirs in attn_recognizer.py / ctc_recognizer.py.
 
 Mirrors (label smoothing 0, as in README.md:92-118), including the stochastic regularisers `--drop`, `--attn_drop_rate`,
 `--drop_path` of the encoder and the recognition decoder's own dropout (0.1, hard-wired by models/decoder.py:13-18,141) -- masks
@@ -27,7 +31,7 @@ from . import arena
 from . import dropout as DR
 from . import encoder_blocks as EB
 from . import ops
-from .recognizer import RecModel, SeqCrossEntropyLoss, SeqLabelSmoothingCrossEntropyLoss  # noqa: F401  (the criteria of this step)
+from .recognizer import RecEncoder, RecModel, SeqCrossEntropyLoss, SeqLabelSmoothingCrossEntropyLoss  # noqa: F401  (the criteria of this step)
 
 BF16, F32 = torch.bfloat16, torch.float32
 cf = ctypes.c_float
@@ -45,27 +49,26 @@ def encoder_plan(M, rows):
     return EB.Plan(chain_ln=FT_MLP_CHAIN and M.F <= 2048 and ops.mlp_chain_supported(M.D, M.F, rows))
 
 
-# what a decoder layer's backward reads of its forward; cross: the saved state of the cross-attention form, opaque here
-_LayerSaved = namedtuple("_LayerSaved", "x h1 m1 r1 qkv a lse1 x1 m2 r2 cross a2 x2 h3 m3 r3 pre u")
+def _rate(name, value):
+    if not 0.0 <= float(value) < 1.0:
+        raise ValueError(f"{name} must be in [0, 1), got {float(value)}")
+    return float(value)
 
 
-class RecModelTrain(RecModel):
-    """`RecModel` with a gradient arena beside its parameter arena.  `.train()` forward = teacher-forced logits with autograd; `.eval()`
-    = greedy decode on the same weights."""
-    _step_cls = None                                    # set below (the forward / backward of one step)
+class EncoderTrain(RecEncoder):
+    """The training layer of every recognition model: `RecEncoder` with a gradient arena beside its parameter arena, the encoder's stochastic
+    regularisers, the reference's initialisation and the `.train()` forward, one autograd node around the head's step object (`_step_cls`)."""
+    _step_cls = None                                    # the forward / backward of one step: every head sets its own
+    _LAYER_NORMS = ()                                   # name prefixes of a head's LayerNorms that no "norm" in their module name tells
+    _ARENAS = ("flat_params", "flat_grads")
 
-    def __init__(self, args=None, *, drop_rate=None, attn_drop_rate=None, drop_path_rate=None, decoder_dropout=0.1, drop_seed=None, **kw):
+    def __init__(self, args=None, *, drop_rate=None, attn_drop_rate=None, drop_path_rate=None, drop_seed=None, **kw):
         """Drop rates: from `args` (--drop / --attn_drop_rate / --drop_path, run_class_finetuning.py:69-74 -> create_model,
-        :300-313) unless given; `decoder_dropout` = 0.1 is what `create_decoder` builds (models/decoder.py:13-18: TFDecoder's
-        default, not configurable in the reference).  drop_seed: base seed of the mask keys (default: torch.initial_seed())."""
+        :300-313) unless given.  drop_seed: base seed of the mask keys (default: torch.initial_seed())."""
         super().__init__(args, **kw)
-        self.drop_rate = float(getattr(args, "drop", 0.0) if drop_rate is None else drop_rate)
-        self.attn_drop_rate = float(getattr(args, "attn_drop_rate", 0.0) if attn_drop_rate is None else attn_drop_rate)
-        self.drop_path_rate = float(getattr(args, "drop_path", 0.0) if drop_path_rate is None else drop_path_rate)
-        self.decoder_dropout = float(decoder_dropout)
-        for name in ("drop_rate", "attn_drop_rate", "drop_path_rate", "decoder_dropout"):
-            if not 0.0 <= getattr(self, name) < 1.0:
-                raise ValueError(f"{name} must be in [0, 1), got {getattr(self, name)}")
+        self.drop_rate = _rate("drop_rate", getattr(args, "drop", 0.0) if drop_rate is None else drop_rate)
+        self.attn_drop_rate = _rate("attn_drop_rate", getattr(args, "attn_drop_rate", 0.0) if attn_drop_rate is None else attn_drop_rate)
+        self.drop_path_rate = _rate("drop_path_rate", getattr(args, "drop_path", 0.0) if drop_path_rate is None else drop_path_rate)
         # stochastic depth decay rule (modeling_finetune.py:273)
         self.dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
         self.drop_seed = torch.initial_seed() if drop_seed is None else int(drop_seed)
@@ -77,9 +80,9 @@ class RecModelTrain(RecModel):
     def init_weights(self):
         """The reference's initialisation, drawn from torch's CPU generator: encoder Linear weights xavier-uniform with zero
         biases and LayerNorm (1, 0) (`PretrainVisionTransformerEncoder._init_weights`, modeling_pretrain_vit.py:66-74); the
-        patch-embed convolution, the decoder and `linear_norm` keep PyTorch's defaults (nn.Conv2d / nn.Linear: U(-1/sqrt(fan_in),
-        1/sqrt(fan_in)) for weight and bias; nn.Embedding: N(0, 1); models/model_builder.py:78-89 adds nothing); mask_token,
-        q_bias, v_bias zero.  Fine-tuning then overwrites the encoder from the pre-training checkpoint (`load_pretrained`)."""
+        patch-embed convolution and the heads keep PyTorch's defaults (nn.Conv2d / nn.Linear: U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for
+        weight and bias; what else a head holds: its own `_init_tensor`); mask_token, q_bias, v_bias zero.  Fine-tuning then overwrites
+        the encoder from the pre-training checkpoint (`load_pretrained`)."""
         sd = OrderedDict((k, self._init_tensor(k, shp)) for k, shp in self.param_shapes().items())
         self.load_state_dict(sd)
 
@@ -87,23 +90,14 @@ class RecModelTrain(RecModel):
         enc = k.startswith("encoder.")
         if k.endswith("mask_token") or k.endswith("q_bias") or k.endswith("v_bias"):
             return torch.zeros(shp)
-        if "norm" in k.split(".")[-2] and len(shp) == 1 or k.startswith("linear_norm.1."):
+        if "norm" in k.split(".")[-2] and len(shp) == 1 or k.startswith(self._LAYER_NORMS):
             return torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
-        if k.endswith("trg_word_emb.weight"):
-            return torch.randn(shp)
-        if k.endswith(".weight"):
-            fan_in = 1
-            for d_ in shp[1:]:
-                fan_in *= d_
-            a = math.sqrt(6.0 / (shp[0] + shp[1])) if enc and len(shp) == 2 else 1.0 / math.sqrt(fan_in)   # xavier_uniform_ / kaiming_uniform_(a=sqrt(5))
+        if k.endswith(".weight"):                                              # xavier_uniform_ / kaiming_uniform_(a=sqrt(5))
+            a = math.sqrt(6.0 / (shp[0] + shp[1])) if enc and len(shp) == 2 else 1.0 / math.sqrt(math.prod(shp[1:]))
             return (torch.rand(shp) * 2 - 1) * a
         if enc and "patch_embed" not in k:                                     # biases
             return torch.zeros(shp)
-        w = self.param_shapes()[k[:-4] + "weight"]
-        fan_in = 1
-        for d_ in w[1:]:
-            fan_in *= d_
-        return (torch.rand(shp) * 2 - 1) / math.sqrt(fan_in)
+        return (torch.rand(shp) * 2 - 1) / math.sqrt(math.prod(self.param_shapes()[k[:-4] + "weight"][1:]))
 
     def load_pretrained(self, checkpoint, model_key="model|module", prefix=""):
         """run_class_finetuning.py:362-440 for the simmim_vit encoders: pick `checkpoint[model_key]`, strip a `backbone.` prefix,
@@ -154,8 +148,6 @@ class RecModelTrain(RecModel):
     def no_weight_decay(self):
         return {"encoder.pos_embed", "encoder.cls_token"}
 
-    _ARENAS = ("flat_params", "flat_grads")
-
     def _own_arenas(self, flat_params):
         super()._own_arenas(flat_params)
         self.flat_grads = torch.zeros_like(flat_params)
@@ -180,9 +172,8 @@ class RecModelTrain(RecModel):
     def forward(self, x):
         if not self.training:
             return super().forward(x)
-        images, targets, lens = x
-        if not images.is_cuda:
-            raise RuntimeError("dig_amd.RecModelTrain runs on an MI355X (cuda device) only; there is no CPU fallback")
+        images = self._device_images(x)
+        _, targets, lens = x
         if self._dev != images.device or self._shadow is None:
             self._bind(images.device)
         anchor = getattr(self, "_anchor", None)
@@ -190,6 +181,15 @@ class RecModelTrain(RecModel):
             anchor = self._anchor = torch.zeros(1, device=images.device, requires_grad=True)
         logits = _RecTrainFn.apply(anchor, self, images, targets.to(images.device), lens.to(images.device))
         return logits, None, None, None
+
+    def eval_tokens(self, images):
+        """What the evaluation of a head that has no decode graph starts with: a step object on freshly cast weights and the encoder's
+        tokens from the training step's walk without dropout keys (and, like it, with the blocks' activations kept)."""
+        if self._dev != images.device or self._shadow is None:
+            self._bind(images.device)
+        step = self._step_cls(self)
+        self.refresh_shadow()
+        return step, self.encoder_front(images, encoder_plan(self, images.shape[0] * self.N), True, frozen=self.frozen_blocks)[0]
 
 
 class ModelEma:
@@ -237,8 +237,10 @@ class FlatGradComm:
         self.dist.all_reduce(model.flat_grads, group=self.group)
 
 
-class _TrainStep:
-    """One forward / backward of the model; all activations needed by the backward are kept on this object."""
+class _EncoderStep:
+    """What one forward / backward of every recognition model shares: lookups by name in the three arenas, the two streams of the backward,
+    the encoder both ways and the padded classifier's backward.  A head's step class adds `forward` and `backward`; all activations
+    needed by the backward are kept on this object."""
 
     def __init__(self, model):
         self.m = model
@@ -277,7 +279,7 @@ class _TrainStep:
             t.record_stream(self._side_st)
 
     def encoder_forward(self, images):
-        """RecModel.encoder_front under this step's dropout / drop-path keys; returns the normalised tokens [B*N, D] (bf16) and keeps what
+        """RecEncoder.encoder_front under this step's dropout / drop-path keys; returns the normalised tokens [B*N, D] (bf16) and keeps what
         `encoder_backward` needs."""
         M = self.m
         M.refresh_shadow()
@@ -297,7 +299,52 @@ class _TrainStep:
         enc, (self.images, self.zmask, self.enc_saved, self.enc_last) = M.encoder_front(images, eplan, True, drops=self.ds_enc, frozen=M.frozen_blocks)
         return enc
 
-    # ---------------------------------------------------------------- forward
+    def encoder_backward(self, denc):
+        """denc: bf16 [B*N, D] gradient w.r.t. the tokens `encoder_forward` returned (call `begin_backward` first)."""
+        M = self.m
+        dev = denc.device
+        D, H, N = M.D, M.H, M.N
+        x_last, emu, ers, enc = self.enc_last
+        dx = ops.layernorm_bwd(denc, x_last, self.p("encoder.norm.weight"), self.p("encoder.norm.bias"), emu, ers, None, self.g("encoder.norm.weight"),
+                               self.g("encoder.norm.bias"))
+        # ---- encoder blocks (encoder_blocks.backward: one view, no masking; frozen blocks are a prefix: the chain stops above them).  The four
+        # weight gradients of a block as ONE grouped launch on the second stream, every reduction handed over as it becomes ready
+        blocks = M.enc_blocks()
+        grouped = (ops.WGRAD_GROUP and not FT_BATCH_REDUCE and
+                   all(ops.wgrad_group_route(o, i_, self.B * N) is not None for o, i_ in ((M.F, D), (D, M.F), (3 * D, D), (D, D))))
+        wT = None
+        if getattr(self, "use_chain", False) and M.frozen_blocks < M.depth:
+            # K-contiguous copies of the MLP weights for the fused backward (one launch per weight shape, 1.2 MB per matrix)
+            live = blocks[M.frozen_blocks:]
+            wT = [None] * M.frozen_blocks + list(zip(ops.transpose_bf16_multi([b_["mlp.fc2.weight"] for b_ in live]),
+                                                     ops.transpose_bf16_multi([b_["mlp.fc1.weight"] for b_ in live])))
+        plan = EB.Plan(chain_bwd=wT is not None, fused_qv=FT_FUSED_QV, grouping="block" if grouped else "off", side_each=True,
+                       batch_reduce=FT_BATCH_REDUCE)
+        dx = EB.backward(plan, blocks, self.enc_saved, dx, wT, self.B, H, self.side, first=M.frozen_blocks, drops=self.ds_enc)
+        if "encoder.patch_embed.proj.weight" in M.frozen:
+            return
+        gtok = torch.zeros(D, device=dev, dtype=F32)                          # mask_token takes no part at fine-tune: gradient discarded
+        ops.patch_embed_bwd_mfma(dx, self.images, self.zmask, self.g("encoder.patch_embed.proj.weight").view(D, 48),
+                                 self.g("encoder.patch_embed.proj.bias"), gtok, D, M.gh, M.gw)
+
+    def classifier_backward(self, dl, o, weight, bias, out_kind=ops.OUT_BF16, classes=None):
+        """The backward of the classifier zero-padded to CLS_PAD rows (self.cls_w): dl bf16 [rows, CLS_PAD], the gradient of its logits with
+        zero pad columns; o [rows, d], its input; classes: its true rows (default nb_classes).  Weight and bias gradients on the second stream
+        (the column sums through a padded vector); returns the gradient w.r.t. o, bf16 or (out_kind = ops.OUT_F32) fp32."""
+        C, (rows, d) = classes or self.m.nb_classes, o.shape
+        self.side(lambda: ops.wgrad(dl, o, self.g(weight), C, d, rows), dl, o)
+        cs = torch.zeros(CLS_PAD, device=dl.device, dtype=F32)
+        self.side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), self.g(bias).add_(cs[:C])), dl, cs)
+        return ops.gemm(dl, self.cls_w, rows, d, CLS_PAD, tb=True, out_kind=out_kind)
+
+
+# what a decoder layer's backward reads of its forward; cross: the saved state of the cross-attention form, opaque here
+_LayerSaved = namedtuple("_LayerSaved", "x h1 m1 r1 qkv a lse1 x1 m2 r2 cross a2 x2 h3 m3 r3 pre u")
+
+
+class _DecoderStep(_EncoderStep):
+    """One forward / backward of `RecModelTrain`: linear_norm and the transformer decoder under teacher forcing."""
+
     def forward(self, images, targets, lens):
         M = self.m
         dev = images.device
@@ -390,45 +437,6 @@ class _TrainStep:
         torch.cuda.current_stream(self.mem.device).wait_event(ev)
         return kept
 
-    def encoder_backward(self, denc):
-        """denc: bf16 [B*N, D] gradient w.r.t. the tokens `encoder_forward` returned (call `begin_backward` first)."""
-        M = self.m
-        dev = denc.device
-        D, H, N = M.D, M.H, M.N
-        x_last, emu, ers, enc = self.enc_last
-        dx = ops.layernorm_bwd(denc, x_last, self.p("encoder.norm.weight"), self.p("encoder.norm.bias"), emu, ers, None, self.g("encoder.norm.weight"),
-                               self.g("encoder.norm.bias"))
-        # ---- encoder blocks (encoder_blocks.backward: one view, no masking; frozen blocks are a prefix: the chain stops above them).  The four
-        # weight gradients of a block as ONE grouped launch on the second stream, every reduction handed over as it becomes ready
-        blocks = M.enc_blocks()
-        grouped = (ops.WGRAD_GROUP and not FT_BATCH_REDUCE and
-                   all(ops.wgrad_group_route(o, i_, self.B * N) is not None for o, i_ in ((M.F, D), (D, M.F), (3 * D, D), (D, D))))
-        wT = None
-        if getattr(self, "use_chain", False) and M.frozen_blocks < M.depth:
-            # K-contiguous copies of the MLP weights for the fused backward (one launch per weight shape, 1.2 MB per matrix)
-            live = blocks[M.frozen_blocks:]
-            wT = [None] * M.frozen_blocks + list(zip(ops.transpose_bf16_multi([b_["mlp.fc2.weight"] for b_ in live]),
-                                                     ops.transpose_bf16_multi([b_["mlp.fc1.weight"] for b_ in live])))
-        plan = EB.Plan(chain_bwd=wT is not None, fused_qv=FT_FUSED_QV, grouping="block" if grouped else "off", side_each=True,
-                       batch_reduce=FT_BATCH_REDUCE)
-        dx = EB.backward(plan, blocks, self.enc_saved, dx, wT, self.B, H, self.side, first=M.frozen_blocks, drops=self.ds_enc)
-        if "encoder.patch_embed.proj.weight" in M.frozen:
-            return
-        gtok = torch.zeros(D, device=dev, dtype=F32)                          # mask_token takes no part at fine-tune: gradient discarded
-        ops.patch_embed_bwd_mfma(dx, self.images, self.zmask, self.g("encoder.patch_embed.proj.weight").view(D, 48),
-                                 self.g("encoder.patch_embed.proj.bias"), gtok, D, M.gh, M.gw)
-
-    def classifier_backward(self, dl, o, weight, bias, out_kind=ops.OUT_BF16):
-        """The backward of the classifier zero-padded to CLS_PAD rows (self.cls_w): dl bf16 [rows, CLS_PAD], the gradient of its logits with
-        zero pad columns; o [rows, d], its input.  Weight and bias gradients on the second stream (the column sums through a padded vector);
-        returns the gradient w.r.t. o, bf16 or (out_kind = ops.OUT_F32) fp32."""
-        C, (rows, d) = self.m.nb_classes, o.shape
-        self.side(lambda: ops.wgrad(dl, o, self.g(weight), C, d, rows), dl, o)
-        cs = torch.zeros(CLS_PAD, device=dl.device, dtype=F32)
-        self.side(lambda: (ops.colsum(dl, cs, cols=CLS_PAD), self.g(bias).add_(cs[:C])), dl, cs)
-        return ops.gemm(dl, self.cls_w, rows, d, CLS_PAD, tb=True, out_kind=out_kind)
-
-    # ---------------------------------------------------------------- backward
     def backward(self, dlogits_btc):
         """dlogits_btc: fp32 [B, T, C] gradient w.r.t. the returned logits."""
         M = self.m
@@ -499,7 +507,19 @@ class _TrainStep:
         main.wait_stream(sd)
 
 
-RecModelTrain._step_cls = _TrainStep
+class RecModelTrain(EncoderTrain, RecModel):
+    """The training form of `RecModel`.  `.train()` forward = teacher-forced logits with autograd; `.eval()` = greedy decode on the same
+    weights.  `decoder_dropout` = 0.1 is what `create_decoder` builds (models/decoder.py:13-18: TFDecoder's default, not configurable in the
+    reference)."""
+    _step_cls, _LAYER_NORMS = _DecoderStep, ("linear_norm.1.",)
+
+    def __init__(self, args=None, *, decoder_dropout=0.1, **kw):
+        self.decoder_dropout = _rate("decoder_dropout", decoder_dropout)
+        super().__init__(args, **kw)
+
+    def _init_tensor(self, k, shp):
+        """The decoder and `linear_norm` keep PyTorch's defaults (models/model_builder.py:78-89 adds nothing); nn.Embedding: N(0, 1)."""
+        return torch.randn(shp) if k.endswith("trg_word_emb.weight") else super()._init_tensor(k, shp)
 
 
 class _RecTrainFn(torch.autograd.Function):

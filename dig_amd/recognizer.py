@@ -9,15 +9,15 @@ models/decoder.py:224-252; encoder factory `simmim_vit_small_patch4_32x128`, mod
 What differs from the reference: the decoder keeps a K/V cache (one token per step instead of re-running all 26 positions 25
 times -- same result, position t only depends on tokens <= t) and the cross-attention keys/values of the encoder memory are
 projected once per layer -- or whatever else the decoder's cross-attention form caches of it: the forms, their extra parameters and their parts
-of training and evaluation live in dig_amd/decoder_cross.py, and the constructor picks one.  The encoder front and the memory projection are written once here for evaluation and for the fine-tune training
-step (dig_amd/finetune.py), which passes its own plan and dropout keys; the sequence losses at the end carry their gradient.  There is no
-CPU fallback."""
+of training and evaluation live in dig_amd/decoder_cross.py, and the constructor picks one.  `RecEncoder` is the encoder with its arenas, the base
+of every recognition model (the GRU attention and CTC heads derive from it through dig_amd/finetune.py, not from `RecModel`); its encoder front and
+`RecModel`'s memory projection are written once here for evaluation and for the fine-tune training step, which passes its own plan and dropout
+keys; the sequence losses at the end carry their gradient.  There is no CPU fallback."""
 import ctypes
+import types
 from collections import OrderedDict
 
 import numpy as np
-import types
-
 import torch
 
 from . import _lib as L
@@ -48,71 +48,38 @@ def _sinusoid(n_position, d_hid):
     return tab
 
 
-class RecModel(torch.nn.Module):
-    def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, n_layers=None, d_model=None, n_head=None, d_k=64,
-                 d_inner=None, nb_classes=97, max_len=25, n_position=200, use_1d_attdec=False, text_cond_vis=False):
+class RecEncoder(torch.nn.Module):
+    """The fine-tune encoder with its arenas, whatever reads its tokens: configuration, the placed parameter arena and its bf16 shadow, the
+    state dict, the bound views and the encoder forward.  A recognition head derives from it and names the parameters behind the encoder
+    (`head_shapes`, in state-dict order) and, if its forward reads bound views, those (`head_views`)."""
+    gh, gw, N = 8, 32, 256
+    beam_width = 0                                      # (the autoregressive --beam_width: RecModel's decoder alone has one)
+    _ARENAS = ("flat_params",)
+
+    def __init__(self, args=None, *, embed_dim=None, depth=12, num_heads=None, nb_classes=97, max_len=25):
         super().__init__()
-        if args is not None:
-            embed_dim, num_heads = ENCODERS[args.model]
-            if args.decoder_name == "decoupled_tf_decoder":
-                raise NotImplementedError("decoupled_tf_decoder is not built: DecoupledTransformerDecoderLayer.forward reads cls_query_attn_maps.size(), "
-                                          "and RecModel.forward passes None for it with every encoder factory of the reference")
-            dk = DECODERS[args.decoder_name]
-            n_layers, d_model, n_head, d_k, d_inner = dk["n_layers"], dk["d_model"], dk["n_head"], dk["d_k"], dk["d_inner"]
-            nb_classes, max_len = args.nb_classes, args.max_len
-            use_1d_attdec = bool(getattr(args, "use_1d_attdec", False))
-            text_cond_vis = bool(getattr(args, "text_cond_vis", False))
-            if getattr(args, "insert_sem", False):
-                raise NotImplementedError("semantic insertion (--insert_sem) is not built: no encoder factory of the reference enables it")
+        if args is not None:                                                # as in run_class_finetuning.py
+            (embed_dim, num_heads), nb_classes, max_len = ENCODERS[args.model], args.nb_classes, args.max_len
         if embed_dim // num_heads != 64:
             raise NotImplementedError("encoder head dimension 64 only")
-        if d_k not in HEAD_DIMS:
-            raise NotImplementedError(f"decoder head dimension {d_k}: the attention kernels are built for {HEAD_DIMS}")
         self.D, self.H, self.depth, self.F = embed_dim, num_heads, depth, 4 * embed_dim
-        self.gh, self.gw, self.N = 8, 32, 256
-        # --use_1d_attdec (run_class_finetuning.py:89, model_builder.py:145-148): the decoder attends over the gw column means of the
-        # token grid instead of all gh*gw tokens
-        self.use_1d_attdec = bool(use_1d_attdec)
-        self.n_mem = self.gw if self.use_1d_attdec else self.N
-        # --text_cond_vis (run_class_finetuning.py, models/decoder.py:13-73): the decoder's cross-attention is the text-conditional one.
-        # Which form of the cross-attention runs (dig_amd/decoder_cross.py) is decided here and nowhere else
-        self.text_cond_vis = bool(text_cond_vis)
-        self.cross = decoder_cross.choose(self.text_cond_vis, self.n_mem, d_model, n_head, d_k)
-        self.n_layers, self.d, self.nh, self.dk, self.d_inner = n_layers, d_model, n_head, d_k, d_inner
-        self.nb_classes, self.max_len, self.n_position = nb_classes, max_len, n_position
-        self.start_idx = nb_classes                                         # decoder.py:149
-        self.use_hip_graph = True
-        self.beam_width = int(getattr(args, "beam_width", 0) or 0) if args is not None else 0      # model_builder.py:110
-        self.eos = 94                                                       # TFDecoder.beam_search's default (decoder.py:254)
+        self.nb_classes, self.max_len = nb_classes, max_len
         # ONE weight store: an fp32 arena laid out by arena.place (each tensor padded to the granule, q|k|v and k|v projection weights
         # adjacent, so the fused projections are views) and its bf16 shadow, the GEMM operands; everything the kernels read is a view of the two
         self._offsets = OrderedDict(self.param_shapes())
         self.n_flat = arena.place(self._offsets)
-        self._loaded = False
-        self._dev = None
+        self._loaded, self._dev, self._tables = False, None, {}
         self._own_arenas(torch.zeros(self.n_flat, dtype=F32))
 
     # ------------------------------------------------------------------ state
     def param_shapes(self):
-        D, d, hk = self.D, self.d, self.nh * self.dk
-        o = arena.encoder_shapes("encoder.", D, self.F, self.depth, True)
-        o["decoder.trg_word_emb.weight"] = (self.nb_classes + 1, d)
-        for i in range(self.n_layers):
-            p = f"decoder.layer_stack.{i}."
-            for n in ("norm1", "norm2", "norm3"):
-                o[p + n + ".weight"] = (d,); o[p + n + ".bias"] = (d,)
-            for a in ("self_attn", "enc_attn"):
-                for w in ("linear_q", "linear_k", "linear_v"):
-                    o[p + a + "." + w + ".weight"] = (hk, hk)
-                o[p + a + ".fc.weight"] = (d, hk)
-            o.update(self.cross.extra_shapes(p + "enc_attn."))
-            o[p + "mlp.w_1.weight"] = (self.d_inner, d); o[p + "mlp.w_1.bias"] = (self.d_inner,)
-            o[p + "mlp.w_2.weight"] = (d, self.d_inner); o[p + "mlp.w_2.bias"] = (d,)
-        o["decoder.layer_norm.weight"] = (d,); o["decoder.layer_norm.bias"] = (d,)
-        o["decoder.classifier.weight"] = (self.nb_classes, d); o["decoder.classifier.bias"] = (self.nb_classes,)
-        o["linear_norm.0.weight"] = (d, D); o["linear_norm.0.bias"] = (d,)
-        o["linear_norm.1.weight"] = (d,); o["linear_norm.1.bias"] = (d,)
-        return o
+        return OrderedDict([*arena.encoder_shapes("encoder.", self.D, self.F, self.depth, True).items(), *self.head_shapes().items()])
+
+    def head_shapes(self):
+        raise NotImplementedError("a recognition head names its parameters")
+
+    def head_views(self, w, p, s):
+        """Add to `w` what the head's forward reads; p / s: name -> view of the fp32 arena / of the bf16 shadow."""
 
     def _view(self, flat, k):
         return arena.view(flat, self._offsets[k])
@@ -138,8 +105,6 @@ class RecModel(torch.nn.Module):
 
     def state_dict(self, *a, **k):
         return OrderedDict((n, self._view(self.flat_params, n).detach().to("cpu", copy=True)) for n in self._offsets)
-
-    _ARENAS = ("flat_params",)
 
     def to(self, device=None, *a, **k):
         if device is not None:
@@ -172,37 +137,24 @@ class RecModel(torch.nn.Module):
         cb[:w.shape[0]].copy_(b)
         return cw, cb
 
+    def _table(self, key, make):
+        """A constant table on the arenas' device, made once per device (own storage: it is no parameter)."""
+        dev = self.flat_params.device
+        if key not in self._tables or self._tables[key][0] != dev:
+            self._tables[key] = (dev, make().to(dev).contiguous())
+        return self._tables[key][1]
+
     def _build_views(self):
         """Everything the forward reads, as views of the fp32 arena (vectors, embeddings) and of the bf16 shadow (GEMM operands); own
-        storage only for the position tables and the classifier padded to a multiple of 8 rows."""
-        P, S, D, has = self.flat_params, self._shadow, self.D, self._offsets.__contains__
-        fused = lambda flat, first, count: arena.fused(flat, self._offsets, first, count)
+        storage only for the position tables and what a head pads."""
+        P, S, D = self.flat_params, self._shadow, self.D
         p, s = (lambda k: self._view(P, k)), (lambda k: self._view(S, k))
-        dev = P.device
         w = {"enc_blocks": arena.enc_block_views(self._offsets, "encoder.", self.depth, D, P, S)}
         w["pe_w"], w["pe_b"] = p("encoder.patch_embed.proj.weight").view(D, 48), p("encoder.patch_embed.proj.bias")
         w["mask_token"] = p("encoder.mask_token").view(D)
-        tabs = getattr(self, "_tables", None)
-        if tabs is None or tabs[0] != dev:                                  # once per device
-            tabs = self._tables = (dev, arena.encoder_pos_table(self.N, D).to(dev).contiguous(), _sinusoid(self.n_position, self.d).to(dev).contiguous())
-        _, w["enc_pos"], w["pos"] = tabs
+        w["enc_pos"] = self._table("enc_pos", lambda: arena.encoder_pos_table(self.N, D))
         w["enc_nw"], w["enc_nb"] = p("encoder.norm.weight"), p("encoder.norm.bias")
-        if has("linear_norm.0.weight"):
-            w["ln_w"], w["ln_b"] = s("linear_norm.0.weight"), p("linear_norm.0.bias")
-            w["ln_nw"], w["ln_nb"] = p("linear_norm.1.weight"), p("linear_norm.1.bias")
-        if has("decoder.classifier.weight"):
-            w["emb"] = p("decoder.trg_word_emb.weight")
-            for i in range(self.n_layers):
-                l = f"decoder.layer_stack.{i}."
-                w[l] = dict(n1w=p(l + "norm1.weight"), n1b=p(l + "norm1.bias"), n2w=p(l + "norm2.weight"), n2b=p(l + "norm2.bias"),
-                            n3w=p(l + "norm3.weight"), n3b=p(l + "norm3.bias"), qkv=fused(S, l + "self_attn.linear_q.weight", 3),
-                            fc=s(l + "self_attn.fc.weight"), q2=s(l + "enc_attn.linear_q.weight"),
-                            kv2=fused(S, l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
-                            w1=s(l + "mlp.w_1.weight"), b1=p(l + "mlp.w_1.bias"), w2=s(l + "mlp.w_2.weight"), b2=p(l + "mlp.w_2.bias"))
-                w[l].update(self.cross.views(l + "enc_attn.", p, s))
-            w["fnw"], w["fnb"] = p("decoder.layer_norm.weight"), p("decoder.layer_norm.bias")
-            w["Cp"] = (self.nb_classes + 7) // 8 * 8
-            w["cls_w"], w["cls_b"] = torch.zeros((w["Cp"], self.d), device=dev, dtype=BF16), torch.zeros(w["Cp"], device=dev, dtype=F32)
+        self.head_views(w, p, s)
         return w
 
     def _views(self):
@@ -223,17 +175,11 @@ class RecModel(torch.nn.Module):
         self._dev = dev
         return self._views()
 
-    def _prepare(self, dev):
-        """Ready for the eval forward on `dev`: views bound, and what is derived from the fp32 arena -- the bf16 shadow (one cast launch) and
-        the padded classifier -- refreshed IN PLACE if the arena was written since.  No address changes, so a captured decode graph stays
-        valid across weight updates: the refresh is ordered before the replay on the caller's stream."""
-        w = self._bind(dev)
-        ver = (self._weights_version, self.flat_params._version)
-        if self._fresh != ver:
-            self.refresh_shadow()
-            if "cls_w" in w:
-                self.padded_classifier("decoder.classifier.weight", "decoder.classifier.bias", w["Cp"], out=(w["cls_w"], w["cls_b"]))
-            self._fresh = ver
+    def _device_images(self, x):
+        images = x[0] if isinstance(x, (tuple, list)) else x
+        if not images.is_cuda:
+            raise RuntimeError(f"dig_amd.{type(self).__name__} runs on an MI355X (cuda device) only; there is no CPU fallback")
+        return images
 
     # ------------------------------------------------------------------ forward pieces
     def enc_blocks(self):
@@ -256,6 +202,92 @@ class RecModel(torch.nn.Module):
     def encoder_features(self, images):
         """PretrainVisionTransformerEncoder.forward_features(x, mask=None): bf16 [B*256, D] -- the plain form, nothing kept."""
         return self.encoder_front(images, EB.Plan(), False)[0]
+
+
+class RecModel(RecEncoder):
+    """The encoder followed by `linear_norm` and the transformer decoder: greedy decode and beam search on a K/V cache."""
+
+    def __init__(self, args=None, *, n_layers=None, d_model=None, n_head=None, d_k=64, d_inner=None, n_position=200, use_1d_attdec=False,
+                 text_cond_vis=False, **encoder):
+        if args is not None:
+            if args.decoder_name == "decoupled_tf_decoder":
+                raise NotImplementedError("decoupled_tf_decoder is not built: DecoupledTransformerDecoderLayer.forward reads cls_query_attn_maps.size(), "
+                                          "and RecModel.forward passes None for it with every encoder factory of the reference")
+            dk = DECODERS[args.decoder_name]
+            n_layers, d_model, n_head, d_k, d_inner = dk["n_layers"], dk["d_model"], dk["n_head"], dk["d_k"], dk["d_inner"]
+            use_1d_attdec = bool(getattr(args, "use_1d_attdec", False))
+            text_cond_vis = bool(getattr(args, "text_cond_vis", False))
+            if getattr(args, "insert_sem", False):
+                raise NotImplementedError("semantic insertion (--insert_sem) is not built: no encoder factory of the reference enables it")
+        if d_k not in HEAD_DIMS:
+            raise NotImplementedError(f"decoder head dimension {d_k}: the attention kernels are built for {HEAD_DIMS}")
+        # --use_1d_attdec (run_class_finetuning.py:89, model_builder.py:145-148): the decoder attends over the gw column means of the
+        # token grid instead of all gh*gw tokens
+        self.use_1d_attdec = bool(use_1d_attdec)
+        self.n_mem = self.gw if self.use_1d_attdec else self.N
+        # --text_cond_vis (run_class_finetuning.py, models/decoder.py:13-73): the decoder's cross-attention is the text-conditional one.
+        # Which form of the cross-attention runs (dig_amd/decoder_cross.py) is decided here and nowhere else
+        self.text_cond_vis = bool(text_cond_vis)
+        self.cross = decoder_cross.choose(self.text_cond_vis, self.n_mem, d_model, n_head, d_k)
+        self.n_layers, self.d, self.nh, self.dk, self.d_inner, self.n_position = n_layers, d_model, n_head, d_k, d_inner, n_position
+        super().__init__(args, **encoder)                                   # (lays the arena out: the decoder's shapes are known by now)
+        self.start_idx = self.nb_classes                                    # decoder.py:149
+        self.use_hip_graph = True
+        self.beam_width = int(getattr(args, "beam_width", 0) or 0) if args is not None else 0      # model_builder.py:110
+        self.eos = 94                                                       # TFDecoder.beam_search's default (decoder.py:254)
+
+    def head_shapes(self):
+        D, d, hk, o = self.D, self.d, self.nh * self.dk, OrderedDict()
+        o["decoder.trg_word_emb.weight"] = (self.nb_classes + 1, d)
+        for i in range(self.n_layers):
+            p = f"decoder.layer_stack.{i}."
+            for n in ("norm1", "norm2", "norm3"):
+                o[p + n + ".weight"] = (d,); o[p + n + ".bias"] = (d,)
+            for a in ("self_attn", "enc_attn"):
+                for w in ("linear_q", "linear_k", "linear_v"):
+                    o[p + a + "." + w + ".weight"] = (hk, hk)
+                o[p + a + ".fc.weight"] = (d, hk)
+            o.update(self.cross.extra_shapes(p + "enc_attn."))
+            o[p + "mlp.w_1.weight"] = (self.d_inner, d); o[p + "mlp.w_1.bias"] = (self.d_inner,)
+            o[p + "mlp.w_2.weight"] = (d, self.d_inner); o[p + "mlp.w_2.bias"] = (d,)
+        o["decoder.layer_norm.weight"] = (d,); o["decoder.layer_norm.bias"] = (d,)
+        o["decoder.classifier.weight"] = (self.nb_classes, d); o["decoder.classifier.bias"] = (self.nb_classes,)
+        o["linear_norm.0.weight"] = (d, D); o["linear_norm.0.bias"] = (d,)
+        o["linear_norm.1.weight"] = (d,); o["linear_norm.1.bias"] = (d,)
+        return o
+
+    def head_views(self, w, p, s):
+        """linear_norm, the decoder layers (fused q|k|v and k|v projections as views) and, with storage of their own, the sinusoid position
+        table and the classifier padded to a multiple of 8 rows."""
+        S, dev = self._shadow, self.flat_params.device
+        fused = lambda first, count: arena.fused(S, self._offsets, first, count)
+        w["pos"] = self._table("pos", lambda: _sinusoid(self.n_position, self.d))
+        w["ln_w"], w["ln_b"] = s("linear_norm.0.weight"), p("linear_norm.0.bias")
+        w["ln_nw"], w["ln_nb"] = p("linear_norm.1.weight"), p("linear_norm.1.bias")
+        w["emb"] = p("decoder.trg_word_emb.weight")
+        for i in range(self.n_layers):
+            l = f"decoder.layer_stack.{i}."
+            w[l] = dict(n1w=p(l + "norm1.weight"), n1b=p(l + "norm1.bias"), n2w=p(l + "norm2.weight"), n2b=p(l + "norm2.bias"),
+                        n3w=p(l + "norm3.weight"), n3b=p(l + "norm3.bias"), qkv=fused(l + "self_attn.linear_q.weight", 3),
+                        fc=s(l + "self_attn.fc.weight"), q2=s(l + "enc_attn.linear_q.weight"),
+                        kv2=fused(l + "enc_attn.linear_k.weight", 2), fc2=s(l + "enc_attn.fc.weight"),
+                        w1=s(l + "mlp.w_1.weight"), b1=p(l + "mlp.w_1.bias"), w2=s(l + "mlp.w_2.weight"), b2=p(l + "mlp.w_2.bias"))
+            w[l].update(self.cross.views(l + "enc_attn.", p, s))
+        w["fnw"], w["fnb"] = p("decoder.layer_norm.weight"), p("decoder.layer_norm.bias")
+        w["Cp"] = (self.nb_classes + 7) // 8 * 8
+        w["cls_w"], w["cls_b"] = torch.zeros((w["Cp"], self.d), device=dev, dtype=BF16), torch.zeros(w["Cp"], device=dev, dtype=F32)
+
+    # ------------------------------------------------------------------ forward pieces
+    def _prepare(self, dev):
+        """Ready for the eval forward on `dev`: views bound, and what is derived from the fp32 arena -- the bf16 shadow (one cast launch) and
+        the padded classifier -- refreshed IN PLACE if the arena was written since.  No address changes, so a captured decode graph stays
+        valid across weight updates: the refresh is ordered before the replay on the caller's stream."""
+        w = self._bind(dev)
+        ver = (self._weights_version, self.flat_params._version)
+        if self._fresh != ver:
+            self.refresh_shadow()
+            self.padded_classifier("decoder.classifier.weight", "decoder.classifier.bias", w["Cp"], out=(w["cls_w"], w["cls_b"]))
+            self._fresh = ver
 
     def linear_norm(self, enc):
         """linear_norm (model_builder.py:86-89): Linear + LayerNorm(eps 1e-5) on the feature map, or with use_1d_attdec on the column means of
@@ -377,9 +409,7 @@ class RecModel(torch.nn.Module):
     def forward(self, x):
         if self.training:
             raise NotImplementedError("the fine-tune training step (SURVEY.md 8f row N1) is not built; call .eval()")
-        images = x[0] if isinstance(x, (tuple, list)) else x
-        if not images.is_cuda:
-            raise RuntimeError("dig_amd.RecModel runs on an MI355X (cuda device) only; there is no CPU fallback")
+        images = self._device_images(x)
         if not self._loaded:
             raise RuntimeError("load_state_dict() first")
         self._prepare(images.device)

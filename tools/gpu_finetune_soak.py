@@ -31,7 +31,8 @@ for name, cls, kw in (("tf_decoder", RecModelTrain, dict(decoder_name="tf_decode
         scaler(loss, opt, clip_grad=5.0, parameters=None)
         if it % 10 == 0 or it == steps - 1:
             losses.append(loss.item()); mem.append(torch.cuda.max_memory_allocated() / 2 ** 20)
-    m.drop_rate = m.attn_drop_rate = 0.0; m.dpr = [0.0] * m.depth; m.decoder_dropout = 0.0
+    m.drop_rate = m.attn_drop_rate = 0.0; m.dpr = [0.0] * m.depth
+    if hasattr(m, "decoder_dropout"): m.decoder_dropout = 0.0   # (the transformer decoder's own)
     tf_pred = m((images, tg, lens))[0].detach().argmax(-1).cpu()                # teacher-forced, regularisers off
     m.eval()
     pred = m((images, None, None))[0].argmax(-1).cpu()

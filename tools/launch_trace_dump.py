@@ -232,6 +232,13 @@ def _gru_model(dev, **kw):
     return m
 
 
+def _ctc_model(dev, **kw):
+    from dig_amd.ctc_recognizer import CTCRecModelTrain
+    m = CTCRecModelTrain(embed_dim=128, depth=2, num_heads=2, nb_classes=97, max_len=8, **kw)
+    m._bind(dev)
+    return m
+
+
 def _train_step(m, images, targets, lens, crit):
     """One forward / loss / backward through the step object (what RecModelTrain.forward's autograd node runs)."""
     st = m._step_cls(m)
@@ -243,13 +250,14 @@ def _train_step(m, images, targets, lens, crit):
     return logits, loss.detach(), lg.grad
 
 
-def finetune(dev, make, lens_on_host=None, smoothing=None, steps=1, optimizer=False):
+def finetune(dev, make, lens_on_host=None, smoothing=None, steps=1, optimizer=False, ctc=False):
     from dig_amd import finetune as FT
+    from dig_amd.ctc_recognizer import SeqCTCLoss
 
     def run():
         m = make(dev).train()
         images, targets, lens = _batch(3, m.max_len, [8, 3, 5])
-        crit = FT.SeqCrossEntropyLoss() if smoothing is None else FT.SeqLabelSmoothingCrossEntropyLoss(smoothing)
+        crit = SeqCTCLoss() if ctc else FT.SeqCrossEntropyLoss() if smoothing is None else FT.SeqLabelSmoothingCrossEntropyLoss(smoothing)
         opt = None
         if optimizer:
             nl = m.get_num_layers()
@@ -321,6 +329,47 @@ def sample(dev):
     return run
 
 
+def ctc_eval(dev):
+    def run():
+        m = _ctc_model(dev).eval()
+        logits = m.logits(_batch(3, m.max_len, [8, 3, 5])[0])
+        out = {"logits": logits}
+        for tag, bw in (("greedy", None), ("beam4", 4)):
+            out.update({f"{tag}.{k}": v for k, v in zip(("ids", "score", "n"), m.decode(logits, bw))})
+        return out
+    return run
+
+
+def layout(dev):
+    """Arena offsets and seeded initial weights of the three models: per model one hash over [(name, offset, shape)] and n_flat, one over the
+    hashes of every tensor of the initial state_dict() (`--full`: each of them)."""
+    from dig_amd.attn_recognizer import AttnRecModelTrain
+    from dig_amd.ctc_recognizer import CTCRecModelTrain
+    from dig_amd.finetune import RecModelTrain
+    small = dict(model="simmim_vit_small_patch4_32x128", nb_classes=97, max_len=25, drop=0.1, attn_drop_rate=0.0, drop_path=0.1)
+    ns = lambda **kw: types.SimpleNamespace(**{**small, **kw})
+    builds = {"tiny_tf": lambda: _tf_model(dev), "tiny_gru": lambda: _gru_model(dev), "tiny_ctc": lambda: _ctc_model(dev),
+              "small_tf_decoder": lambda: RecModelTrain(ns(decoder_name="tf_decoder")),
+              "small_corres_small_tf_decoder": lambda: RecModelTrain(ns(decoder_name="corres_small_tf_decoder")),
+              "small_tf_decoder_text_cond_vis": lambda: RecModelTrain(ns(decoder_name="tf_decoder", text_cond_vis=True)),
+              "small_gru_args": lambda: AttnRecModelTrain(ns()), "small_ctc_args": lambda: CTCRecModelTrain(ns(ctc_beam_width=4))}
+
+    def run():
+        out = {}
+        for tag, build in builds.items():
+            torch.manual_seed(0)
+            m = build()
+            out[tag + ".offsets"] = sha([(k, s.offset, s.shape) for k, s in m._offsets.items()] + [m.n_flat])
+            each = [(k, sha(v)) for k, v in m.state_dict().items()]
+            out[tag + ".init"] = sha(each)
+            out[tag + ".config"] = sha((m.D, m.H, m.depth, m.F, m.nb_classes, m.max_len, m.drop_rate, m.attn_drop_rate, m.dpr, m.beam_width,
+                                        getattr(m, "ctc_beam_width", None)))
+            if FULL:
+                out.update({f"{tag}.init.{k}": h for k, h in each})
+        return out
+    return run
+
+
 def losses(dev):
     def run():
         from dig_amd import finetune as FT
@@ -369,12 +418,17 @@ def main():
         case("finetune_tf_tcv_1d", finetune(dev, lambda d: _tf_model(d, text_cond_vis=True, use_1d_attdec=True)))
         case("finetune_tf_hd24", finetune(dev, lambda d: _tf_model(d, **HD24)))
         case("finetune_tf_hd48", finetune(dev, lambda d: _tf_model(d, **HD48)))
+        case("finetune_ctc", finetune(dev, _ctc_model, ctc=True))
+        case("finetune_ctc_drop", finetune(dev, lambda d: _ctc_model(d, drop_rate=0.1, attn_drop_rate=0.1, drop_path_rate=0.1, drop_seed=3), ctc=True))
+        case("finetune_ctc_adamw_two_steps_reload", finetune(dev, _ctc_model, steps=2, optimizer=True, ctc=True))
         case("eval_greedy", decode(dev, 0))
         case("eval_beam3", decode(dev, 3))
         case("eval_greedy_tcv", decode(dev, 0, text_cond_vis=True))
         case("eval_beam3_tcv", decode(dev, 3, text_cond_vis=True))
         case("eval_greedy_hd24", decode(dev, 0, **HD24))
         case("gru_sample", sample(dev))
+        case("ctc_eval", ctc_eval(dev))
+        case("layout", layout(dev))
         case("losses", losses(dev))
 
 
