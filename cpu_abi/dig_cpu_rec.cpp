@@ -298,6 +298,59 @@ int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int bea
   return DIG_OK;
 }
 
+// dig_beam_step's rule (its statements), then the gather of the recurrent state by predecessor and the next step's target embedding
+int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
+                          long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in, const void* sbf_in_,
+                          float* s_out, void* sbf_out_, int S, const float* table, int E, void* inp_, int ld_inp, hipStream_t) {
+  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || !s_in || !sbf_in_ || !s_out || !sbf_out_ || !table || !inp_ || B <= 0 ||
+      C <= 0 || ld < C || S <= 0 || E <= 0 || ld_inp < E)
+    return DIG_ERR_ARG;
+  if (beam_width < 1 || beam_width > 8 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
+  const size_t rows = (size_t)B * beam_width * S;
+  auto overlap = [](const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+  };
+  if (overlap(s_in, s_out, rows * sizeof(float)) || overlap(sbf_in_, sbf_out_, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
+  const bf16_t* sbf_in = (const bf16_t*)sbf_in_;
+  bf16_t* sbf_out = (bf16_t*)sbf_out_;
+  bf16_t* inp = (bf16_t*)inp_;
+  const int bw = beam_width, n = bw * C;
+  for (int b = 0; b < B; ++b) {
+    std::vector<float> cand(n);
+    for (int k = 0; k < bw; ++k) {
+      const float* row = logits + (size_t)(b * bw + k) * ld;
+      float m, s;
+      row_max_sum(row, C, m, s);
+      const float lse = m + std::log(s);
+      for (int c = 0; c < C; ++c) cand[k * C + c] = seq_scores[b * bw + k] + (row[c] - lse);
+    }
+    for (int r = 0; r < bw; ++r) {
+      float bv = NEG_INF;
+      int bi = 0x7fffffff;
+      if (force_candidates) {
+        const long long f = force_candidates[b * bw + r];
+        bi = (int)(f < 0 ? 0 : (f >= n ? n - 1 : f));
+        bv = cand[bi];
+      } else {
+        for (int i = 0; i < n; ++i)
+          if (cand[i] > bv || (cand[i] == bv && i < bi)) { bv = cand[i]; bi = i; }
+        if (bi == 0x7fffffff) bi = r;
+        cand[bi] = NEG_INF;
+      }
+      const int sym = bi % C, j = b * bw + r;
+      const size_t pred = (size_t)(bi / C + b * bw);
+      symbols[j] = sym;
+      predecessors[j] = (long long)pred;
+      stored_scores[j] = bv;
+      seq_scores[j] = sym == eos ? NEG_INF : bv;
+      for (int c = 0; c < S; ++c) { s_out[(size_t)j * S + c] = s_in[pred * S + c]; sbf_out[(size_t)j * S + c] = sbf_in[pred * S + c]; }
+      for (int c = 0; c < E; ++c) inp[(size_t)j * ld_inp + c] = f2bf(table[(size_t)sym * E + c]);
+    }
+  }
+  return DIG_OK;
+}
+
 int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos, int B, int T,
                      unsigned char* match, hipStream_t) {
   if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
@@ -715,6 +768,39 @@ int dig_addattn_fwd(const void* xproj_, const void* sproj_, const float* w, cons
       float a = 0.f;
       for (int n = 0; n < N; ++n) a += v[n] * bf2f(x[((size_t)b * N + n) * X + c]);
       ctx[(size_t)b * ldc + c] = f2bf(a);
+    }
+  }
+  return DIG_OK;
+}
+
+// dig_addattn_fwd's loops for the K slots of a sample (sproj row / alpha row / context row b*K + k, tokens of sample b)
+int dig_addattn_fwd_slots(const void* xproj_, const void* sproj_, const float* w, const void* x_, float* alpha, void* ctx_, int ldc, int B, int N,
+                          int A, int X, int slots, hipStream_t) {
+  if (!xproj_ || !sproj_ || !w || !x_ || !ctx_ || B <= 0 || N <= 0 || A <= 0 || X <= 0 || (X & 1) || (ldc & 1)) return DIG_ERR_ARG;
+  if (N > 512 || A > 1024 || (A & 7) || slots < 1 || slots > 8) return DIG_ERR_UNSUPPORTED;
+  if (!aligned16(xproj_)) return DIG_ERR_ALIGN;
+  const bf16_t* xproj = (const bf16_t*)xproj_; const bf16_t* sproj = (const bf16_t*)sproj_; const bf16_t* x = (const bf16_t*)x_;
+  bf16_t* ctx = (bf16_t*)ctx_;
+  const int K = slots;
+#pragma omp parallel for
+  for (int r = 0; r < B * K; ++r) {
+    const int b = r / K;
+    std::vector<float> v(N);
+    float m = NEG_INF;
+    for (int n = 0; n < N; ++n) {
+      float acc = 0.f;
+      for (int a = 0; a < A; ++a) acc += w[a] * std::tanh(bf2f(sproj[(size_t)r * A + a]) + bf2f(xproj[((size_t)b * N + n) * A + a]));
+      v[n] = acc;
+      m = std::max(m, acc);
+    }
+    float sum = 0.f;
+    for (int n = 0; n < N; ++n) { v[n] = std::exp(v[n] - m); sum += v[n]; }
+    const float inv = 1.f / sum;
+    for (int n = 0; n < N; ++n) { v[n] *= inv; if (alpha) alpha[(size_t)r * N + n] = v[n]; }
+    for (int c = 0; c < X; ++c) {
+      float a = 0.f;
+      for (int n = 0; n < N; ++n) a += v[n] * bf2f(x[((size_t)b * N + n) * X + c]);
+      ctx[(size_t)r * ldc + c] = f2bf(a);
     }
   }
   return DIG_OK;

@@ -7,7 +7,9 @@ zero-padded to max_len -- and the greedy `sample`; `DecoderUnit` = additive atte
 Same state-dict keys as the reference (`decoder.decoder.attention_unit.{sEmbed,xEmbed,wEmbed}.*`, `decoder.decoder.tgt_embedding.weight`,
 `decoder.decoder.gru.{weight,bias}_{ih,hh}_l0`, `decoder.decoder.fc.*`).  Flat arenas, one autograd node, the encoder on the
 pre-training hot-path kernels (model and step on dig_amd.finetune.EncoderTrain / _EncoderStep); the head's steps run on `dig_gemm_bf16` + `dig_addattn_*` +
-`dig_gru_cell_*` (csrc/gru_attn.hip), weight gradients as ONE GEMM per weight over the stacked steps.  Beam search is not built."""
+`dig_gru_cell_*` (csrc/gru_attn.hip), weight gradients as ONE GEMM per weight over the stacked steps.  Evaluation decodes greedily (`sample`)
+or, with `--beam_width K` (1..8), by the head's `beam_search` (attn_decoder.py:84-200, which the reference carries and never reaches): the K
+hypotheses of a sample share one copy of its tokens (`dig_addattn_fwd_slots`) and `dig_attn_beam_advance` closes every step."""
 import math
 import types
 
@@ -19,6 +21,7 @@ from .finetune import EncoderTrain, _EncoderStep, CLS_PAD
 
 BF16, F32 = torch.bfloat16, torch.float32
 PRE = "decoder.decoder."
+MAX_BEAM_WIDTH = 8                                      # dig_addattn_fwd_slots / dig_attn_beam_advance: the slots of a sample in one workgroup
 
 
 class _AttnTrainStep(_EncoderStep):
@@ -38,14 +41,19 @@ class _AttnTrainStep(_EncoderStep):
                                      wih=w(PRE + "gru.weight_ih_l0"), bih=p(PRE + "gru.bias_ih_l0"),
                                      whh=w(PRE + "gru.weight_hh_l0"), bhh=p(PRE + "gru.bias_hh_l0"))
 
-    def gru_attention_step(self, hd, sbf, s_prev, inp, sproj, alpha, s_new, sbf_new, gates):
+    def gru_attention_step(self, hd, sbf, s_prev, inp, sproj, alpha, s_new, sbf_new, gates, slots=0):
         """One DecoderUnit step (attn_decoder.py:236-272) from the state sbf (bf16; s_prev: the same in fp32, None = zeros): sEmbed(state) ->
         additive attention over the tokens, whose context lands in inp[:, E:] behind the target embedding the caller put into inp[:, :E] ->
-        the two gate GEMMs -> the GRU cell.  Writes sproj, alpha, gates and the new state (s_new fp32, sbf_new bf16)."""
+        the two gate GEMMs -> the GRU cell.  Writes sproj, alpha, gates and the new state (s_new fp32, sbf_new bf16).  slots = K > 0 (beam
+        search): the rows are the K hypotheses of every sample over that sample's one copy of the tokens, and alpha may be None."""
         A, S, X, E, _ = self._w()
         B, N = sbf.shape[0], self.m.N
         ops.linear_fwd(sbf, hd.ws, bias=hd.bs, out=sproj)
-        L.call("dig_addattn_fwd", L.ptr(hd.xproj), L.ptr(sproj), L.ptr(hd.wv), L.ptr(hd.x), L.ptr(alpha), L.ptr(inp[:, E:]), E + X, B, N, A, X, L.stream())
+        if slots:
+            L.call("dig_addattn_fwd_slots", L.ptr(hd.xproj), L.ptr(sproj), L.ptr(hd.wv), L.ptr(hd.x), L.ptr(alpha), L.ptr(inp[:, E:]), E + X, B // slots, N, A,
+                   X, slots, L.stream())
+        else:
+            L.call("dig_addattn_fwd", L.ptr(hd.xproj), L.ptr(sproj), L.ptr(hd.wv), L.ptr(hd.x), L.ptr(alpha), L.ptr(inp[:, E:]), E + X, B, N, A, X, L.stream())
         gi = ops.linear_fwd(inp, hd.wih, bias=hd.bih)
         gh = ops.linear_fwd(sbf, hd.whh, bias=hd.bhh)
         L.call("dig_gru_cell_fwd", L.ptr(gi), L.ptr(gh), L.ptr(s_prev), L.ptr(s_new), L.ptr(sbf_new), L.ptr(gates), B, S, L.stream())
@@ -153,18 +161,22 @@ class _AttnTrainStep(_EncoderStep):
 
 class AttnRecModelTrain(EncoderTrain):
     """models.model_builder.AttnRecModel: `.train()` forward = teacher-forced logits [B, max_len, nb_classes] (+ three Nones),
-    `.eval()` forward = greedy `sample` probabilities, both as the reference returns them."""
+    `.eval()` forward = greedy `sample` probabilities, both as the reference returns them; built with args.beam_width = K in 1..8 the
+    `.eval()` forward is `beam_search`: token ids [B, max_len] (+ None, None, ones), as RecModel returns them under its beam."""
     _step_cls = _AttnTrainStep
 
     def __init__(self, args=None, *, sDim=512, attDim=512, **kw):
-        if getattr(args, "beam_width", 0):
-            # the reference never reaches AttentionRecognitionHead.beam_search: AttnRecModel.forward (model_builder.py:66-72) calls
-            # the head's __call__ (forward_train / sample) whatever args.beam_width says, and the method itself indexes with the float
-            # result of `candidates / num_classes` (attn_decoder.py:126-127).  Refused here rather than silently decoded greedily.
-            raise NotImplementedError("--beam_width with --decoder_type attention: the reference's AttnRecModel ignores it (greedy sample()); "
-                                      "beam search is built for tf_decoder")
+        # the reference never reaches AttentionRecognitionHead.beam_search: AttnRecModel.forward (model_builder.py:66-72) calls the head's
+        # __call__ (forward_train / sample) whatever args.beam_width says, and the method itself indexes with the float result of
+        # `candidates / num_classes` (attn_decoder.py:126-127).  Here args.beam_width = K > 0 makes the `.eval()` forward run that method,
+        # with the division an integer one; 0 keeps the greedy sample().
+        bw = int(getattr(args, "beam_width", 0) or 0)
+        if not 0 <= bw <= MAX_BEAM_WIDTH:
+            raise ValueError(f"beam_width {bw}: 0 (greedy sample) or a beam search of width 1..{MAX_BEAM_WIDTH}")
         self.sDim, self.attDim = sDim, attDim
         super().__init__(args, **kw)
+        self.beam_width = bw
+        self.eos = self.nb_classes - 3                                      # a vocabulary ends in EOS, PADDING, UNKNOWN (datasets.find_classes)
         if attDim % 8 or attDim > 1024 or sDim % 64 or (attDim + self.D) % 64:
             raise NotImplementedError("attDim must be a multiple of 8 (<= 1024), sDim and attDim + embed_dim multiples of 64")
 
@@ -221,9 +233,68 @@ class AttnRecModelTrain(EncoderTrain):
             y = tok.clone()
         return probs
 
+    # ------------------------------------------------------------------ eval: beam search (attn_decoder.py:84-200)
+    @torch.no_grad()
+    def beam_search(self, images, beam_width, eos=None, force_logits=None, force_decisions=None, return_logits=False):
+        """AttentionRecognitionHead.beam_search with `predecessors` an integer division (the reference's float result cannot index on a
+        current torch).  The K = beam_width hypotheses of a sample are rows b*K .. b*K + K - 1 of every per-step tensor and share the
+        sample's encoder tokens and xEmbed(x), which stay one copy per sample (`dig_addattn_fwd_slots`).  A step is 7 launches: the sEmbed
+        GEMM, the K-slot attention, the two gate GEMMs, the GRU cell, the classifier GEMM and `dig_attn_beam_advance`, which ranks the K*C
+        candidates by dig_beam_step's rule, moves every slot's recurrent state to that of its predecessor (attn_decoder.py:127-128; the
+        transformer decoder's beam never re-orders its slots) and writes the emitted symbols' embeddings for the next step.  The decisions
+        [T, B*K] go to the host once, into `recognizer.beam_backtrack` (the rule of :140-200).  Returns ids [B, max_len] int64.
+        Parity hooks: force_logits ([T, B*K, C] fp32) stand in for the classifier's outputs in the ranking; force_decisions ([T, B, K]
+        int64 candidate indices k*C + c) stand in for the top-K; return_logits also returns (logits [T, B*K, C], scores, predecessors,
+        symbols [T, B*K]) of the run."""
+        from .recognizer import beam_backtrack
+        K = int(beam_width)
+        if not 1 <= K <= MAX_BEAM_WIDTH:
+            raise ValueError(f"beam_width {beam_width}: a width of 1..{MAX_BEAM_WIDTH}")
+        eos = self.eos if eos is None else int(eos)
+        dev, B, N, T = images.device, images.shape[0], self.N, self.max_len
+        step, x = self.eval_tokens(images)
+        A, S, X, E, C = step._w()
+        hd = step.head_inputs(x)
+        cls_w, cb = self.padded_classifier(PRE + "fc.weight", PRE + "fc.bias", CLS_PAD)
+        emb = step.p(PRE + "tgt_embedding.weight")
+        R = B * K
+        s, sbf = torch.zeros((R, S), device=dev, dtype=F32), torch.zeros((R, S), device=dev, dtype=BF16)     # step 0: zero state (:97)
+        s_new, sbf_new = torch.empty_like(s), torch.empty_like(sbf)
+        inp = torch.empty((R, E + X), device=dev, dtype=BF16)
+        sproj = torch.empty((R, A), device=dev, dtype=BF16)
+        gates = torch.empty((R, 4 * S), device=dev, dtype=F32)
+        logit = torch.empty((R, CLS_PAD), device=dev, dtype=F32)
+        seq_scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+        seq_scores[::K] = 0.0                                                # only slot 0 of a sample is live at step 0 (:101-103)
+        syms = torch.empty((T, R), device=dev, dtype=torch.int64)
+        preds = torch.empty((T, R), device=dev, dtype=torch.int64)
+        scores = torch.empty((T, R), device=dev, dtype=F32)
+        forced = None if force_decisions is None else force_decisions.to(dev).long().reshape(T, R).contiguous()
+        flog = None if force_logits is None else force_logits.to(dev).float().contiguous()
+        kept = []
+        bos = torch.full((R,), C, device=dev, dtype=torch.int64)             # <BOS> = num_classes (:107)
+        L.call("dig_embed_rows", L.ptr(bos), L.ptr(emb), L.ptr(inp), E + X, R, E, C + 1, L.stream())
+        for t in range(T):
+            step.gru_attention_step(hd, sbf, s, inp, sproj, None, s_new, sbf_new, gates, slots=K)
+            ops.gemm(sbf_new, cls_w, R, CLS_PAD, S, out=logit, out_kind=ops.OUT_F32, bias=cb)
+            if return_logits:
+                kept.append(logit[:, :C].clone())
+            lg, ld = (logit, CLS_PAD) if flog is None else (flog[t], flog.shape[-1])
+            L.call("dig_attn_beam_advance", L.ptr(lg), ld, L.ptr(seq_scores), B, K, C, eos, L.ptr(syms[t]), L.ptr(preds[t]), L.ptr(scores[t]),
+                   L.ptr(forced[t]) if forced is not None else None, L.ptr(s_new), L.ptr(sbf_new), L.ptr(s), L.ptr(sbf), S, L.ptr(emb), E,
+                   L.ptr(inp), E + X, L.stream())
+        # one device -> host copy: float64 holds the fp32 scores (-inf included) and the small integers exactly
+        host = torch.stack([scores.double(), preds.double(), syms.double()]).cpu().numpy()
+        ids = beam_backtrack(host[0], host[1].astype("int64"), host[2].astype("int64"), B, K, eos).to(dev)
+        return (ids, torch.stack(kept), scores, preds, syms) if return_logits else ids
+
     def forward(self, x):
         if self.training:
             lens = x[2]
             self._steps_hint = int(lens.max()) if (torch.is_tensor(lens) and not lens.is_cuda and lens.numel()) else None
             return super().forward(x)
+        if self.beam_width > 0:
+            # token ids and an all-ones tensor in place of (probabilities, attention maps), as RecModel.forward returns them under a beam
+            ids = self.beam_search(self._device_images(x), self.beam_width)
+            return ids, None, None, torch.ones_like(ids)
         return self.sample(self._device_images(x)), None, None, None

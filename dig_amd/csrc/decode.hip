@@ -211,6 +211,91 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict_
   }
 }
 
+// What closes a step of AttentionRecognitionHead.beam_search (attn_decoder.py:116-138) for one sample, in one launch: beam_step_kernel's
+// ranking and bookkeeping, statement by statement (so its results are the same bits), then what the GRU head's next step needs and the
+// transformer decoder's does not -- the recurrent state of slot j becomes the state of its predecessor (fp32 and bf16 copies, gathered
+// into buffers distinct from their sources), and the embedding of the symbol slot j emitted goes into columns [0, E) of its GRU input row.
+// forced (nullable): candidate indices that stand in for the top-bw search.  bw <= 8.
+__global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C,
+                                                                int eos, long long* __restrict__ symbols, long long* __restrict__ preds,
+                                                                float* __restrict__ stored, const long long* __restrict__ forced,
+                                                                const float* __restrict__ s_in, const bf16_t* __restrict__ sbf_in,
+                                                                float* __restrict__ s_out, bf16_t* __restrict__ sbf_out, int S,
+                                                                const float* __restrict__ table, int E, bf16_t* __restrict__ inp, int ld_inp) {
+  extern __shared__ float cand[];                                       // [bw * C]
+  __shared__ float lse[8];
+  __shared__ float rv[4];
+  __shared__ int ri[4];
+  __shared__ int sym_s[8], pred_s[8];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = wave; k < bw; k += 4) {
+    const float* row = logits + (size_t)(b * bw + k) * ld;
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += __expf(row[c] - m);
+    s = wave_sum(s);
+    if (lane == 0) lse[k] = m + __logf(s);
+  }
+  __syncthreads();
+  const int n = bw * C;
+  for (int i = tid; i < n; i += 256) {
+    const int k = i / C, c = i - k * C;
+    cand[i] = seq_scores[b * bw + k] + (logits[(size_t)(b * bw + k) * ld + c] - lse[k]);
+  }
+  __syncthreads();
+  for (int r = 0; r < bw; ++r) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    if (!forced) {
+      for (int i = tid; i < n; i += 256) {
+        const float v = cand[i];
+        if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+      }
+      if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      if (forced) {
+        const long long f = forced[b * bw + r];
+        bi = (int)(f < 0 ? 0 : (f >= n ? n - 1 : f));
+        bv = cand[bi];
+      } else {
+        for (int w = 1; w < 4; ++w)
+          if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
+        if (bi == 0x7fffffff) bi = r;
+        cand[bi] = -INFINITY;
+      }
+      const int sym = bi % C;
+      symbols[b * bw + r] = sym;
+      preds[b * bw + r] = bi / C + b * bw;
+      stored[b * bw + r] = bv;
+      seq_scores[b * bw + r] = sym == eos ? -INFINITY : bv;
+      sym_s[r] = sym;
+      pred_s[r] = bi / C + b * bw;
+    }
+    __syncthreads();
+  }
+  // bi / C < bw and sym < C: the sources below are rows of this sample's slots and of the table's first C rows
+  const size_t row0 = (size_t)b * bw;
+  for (int i = tid; i < bw * S; i += 256) {
+    const int j = i / S, c = i - j * S;
+    const size_t src = (size_t)pred_s[j] * S + c, dst = (row0 + j) * S + c;
+    s_out[dst] = s_in[src];
+    sbf_out[dst] = sbf_in[src];
+  }
+  for (int i = tid; i < bw * E; i += 256) {
+    const int j = i / E, c = i - j * E;
+    inp[(row0 + j) * ld_inp + c] = f2bf(table[(size_t)sym_s[j] * E + c]);
+  }
+}
+
 // Accuracy (evaluation_metric/metrics.py:19-81): both label rows are cut at EOS, UNKNOWN and every class that is not a digit
 // or letter are dropped, letters compare case-insensitively.  canon[c] = canonical code of class c (0 = dropped, EOS and
 // UNKNOWN included).  One thread per sample; match[b] = 1 when the normalised strings are equal.
@@ -426,6 +511,27 @@ extern "C" int dig_beam_step(const float* logits, int ld, float* seq_scores, int
   if (beam_width < 1 || beam_width > 16 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
                      eos, symbols, predecessors, stored_scores);
+  return dig_check_launch();
+}
+
+static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+
+extern "C" int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
+                                     long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in,
+                                     const void* sbf_in, float* s_out, void* sbf_out, int S, const float* table, int E, void* inp, int ld_inp,
+                                     hipStream_t stream) {
+  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || !s_in || !sbf_in || !s_out || !sbf_out || !table || !inp || B <= 0 ||
+      C <= 0 || ld < C || S <= 0 || E <= 0 || ld_inp < E)
+    return DIG_ERR_ARG;
+  if (beam_width < 1 || beam_width > 8 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
+  const size_t rows = (size_t)B * beam_width * S;
+  if (ranges_overlap(s_in, s_out, rows * sizeof(float)) || ranges_overlap(sbf_in, sbf_out, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
+  hipLaunchKernelGGL(attn_beam_advance_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
+                     eos, symbols, predecessors, stored_scores, force_candidates, s_in, (const bf16_t*)sbf_in, s_out, (bf16_t*)sbf_out, S, table, E,
+                     (bf16_t*)inp, ld_inp);
   return dig_check_launch();
 }
 

@@ -118,6 +118,108 @@ __global__ __launch_bounds__(NT) void addattn_fwd_kernel(const bf16_t* __restric
   }
 }
 
+// ---- forward for the K beam slots of a sample (beam search of the head: the K hypotheses share the sample's tokens).  sproj [B*K, A], alpha
+// [B*K, N] (may be null), context row b*K + k at ctx + (b*K + k) * ldc; xproj and x hold one copy per sample and every row of either is
+// loaded once for all K slots.  Dynamic LDS (floats): sp [K][A] | ws [A] (after the scores the same words hold the second half-block's
+// partial contexts, part [K][X]) then, from v_off on, v [K][N].  Per slot the scores are token_score's sum term by term; the softmax of
+// slot k runs on wave k (K <= NW), so its sums meet in another order than addattn_fwd_kernel's block reductions.
+template <int K>
+__global__ __launch_bounds__(NT) void addattn_fwd_slots_kernel(const bf16_t* __restrict__ xproj, const bf16_t* __restrict__ sproj,
+                                                               const float* __restrict__ w, const bf16_t* __restrict__ x, float* __restrict__ alpha,
+                                                               bf16_t* __restrict__ ctx, int ldc, int N, int A, int X, int v_off) {
+  extern __shared__ float sm[];
+  float* sp = sm;
+  float* ws = sm + K * A;
+  float* part = sm;
+  float* v = sm + v_off;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < K * A; i += NT) sp[i] = bf2f(sproj[(size_t)b * K * A + i]);
+  for (int a = tid; a < A; a += NT) ws[a] = w[a];
+  __syncthreads();
+  for (int n = wave; n < N; n += NW) {
+    const bf16_t* xp_row = xproj + ((size_t)b * N + n) * A;
+    float acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.f;
+    for (int a0 = lane * 8; a0 < A; a0 += 512) {
+      float xv[8], wv[8];
+      load8f(xp_row + a0, xv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) wv[e] = ws[a0 + e];                       // (read once for the K slots)
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[k] += wv[e] * tanh_fast(sp[k * A + a0 + e] + xv[e]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float s = wave_sum(acc[k]);
+      if (lane == 0) v[k * N + n] = s;
+    }
+  }
+  __syncthreads();
+  if (wave < K) {
+    float* vk = v + wave * N;
+    float m = -INFINITY;
+    for (int n = lane; n < N; n += 64) m = fmaxf(m, vk[n]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int n = lane; n < N; n += 64) { const float e = __expf(vk[n] - m); vk[n] = e; s += e; }
+    const float inv = 1.f / wave_sum(s);
+    for (int n = lane; n < N; n += 64) {
+      const float a = vk[n] * inv;
+      vk[n] = a;
+      if (alpha) alpha[((size_t)b * K + wave) * N + n] = a;
+    }
+  }
+  __syncthreads();                                                       // (sp / ws are dead from here: part may overwrite them)
+  // contexts: as addattn_fwd_kernel, a thread owns two channels and now K accumulator pairs; every x row is read once
+  const int CP = X / 2;
+  bf16_t* cb = ctx + (size_t)b * K * ldc;
+  if (CP <= NT / 2) {
+    const int half = tid >= NT / 2 ? 1 : 0, cp = tid - half * (NT / 2);
+    float a0[K], a1[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { a0[k] = 0.f; a1[k] = 0.f; }
+    if (cp < CP) {
+      const bf16_t* xb = x + (size_t)b * N * X + 2 * cp;
+      const int n_hi = half ? N : N / 2;
+      for (int n = half ? N / 2 : 0; n < n_hi; ++n) {
+        const unsigned p = *reinterpret_cast<const unsigned*>(xb + (size_t)n * X);
+        const float x0 = bf2f((bf16_t)(p & 0xffff)), x1 = bf2f((bf16_t)(p >> 16));
+#pragma unroll
+        for (int k = 0; k < K; ++k) { a0[k] += v[k * N + n] * x0; a1[k] += v[k * N + n] * x1; }
+      }
+      if (half) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) { part[k * X + 2 * cp] = a0[k]; part[k * X + 2 * cp + 1] = a1[k]; }
+      }
+    }
+    __syncthreads();
+    if (!half && cp < CP) {
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+        *reinterpret_cast<unsigned*>(cb + (size_t)k * ldc + 2 * cp) = pack_bf2(a0[k] + part[k * X + 2 * cp], a1[k] + part[k * X + 2 * cp + 1]);
+    }
+  } else {
+    for (int c = tid * 2; c < X; c += 2 * NT) {
+      float a0[K], a1[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) { a0[k] = 0.f; a1[k] = 0.f; }
+      const bf16_t* xb = x + (size_t)b * N * X + c;
+      for (int n = 0; n < N; ++n) {
+        const unsigned p = *reinterpret_cast<const unsigned*>(xb + (size_t)n * X);
+        const float x0 = bf2f((bf16_t)(p & 0xffff)), x1 = bf2f((bf16_t)(p >> 16));
+#pragma unroll
+        for (int k = 0; k < K; ++k) { a0[k] += v[k * N + n] * x0; a1[k] += v[k * N + n] * x1; }
+      }
+#pragma unroll
+      for (int k = 0; k < K; ++k) *reinterpret_cast<unsigned*>(cb + (size_t)k * ldc + c) = pack_bf2(a0[k], a1[k]);
+    }
+  }
+}
+
 // ---- backward of one step: dctx [B, X] (bf16, row stride ldd) -> dv [B, N] (fp32, kept for the final kernels), dsproj [B, A] (bf16),
 // dw_acc [B, A] (fp32, += : per-sample partials of the wEmbed gradient, summed over samples at the end)
 __global__ __launch_bounds__(NT) void addattn_bwd_kernel(const bf16_t* __restrict__ xproj, const bf16_t* __restrict__ sproj,
@@ -308,6 +410,26 @@ extern "C" int dig_addattn_fwd(const void* xproj, const void* sproj, const float
   if (!aligned16(xproj)) return DIG_ERR_ALIGN;
   hipLaunchKernelGGL(addattn_fwd_kernel, dim3(B), dim3(NT), 0, stream, (const bf16_t*)xproj, (const bf16_t*)sproj, w, (const bf16_t*)x, alpha,
                      (bf16_t*)ctx, ldc, N, A, X);
+  return dig_check_launch();
+}
+
+extern "C" int dig_addattn_fwd_slots(const void* xproj, const void* sproj, const float* w, const void* x, float* alpha, void* ctx, int ldc, int B, int N,
+                                     int A, int X, int slots, hipStream_t stream) {
+  if (!xproj || !sproj || !w || !x || !ctx || B <= 0 || N <= 0 || A <= 0 || X <= 0 || (X & 1) || (ldc & 1)) return DIG_ERR_ARG;
+  if (N > MAXN || A > MAXA || (A & 7) || slots < 1 || slots > 8) return DIG_ERR_UNSUPPORTED;
+  if (!aligned16(xproj)) return DIG_ERR_ALIGN;
+  // sp [K][A] | ws [A], re-used by part [K][X] on the split-token path (X <= NT), then v [K][N]: at most 8 * (1024 + 512) * 4 + 4096 B
+  const int K = slots, v_off = std::max(K * A + A, X / 2 <= NT / 2 ? K * X : 0);
+  const size_t lds = (size_t)(v_off + K * N) * sizeof(float);                     // <= 53,248 B: below the 64 KB a launch gets by default
+#define DIG_SLOTS_CASE(KK)                                                                                                                      \
+  case KK:                                                                                                                                      \
+    hipLaunchKernelGGL(addattn_fwd_slots_kernel<KK>, dim3(B), dim3(NT), lds, stream, (const bf16_t*)xproj, (const bf16_t*)sproj, w, (const bf16_t*)x, \
+                       alpha, (bf16_t*)ctx, ldc, N, A, X, v_off);                                                                               \
+    break;
+  switch (K) {
+    DIG_SLOTS_CASE(1) DIG_SLOTS_CASE(2) DIG_SLOTS_CASE(3) DIG_SLOTS_CASE(4) DIG_SLOTS_CASE(5) DIG_SLOTS_CASE(6) DIG_SLOTS_CASE(7) DIG_SLOTS_CASE(8)
+  }
+#undef DIG_SLOTS_CASE
   return dig_check_launch();
 }
 

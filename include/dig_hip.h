@@ -777,6 +777,36 @@ int dig_gru_cell_bwd(const float* ds_a, const float* ds_b, const float* ds_c, co
                      void* dgh, float* ds_prev, int B, int S, hipStream_t stream);
 /* out[r, :cols] (bf16, row stride ld) = table[clamp(tokens[r]), :cols] (fp32 table): tgt_embedding lookups (attn_decoder.py:264). */
 int dig_embed_rows(const long long* tokens, const float* table, void* out, int ld, int rows, int cols, int vocab, hipStream_t stream);
+/* ---- beam search of the GRU attention head (AttentionRecognitionHead.beam_search, models/attn_decoder.py:84-200): the `slots` = beam
+ * width K hypotheses of a sample share its encoder tokens, so neither x nor xEmbed(x) is inflated K times.
+ * dig_addattn_fwd_slots: dig_addattn_fwd for K states per sample.  xproj [B,N,A] and x [B,N,X] (bf16) hold ONE copy per sample; sproj is
+ *   [B*K, A] (bf16, row b*K + k = slot k of sample b); alpha [B*K, N] fp32 may be NULL (evaluation keeps no softmax); context row b*K + k
+ *   is written at ctx + (b*K + k)*ldc (bf16).  One workgroup per sample: every xproj row is loaded once and scored against the K sproj rows
+ *   held in LDS, every x row once for the K contexts; fp32 reductions, the tanh / softmax forms of dig_addattn_fwd (the softmax sums run
+ *   in another order: a wave per slot).  Dynamic LDS: K*(A + N)*4 bytes for the sproj rows and scores + A*4 for w (the partial contexts
+ *   of the split-token path re-use the sproj rows) = 53,248 B at K = 8, A = 1024, N = 512, so two workgroups fit a CU's 160 KB of LDS;
+ *   their registers fit as well while an instantiation stays at or below 128 VGPRs (dig_amd/build.py's flags: 43..53 for K = 1..8, no
+ *   AGPRs; tests/test_attn_beam.py holds the build to it).
+ *   Null pointer (but alpha), non-positive dimension, odd X or ldc: DIG_ERR_ARG; xproj not 16-byte aligned: DIG_ERR_ALIGN; N > 512,
+ *   A > 1024, A not a multiple of 8 or slots outside 1..8: DIG_ERR_UNSUPPORTED.  A refused call launches nothing. */
+int dig_addattn_fwd_slots(const void* xproj, const void* sproj, const float* w, const void* x, float* alpha /* nullable */, void* ctx, int ldc,
+                          int B, int N, int A, int X, int slots, hipStream_t stream);
+/* dig_attn_beam_advance: what closes a step of that beam search, one launch, one workgroup per sample.
+ *   (a) the rule of dig_beam_step, tie-breaking included, on logits (row stride ld) and seq_scores [B*K] (in / out): symbols, predecessors
+ *       (int64 [B*K]), stored_scores (fp32 [B*K]), seq_scores = -inf for a slot that emitted `eos`.  With force_candidates (int64 [B*K],
+ *       nullable; values in [0, K*C), others are clamped) slot j takes candidate force_candidates[b*K + j] of its sample in place of the
+ *       j-th best: parity runs that follow given decisions.
+ *   (b) the recurrent state follows its hypothesis (attn_decoder.py:127-128): s_out[j] = s_in[predecessors[j]] (fp32 [B*K, S]) and
+ *       sbf_out[j] = sbf_in[predecessors[j]] (bf16 [B*K, S]).  A gather cannot run in place: an output that overlaps its input is
+ *       DIG_ERR_ARG.
+ *   (c) the next step's target embedding: inp[j, :E] = bf16(table[symbols[j], :E]) (table fp32 [> C rows, E]; inp bf16 rows of stride
+ *       ld_inp); columns from E on are not written.
+ *   Null pointer (but force_candidates), non-positive dimension, ld < C, ld_inp < E, aliased state: DIG_ERR_ARG; beam_width outside 1..8 or
+ *   beam_width*C*4 > 60000 bytes of LDS (dig_beam_step's condition): DIG_ERR_UNSUPPORTED. */
+int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
+                          long long* predecessors, float* stored_scores, const long long* force_candidates /* nullable */, const float* s_in,
+                          const void* sbf_in, float* s_out, void* sbf_out, int S, const float* table, int E, void* inp, int ld_inp,
+                          hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * One call per encoder block (Block.forward, modeling_finetune.py:150-158, and its gradient): the launch sequences of

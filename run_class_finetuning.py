@@ -37,6 +37,8 @@ What is different, on purpose:
     has no criterion.  Here it builds `CTCRecModelTrain` under `SeqCTCLoss` whatever --smoothing says (reported once when --smoothing > 0 is
     ignored); --beam_width > 0 (the autoregressive beam), --text_cond_vis and --use_1d_attdec stop with it (dig_amd/ctc_recognizer.py says
     what is mirrored and what is this project's own definition);
+  * `--decoder_type attention --beam_width K` (K <= 8): the reference's `AttnRecModel.forward` ignores the flag and samples greedily although its
+    head carries `beam_search`; here `evaluate` decodes by that method (said once), with its `predecessors` an integer division;
   * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`), --ctc_beam_width K
     (with --decoder_type ctc: `evaluate` decodes by CTC prefix beam search of width K <= 32, said once; 0, the default, is the greedy collapse;
     the training loop's class accuracy stays greedy).
@@ -202,6 +204,8 @@ def refuse_unbuilt(args):
         if args.use_1d_attdec:
             raise SystemExit("--use_1d_attdec with --decoder_type ctc: the CTC head always classifies the 32 column means of the token grid; the flag selects "
                              "the attention decoders' memory")
+    if args.decoder_type == "attention" and not 0 <= args.beam_width <= 8:
+        raise SystemExit(f"--beam_width {args.beam_width} with --decoder_type attention: 0 (greedy sample) or a beam search of width 1..8")
     if args.ctc_beam_width != 0 and args.decoder_type != "ctc":
         raise SystemExit(f"--ctc_beam_width with --decoder_type {args.decoder_type}: the prefix beam search decodes the CTC head's frames "
                          "(--decoder_type ctc); the transformer decoder's beam is --beam_width")
@@ -356,6 +360,9 @@ def main(args):
         criterion.ignore_index = dataset_train.class_to_idx["PADDING"]
     else:
         criterion = SeqCrossEntropyLoss()
+    if args.decoder_type == "attention" and model.beam_width > 0:
+        print(f"evaluation decoder = beam search of the GRU attention head, width {model.beam_width} (--beam_width); the training loop's accuracy "
+              "is the teacher-forced arg-max")
     print("criterion = %s" % str(criterion))
 
     utils.auto_load_model(args=args, model=model, model_without_ddp=model, optimizer=optimizer, loss_scaler=loss_scaler, model_ema=model_ema)

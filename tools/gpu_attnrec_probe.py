@@ -1,12 +1,18 @@
 """Throughput of the AttnRecModel training step (GRU attention head, `--decoder_type attention`): simmim_vit_small_patch4_32x128 encoder,
 sDim = attDim = 512, 97 classes, max_len 25, batch 256, README drop rates for the encoder, AdamW with layer decay 0.75; random weights
-and labels.  Also the greedy sample (evaluation) rate."""
-import os, sys, time, types
+and labels.  Also the greedy sample (evaluation) rate and, with `--beam_width K [K ...]`, the rate of the evaluation forward + beam search of
+each width (same images, same weights, same run); the last line is the kernel-source hash the figures belong to."""
+import argparse, os, sys, time, types
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dig_amd.attn_recognizer import AttnRecModelTrain
 from dig_amd.finetune import SeqCrossEntropyLoss, LayerDecayValueAssigner, create_optimizer
 from dig_amd.utils import NativeScalerWithGradNormCount
+from dig_amd.build import source_hash
+ap = argparse.ArgumentParser()
+ap.add_argument("--beam_width", type=int, nargs="*", default=[], help="also time the evaluation with a beam search of these widths (1..8)")
+ap.add_argument("--skip_train", action="store_true", help="time the evaluation only")
+opts = ap.parse_args()
 dev = torch.device("cuda:0")
 args = types.SimpleNamespace(model="simmim_vit_small_patch4_32x128", nb_classes=97, max_len=25, drop=0.1, attn_drop_rate=0.1, drop_path=0.1,
                              opt="adamw", lr=1e-4, weight_decay=0.05, opt_eps=1e-8, opt_betas=[0.9, 0.999])
@@ -28,14 +34,22 @@ def step():
     opt.zero_grad()
     loss = crit(m((images, tg, lens))[0], tg, lens)
     return loss, scaler(loss, opt, clip_grad=None, parameters=None)
-for _ in range(3): loss, gn = step()
-torch.cuda.synchronize(); t = time.perf_counter(); n = 10
-for _ in range(n): loss, gn = step()
-torch.cuda.synchronize(); dt = (time.perf_counter() - t) / n
-print(f"AttnRecModel training step B={B}: {dt*1e3:.1f} ms = {B/dt:.0f} images/s  (loss {loss.item():.3f}, grad norm {gn.item():.3f})")
+if not opts.skip_train:
+    for _ in range(3): loss, gn = step()
+    torch.cuda.synchronize(); t = time.perf_counter(); n = 10
+    for _ in range(n): loss, gn = step()
+    torch.cuda.synchronize(); dt = (time.perf_counter() - t) / n
+    print(f"AttnRecModel training step B={B}: {dt*1e3:.1f} ms = {B/dt:.0f} images/s  (loss {loss.item():.3f}, grad norm {gn.item():.3f})")
 m.eval()
-for _ in range(2): p = m((images, None, None))[0]
-torch.cuda.synchronize(); t = time.perf_counter()
-for _ in range(5): p = m((images, None, None))[0]
-torch.cuda.synchronize(); dt = (time.perf_counter() - t) / 5
-print(f"AttnRecModel greedy sample B={B}: {dt*1e3:.1f} ms = {B/dt:.0f} images/s")
+def timed_eval(what):
+    for _ in range(2): p = m((images, None, None))[0]
+    torch.cuda.synchronize(); t = time.perf_counter()
+    for _ in range(5): p = m((images, None, None))[0]
+    torch.cuda.synchronize(); dt = (time.perf_counter() - t) / 5
+    print(f"AttnRecModel {what} B={B}: {dt*1e3:.1f} ms = {B/dt:.0f} images/s")
+timed_eval("greedy sample")
+for k in opts.beam_width:
+    m.beam_width = k                                   # (what args.beam_width sets at construction)
+    timed_eval(f"beam search width {k}")
+m.beam_width = 0
+print("kernel sources", source_hash())
