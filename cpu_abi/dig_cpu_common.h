@@ -23,6 +23,10 @@ inline bf16_t f2bf(float f) {                       // round to nearest even, as
   return (bf16_t)(u >> 16);
 }
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {      // [a, a + bytes) and [b, b + bytes) share a byte
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
 inline unsigned drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
   unsigned x = a ^ k0;
   x ^= x >> 16; x *= 0x7feb352du;

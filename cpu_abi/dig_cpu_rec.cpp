@@ -267,57 +267,21 @@ int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tok
   return DIG_OK;
 }
 
-int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
-                  long long* predecessors, float* stored_scores, hipStream_t) {
+// the arguments of the ranking, as both beam entry points check them
+static int beam_check(const float* logits, int ld, const float* seq_scores, int B, int beam_width, int max_width, int C, const long long* symbols,
+                      const long long* predecessors, const float* stored_scores) {
   if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > 16 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
-  const int bw = beam_width, n = bw * C;
-  for (int b = 0; b < B; ++b) {
-    std::vector<float> cand(n);
-    for (int k = 0; k < bw; ++k) {
-      const float* row = logits + (size_t)(b * bw + k) * ld;
-      float m, s;
-      row_max_sum(row, C, m, s);
-      const float lse = m + std::log(s);
-      for (int c = 0; c < C; ++c) cand[k * C + c] = seq_scores[b * bw + k] + (row[c] - lse);
-    }
-    for (int r = 0; r < bw; ++r) {
-      float bv = NEG_INF;
-      int bi = 0x7fffffff;
-      for (int i = 0; i < n; ++i)
-        if (cand[i] > bv || (cand[i] == bv && i < bi)) { bv = cand[i]; bi = i; }
-      if (bi == 0x7fffffff) bi = r;
-      const int sym = bi % C;
-      symbols[b * bw + r] = sym;
-      predecessors[b * bw + r] = bi / C + b * bw;
-      stored_scores[b * bw + r] = bv;
-      seq_scores[b * bw + r] = sym == eos ? NEG_INF : bv;
-      cand[bi] = NEG_INF;
-    }
-  }
+  if (beam_width < 1 || beam_width > max_width || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
   return DIG_OK;
 }
 
-// dig_beam_step's rule (its statements), then the gather of the recurrent state by predecessor and the next step's target embedding
-int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
-                          long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in, const void* sbf_in_,
-                          float* s_out, void* sbf_out_, int S, const float* table, int E, void* inp_, int ld_inp, hipStream_t) {
-  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || !s_in || !sbf_in_ || !s_out || !sbf_out_ || !table || !inp_ || B <= 0 ||
-      C <= 0 || ld < C || S <= 0 || E <= 0 || ld_inp < E)
-    return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > 8 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
-  const size_t rows = (size_t)B * beam_width * S;
-  auto overlap = [](const void* a, const void* b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-  };
-  if (overlap(s_in, s_out, rows * sizeof(float)) || overlap(sbf_in_, sbf_out_, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
-  const bf16_t* sbf_in = (const bf16_t*)sbf_in_;
-  bf16_t* sbf_out = (bf16_t*)sbf_out_;
-  bf16_t* inp = (bf16_t*)inp_;
-  const int bw = beam_width, n = bw * C;
+// The ranking of a beam-search step (beam_rank of csrc/decode.hip): per sample the candidate table, the top bw by (value, lowest index)
+// -- or the forced candidates in their place -- and the step's symbol / predecessor / stored score / next running score.
+static void beam_rank(const float* logits, int ld, float* seq_scores, int B, int bw, int C, int eos, long long* symbols, long long* predecessors,
+                      float* stored_scores, const long long* forced) {
+  const int n = bw * C;
+  std::vector<float> cand(n);
   for (int b = 0; b < B; ++b) {
-    std::vector<float> cand(n);
     for (int k = 0; k < bw; ++k) {
       const float* row = logits + (size_t)(b * bw + k) * ld;
       float m, s;
@@ -328,9 +292,8 @@ int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B,
     for (int r = 0; r < bw; ++r) {
       float bv = NEG_INF;
       int bi = 0x7fffffff;
-      if (force_candidates) {
-        const long long f = force_candidates[b * bw + r];
-        bi = (int)(f < 0 ? 0 : (f >= n ? n - 1 : f));
+      if (forced) {
+        bi = (int)clamp_tok(forced[b * bw + r], n);
         bv = cand[bi];
       } else {
         for (int i = 0; i < n; ++i)
@@ -338,19 +301,45 @@ int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B,
         if (bi == 0x7fffffff) bi = r;
         cand[bi] = NEG_INF;
       }
-      const int sym = bi % C, j = b * bw + r;
-      const size_t pred = (size_t)(bi / C + b * bw);
-      symbols[j] = sym;
-      predecessors[j] = (long long)pred;
-      stored_scores[j] = bv;
-      seq_scores[j] = sym == eos ? NEG_INF : bv;
-      for (int c = 0; c < S; ++c) { s_out[(size_t)j * S + c] = s_in[pred * S + c]; sbf_out[(size_t)j * S + c] = sbf_in[pred * S + c]; }
-      for (int c = 0; c < E; ++c) inp[(size_t)j * ld_inp + c] = f2bf(table[(size_t)sym * E + c]);
+      const int sym = bi % C;
+      symbols[b * bw + r] = sym;
+      predecessors[b * bw + r] = bi / C + b * bw;
+      stored_scores[b * bw + r] = bv;
+      seq_scores[b * bw + r] = sym == eos ? NEG_INF : bv;
     }
+  }
+}
+
+int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
+                  long long* predecessors, float* stored_scores, hipStream_t) {
+  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 16, C, symbols, predecessors, stored_scores);
+  if (rc != DIG_OK) return rc;
+  beam_rank(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores, nullptr);
+  return DIG_OK;
+}
+
+// the ranking, then the gather of the recurrent state by predecessor and the next step's target embedding
+int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
+                          long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in, const void* sbf_in_,
+                          float* s_out, void* sbf_out_, int S, const float* table, int E, void* inp_, int ld_inp, hipStream_t) {
+  if (!s_in || !sbf_in_ || !s_out || !sbf_out_ || !table || !inp_ || S <= 0 || E <= 0 || ld_inp < E) return DIG_ERR_ARG;
+  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 8, C, symbols, predecessors, stored_scores);
+  if (rc != DIG_OK) return rc;
+  const size_t rows = (size_t)B * beam_width * S;
+  if (ranges_overlap(s_in, s_out, rows * sizeof(float)) || ranges_overlap(sbf_in_, sbf_out_, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
+  const bf16_t* sbf_in = (const bf16_t*)sbf_in_;
+  bf16_t* sbf_out = (bf16_t*)sbf_out_;
+  bf16_t* inp = (bf16_t*)inp_;
+  beam_rank(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores, force_candidates);
+  for (size_t j = 0; j < (size_t)B * beam_width; ++j) {
+    const size_t pred = (size_t)predecessors[j], sym = (size_t)symbols[j];
+    for (int c = 0; c < S; ++c) { s_out[j * S + c] = s_in[pred * S + c]; sbf_out[j * S + c] = sbf_in[pred * S + c]; }
+    for (int c = 0; c < E; ++c) inp[j * ld_inp + c] = f2bf(table[sym * E + c]);
   }
   return DIG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- strings (csrc/metrics.hip)
 int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos, int B, int T,
                      unsigned char* match, hipStream_t) {
   if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
@@ -394,7 +383,6 @@ int dig_char_fmeasure(const long long* pred, const long long* target, const unsi
   return DIG_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- strings (csrc/metrics.hip)
 int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text, int* len,
                        hipStream_t) {
   if (!tokens || !canon || !text || !len || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
@@ -486,7 +474,7 @@ int dig_seq_confidence(const float* score, const int* text_len, int B, int T, do
   return DIG_OK;
 }
 
-// ---------------------------------------------------------------------------------------------------------------- sequence losses
+// ---------------------------------------------------------------------------------------------------------------- sequence losses (csrc/seq_loss.hip)
 int dig_seq_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C, float* row_workspace,
                           float* loss, hipStream_t) {
   if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0) return DIG_ERR_ARG;
@@ -505,6 +493,25 @@ int dig_seq_cross_entropy(const float* input, const long long* target, const lon
     total += v;
   }
   loss[0] = (float)total * (1.0f / (float)B);
+  return DIG_OK;
+}
+
+int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar, int B, int T,
+                              int C, void* dlogits_, int ldd, hipStream_t) {
+  if (!logits || !target || !length || !dlogits_ || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C) return DIG_ERR_ARG;
+  bf16_t* dlogits = (bf16_t*)dlogits_;
+  const float sc = (gscalar ? gscalar[0] : 1.f) * (1.0f / (float)B);
+  for (int row = 0; row < B * T; ++row) {
+    const int b = row / T, t = row - b * T;
+    bf16_t* out = dlogits + (size_t)row * ldd;
+    if (t >= length[b]) { for (int c = 0; c < ldd; ++c) out[c] = 0; continue; }
+    const float* x = logits + (size_t)row * ld;
+    float m, s;
+    row_max_sum(x, C, m, s);
+    const float inv = 1.f / s;
+    const long long y = clamp_tok(target[row], C);
+    for (int c = 0; c < ldd; ++c) out[c] = c < C ? f2bf(sc * (std::exp(x[c] - m) * inv - (c == y ? 1.f : 0.f))) : (bf16_t)0;
+  }
   return DIG_OK;
 }
 
@@ -720,25 +727,6 @@ int dig_seq_embed_bwd_lens(const long long* tokens, const void* dx_, float* demb
 
 int dig_seq_embed_bwd(const long long* tokens, const void* dx, float* demb, int n_tok, int d, int vocab, hipStream_t st) {
   return dig_seq_embed_bwd_lens(tokens, dx, demb, n_tok, d, vocab, 0, nullptr, st);
-}
-
-int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar, int B, int T,
-                              int C, void* dlogits_, int ldd, hipStream_t) {
-  if (!logits || !target || !length || !dlogits_ || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C) return DIG_ERR_ARG;
-  bf16_t* dlogits = (bf16_t*)dlogits_;
-  const float sc = (gscalar ? gscalar[0] : 1.f) * (1.0f / (float)B);
-  for (int row = 0; row < B * T; ++row) {
-    const int b = row / T, t = row - b * T;
-    bf16_t* out = dlogits + (size_t)row * ldd;
-    if (t >= length[b]) { for (int c = 0; c < ldd; ++c) out[c] = 0; continue; }
-    const float* x = logits + (size_t)row * ld;
-    float m, s;
-    row_max_sum(x, C, m, s);
-    const float inv = 1.f / s;
-    const long long y = clamp_tok(target[row], C);
-    for (int c = 0; c < ldd; ++c) out[c] = c < C ? f2bf(sc * (std::exp(x[c] - m) * inv - (c == y ? 1.f : 0.f))) : (bf16_t)0;
-  }
-  return DIG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- GRU attention head (N1)

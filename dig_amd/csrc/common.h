@@ -45,6 +45,8 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// y clamped into [0, C): the class a label (token, candidate) outside the range stands for; no index is formed from the raw value
+__device__ __forceinline__ long long clamp_class(long long y, int C) { return y < 0 ? 0 : (y >= C ? C - 1 : y); }
 
 // erf(x) by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, i.e. fp32 round-off class): 1 rcp + 1 exp + 6 fma instead
 // of the ~40-instruction libm erff -- the exact-erf GELU of nn.GELU() sits in a GEMM epilogue where VALU time matters.
@@ -252,3 +254,8 @@ static inline int dig_check_launch() {
   return e == hipSuccess ? DIG_OK : DIG_ERR_LAUNCH;
 }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// [a, a + bytes) and [b, b + bytes) share a byte
+static inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}

@@ -17,7 +17,7 @@
 // has nll = 0 and zero gradient rows; no index is ever formed from such a label.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "row_ops.h"
 
 namespace {
 
@@ -69,9 +69,7 @@ __device__ __forceinline__ void ctc_emissions(const float* __restrict__ x, int l
   for (int t = 0; t < T; ++t) {
     const float* row = x + (size_t)t * ld;
     const float xl = row[s.lab], xb = row[blank];
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
-    m = wave_max(m);
+    const float m = row_max(row, C, lane);
     double e = 0.0;
     for (int c = lane; c < C; c += 64) e += (double)expf((float)((double)row[c] - (double)m));
     const double ls = log(wave_sum_f64(e));
@@ -219,21 +217,10 @@ __global__ __launch_bounds__(64) void ctc_greedy_kernel(const float* __restrict_
   float prob = 1.f;
   for (int t = 0; t < T; ++t) {
     const float* row = x + (size_t)t * ld;
-    float m = -INFINITY;
-    int am = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = row[c];
-      if (v > m) { m = v; am = c; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(m, o, 64);
-      const int oa = __shfl_xor(am, o, 64);
-      if (om > m || (om == m && oa < am)) { m = om; am = oa; }
-    }
-    float e = 0.f;
-    for (int c = lane; c < C; c += 64) e += expf(row[c] - m);
-    e = wave_sum(e);
+    float m;
+    int am;
+    row_argmax_first(row, C, lane, m, am);
+    const float e = row_exp_sum<true>(row, C, lane, m);                     // (expf, not __expf: the score is defined by it)
     if (lane == t) { cls = am; prob = 1.f / e; }
   }
   const int prev = __shfl_up(cls, 1, 64);

@@ -1,4 +1,4 @@
-// Greedy decode with a K/V cache: the per-step pieces of TFDecoder.forward_test
+// Decode with a K/V cache: the per-step pieces of TFDecoder.forward_test (greedy) and of the two beam searches
 // (models/decoder.py:224-252) that are not GEMMs / LayerNorms.  The reference re-runs the whole decoder over all 26 positions
 // at every one of the 25 steps; position t only depends on tokens <= t, so the device path feeds one token per step, keeps
 // the self-attention keys/values of each layer in HBM ([B, T, 3*H*dk] bf16: the fused q|k|v projection writes row t in place)
@@ -8,6 +8,9 @@
 //   dig_decode_self_attn   one query (row t) against cached rows 0..t, per (sample, head)        (transformer_layer.py:238-281)
 //   dig_decode_cross_attn  one query against the Nm memory keys/values, per (sample, head); optional per-head weights
 //   dig_softmax_argmax     probabilities + greedy token of a logit row                           (decoder.py:238-246)
+//   dig_beam_step          one step of TFDecoder.beam_search: rank the candidates, keep the beam's books        (decoder.py:283-307)
+//   dig_attn_beam_advance  the same ranking for the GRU attention head, + its state gather and next input rows  (attn_decoder.py:116-138)
+// The string metrics are in metrics.hip, the sequence losses in seq_loss.hip.
 // Head dimension d_k = d_v = 64 (`tf_decoder`, `small_tf_decoder`, `corres_base_tf_decoder`), 48 (`corres_small_tf_decoder`) or 24
 // (`corres_tiny_tf_decoder`): a template parameter of the two attention kernels, heads are not padded.  All HBM-bound and tiny; one
 // wave (self) or four waves (cross) per (sample, head), fp32 softmax.
@@ -15,7 +18,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "row_ops.h"
 
 namespace {
 
@@ -24,8 +27,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const long long* __restrict_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * d) return;
   const int b = i / d, c = i - b * d;
-  long long t = tok[b];
-  t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
+  const long long t = clamp_class(tok[b], vocab);
   x[i] = f2bf(emb[(size_t)t * d + c] + pe_row[c]);
 }
 
@@ -134,108 +136,30 @@ __global__ __launch_bounds__(64) void softmax_argmax_kernel(const float* __restr
                                                             long long* __restrict__ token, int C) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const float* row = logits + (size_t)b * ld;
-  float m = -INFINITY;
-  int am = 0x7fffffff;
-  for (int c = lane; c < C; c += 64) {
-    const float v = row[c];
-    if (v > m) { m = v; am = c; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o, 64);
-    const int oa = __shfl_xor(am, o, 64);
-    if (om > m || (om == m && oa < am)) { m = om; am = oa; }
-  }
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __expf(row[c] - m);
-  s = wave_sum(s);
-  const float inv = 1.f / s;
+  float m;
+  int am;
+  row_argmax_first(row, C, lane, m, am);
+  const float inv = 1.f / row_exp_sum(row, C, lane, m);
   for (int c = lane; c < C; c += 64) probs[(size_t)b * C + c] = __expf(row[c] - m) * inv;
   if (lane == 0) token[b] = am;
 }
 
-// One step of TFDecoder.beam_search (decoder.py:283-307) for one sample: log-softmax of its `bw` slots' logits, + the slots' running
-// scores, top-`bw` of the bw*C candidates (ties: the lower candidate index, i.e. torch.topk's result wherever it is defined), then the
-// bookkeeping of that step: symbol = candidate % C, predecessor = candidate / C + b*bw, stored score, and the running score that
-// the next step starts from (-inf once a slot has emitted EOS, :299-301).  One 256-thread workgroup per sample; bw <= 16.
-__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C,
-                                                        int eos, long long* __restrict__ symbols, long long* __restrict__ preds,
-                                                        float* __restrict__ stored) {
-  extern __shared__ float cand[];                                       // [bw * C]
+// The ranking of one beam-search step for one sample (TFDecoder.beam_search, decoder.py:283-307), the one copy both kernels below run:
+// log-softmax of its `bw` slots' logits, + the slots' running scores, top-`bw` of the bw*C candidates (ties: the lower candidate index,
+// i.e. torch.topk's result wherever it is defined), then the bookkeeping of that step: symbol = candidate % C, predecessor =
+// candidate / C + b*bw, stored score, and the running score that the next step starts from (-inf once a slot has emitted EOS, :299-301).
+// One 256-thread workgroup; bw <= 16.  cand: LDS [bw * C].  forced (nullable): candidate indices that stand in for the top-bw search.
+// sym_s / pred_s (nullable, LDS [bw]): symbol and predecessor row of every slot, for what the caller does after the final barrier.
+__device__ __forceinline__ void beam_rank(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C, int eos,
+                                          long long* __restrict__ symbols, long long* __restrict__ preds, float* __restrict__ stored,
+                                          const long long* __restrict__ forced, float* cand, int* sym_s, int* pred_s) {
   __shared__ float lse[16];
   __shared__ float rv[4];
   __shared__ int ri[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int k = wave; k < bw; k += 4) {                                   // a wave per slot: log-sum-exp of the row
-    const float* row = logits + (size_t)(b * bw + k) * ld;
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += __expf(row[c] - m);
-    s = wave_sum(s);
-    if (lane == 0) lse[k] = m + __logf(s);
-  }
-  __syncthreads();
-  const int n = bw * C;
-  for (int i = tid; i < n; i += 256) {
-    const int k = i / C, c = i - k * C;
-    cand[i] = seq_scores[b * bw + k] + (logits[(size_t)(b * bw + k) * ld + c] - lse[k]);
-  }
-  __syncthreads();
-  for (int r = 0; r < bw; ++r) {
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < n; i += 256) {
-      const float v = cand[i];
-      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
-      if (bi == 0x7fffffff) bi = r;                                      // every candidate is NaN / -inf and already taken: keep indices valid
-      const int sym = bi % C;
-      symbols[b * bw + r] = sym;
-      preds[b * bw + r] = bi / C + b * bw;
-      stored[b * bw + r] = bv;
-      seq_scores[b * bw + r] = sym == eos ? -INFINITY : bv;
-      cand[bi] = -INFINITY;                                              // taken (a -inf candidate can be taken again: the reference's
-    }                                                                    //  order among -inf ties is unspecified as well)
-    __syncthreads();
-  }
-}
-
-// What closes a step of AttentionRecognitionHead.beam_search (attn_decoder.py:116-138) for one sample, in one launch: beam_step_kernel's
-// ranking and bookkeeping, statement by statement (so its results are the same bits), then what the GRU head's next step needs and the
-// transformer decoder's does not -- the recurrent state of slot j becomes the state of its predecessor (fp32 and bf16 copies, gathered
-// into buffers distinct from their sources), and the embedding of the symbol slot j emitted goes into columns [0, E) of its GRU input row.
-// forced (nullable): candidate indices that stand in for the top-bw search.  bw <= 8.
-__global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C,
-                                                                int eos, long long* __restrict__ symbols, long long* __restrict__ preds,
-                                                                float* __restrict__ stored, const long long* __restrict__ forced,
-                                                                const float* __restrict__ s_in, const bf16_t* __restrict__ sbf_in,
-                                                                float* __restrict__ s_out, bf16_t* __restrict__ sbf_out, int S,
-                                                                const float* __restrict__ table, int E, bf16_t* __restrict__ inp, int ld_inp) {
-  extern __shared__ float cand[];                                       // [bw * C]
-  __shared__ float lse[8];
-  __shared__ float rv[4];
-  __shared__ int ri[4];
-  __shared__ int sym_s[8], pred_s[8];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int k = wave; k < bw; k += 4) {
-    const float* row = logits + (size_t)(b * bw + k) * ld;
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
-    m = wave_max(m);
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += __expf(row[c] - m);
-    s = wave_sum(s);
+    float m, s;
+    row_max_sum(logits + (size_t)(b * bw + k) * ld, C, lane, m, s);
     if (lane == 0) lse[k] = m + __logf(s);
   }
   __syncthreads();
@@ -253,36 +177,53 @@ __global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __r
         const float v = cand[i];
         if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
       }
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
+      wave_argmax_first(bv, bi);
       if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
       __syncthreads();
     }
     if (tid == 0) {
       if (forced) {
-        const long long f = forced[b * bw + r];
-        bi = (int)(f < 0 ? 0 : (f >= n ? n - 1 : f));
+        bi = (int)clamp_class(forced[b * bw + r], n);
         bv = cand[bi];
       } else {
         for (int w = 1; w < 4; ++w)
           if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
-        if (bi == 0x7fffffff) bi = r;
-        cand[bi] = -INFINITY;
-      }
+        if (bi == 0x7fffffff) bi = r;                                      // every candidate is NaN / -inf and already taken: keep indices valid
+        cand[bi] = -INFINITY;                                              // taken (a -inf candidate can be taken again: the reference's
+      }                                                                    //  order among -inf ties is unspecified as well)
       const int sym = bi % C;
       symbols[b * bw + r] = sym;
       preds[b * bw + r] = bi / C + b * bw;
       stored[b * bw + r] = bv;
       seq_scores[b * bw + r] = sym == eos ? -INFINITY : bv;
-      sym_s[r] = sym;
-      pred_s[r] = bi / C + b * bw;
+      if (sym_s) { sym_s[r] = sym; pred_s[r] = bi / C + b * bw; }
     }
     __syncthreads();
   }
-  // bi / C < bw and sym < C: the sources below are rows of this sample's slots and of the table's first C rows
+}
+
+__global__ __launch_bounds__(256) void beam_step_kernel(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C,
+                                                        int eos, long long* __restrict__ symbols, long long* __restrict__ preds,
+                                                        float* __restrict__ stored) {
+  extern __shared__ float cand[];                                       // [bw * C]
+  beam_rank(logits, ld, seq_scores, bw, C, eos, symbols, preds, stored, nullptr, cand, nullptr, nullptr);
+}
+
+// What closes a step of AttentionRecognitionHead.beam_search (attn_decoder.py:116-138) for one sample, in one launch: the ranking, then
+// what the GRU head's next step needs and the transformer decoder's does not -- the recurrent state of slot j becomes the state of its
+// predecessor (fp32 and bf16 copies, gathered into buffers distinct from their sources), and the embedding of the symbol slot j emitted
+// goes into columns [0, E) of its GRU input row.  bw <= 8.
+__global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __restrict__ logits, int ld, float* __restrict__ seq_scores, int bw, int C,
+                                                                int eos, long long* __restrict__ symbols, long long* __restrict__ preds,
+                                                                float* __restrict__ stored, const long long* __restrict__ forced,
+                                                                const float* __restrict__ s_in, const bf16_t* __restrict__ sbf_in,
+                                                                float* __restrict__ s_out, bf16_t* __restrict__ sbf_out, int S,
+                                                                const float* __restrict__ table, int E, bf16_t* __restrict__ inp, int ld_inp) {
+  extern __shared__ float cand[];                                       // [bw * C]
+  __shared__ int sym_s[8], pred_s[8];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  beam_rank(logits, ld, seq_scores, bw, C, eos, symbols, preds, stored, forced, cand, sym_s, pred_s);
+  // pred_s[j] - b*bw < bw and sym_s[j] < C: the sources below are rows of this sample's slots and of the table's first C rows
   const size_t row0 = (size_t)b * bw;
   for (int i = tid; i < bw * S; i += 256) {
     const int j = i / S, c = i - j * S;
@@ -294,172 +235,6 @@ __global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __r
     const int j = i / E, c = i - j * E;
     inp[(row0 + j) * ld_inp + c] = f2bf(table[(size_t)sym_s[j] * E + c]);
   }
-}
-
-// Accuracy (evaluation_metric/metrics.py:19-81): both label rows are cut at EOS, UNKNOWN and every class that is not a digit
-// or letter are dropped, letters compare case-insensitively.  canon[c] = canonical code of class c (0 = dropped, EOS and
-// UNKNOWN included).  One thread per sample; match[b] = 1 when the normalised strings are equal.
-__global__ void string_match_kernel(const long long* __restrict__ pred, const long long* __restrict__ target,
-                                    const unsigned char* __restrict__ canon, int n_classes, int eos, int B, int T,
-                                    unsigned char* __restrict__ match) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const long long* p = pred + (size_t)b * T;
-  const long long* t = target + (size_t)b * T;
-  int i = 0, j = 0;
-  bool ok = true;
-  while (ok) {
-    unsigned char a = 0, c = 0;
-    while (i < T && p[i] != eos) {                                      // next kept character of the prediction
-      const long long v = p[i++];
-      a = (v >= 0 && v < n_classes) ? canon[v] : 0;
-      if (a) break;
-    }
-    if (i < T && p[i] == eos && !a) i = T;
-    while (j < T && t[j] != eos) {
-      const long long v = t[j++];
-      c = (v >= 0 && v < n_classes) ? canon[v] : 0;
-      if (c) break;
-    }
-    if (j < T && t[j] == eos && !c) j = T;
-    if (a != c) ok = false;
-    if (!a && !c) break;                                                // both strings ended
-  }
-  match[b] = ok ? 1 : 0;
-}
-
-// SeqCrossEntropyLoss.forward (loss/seqCrossEntropyLoss.py:47-63): row (b,t) contributes -log_softmax(input[b,t])[target[b,t]]
-// when t < length[b].  One wave per row writes its term; a single block then adds the B*T terms in a fixed order.
-__global__ __launch_bounds__(64) void seq_ce_rows_kernel(const float* __restrict__ input, const long long* __restrict__ target,
-                                                         const long long* __restrict__ length, int T, int C, float* __restrict__ rowloss) {
-  const int row = blockIdx.x, b = row / T, t = row - b * T, lane = threadIdx.x;
-  if (t >= length[b]) {
-    if (lane == 0) rowloss[row] = 0.f;
-    return;
-  }
-  const float* x = input + (size_t)row * C;
-  float m = -INFINITY;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-  m = wave_max(m);
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __expf(x[c] - m);
-  s = wave_sum(s);
-  if (lane == 0) {
-    long long y = target[row];
-    y = y < 0 ? 0 : (y >= C ? C - 1 : y);
-    rowloss[row] = -(x[y] - m - __logf(s));
-  }
-}
-
-__global__ __launch_bounds__(256) void fixed_order_sum_kernel(const float* __restrict__ v, int n, float scale, float* __restrict__ out) {
-  __shared__ float red[256];
-  float a = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) a += v[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] * scale;
-}
-
-// SeqLabelSmoothingCrossEntropyLoss.forward (loss/seqLabelSmoothingCrossEntropyLoss.py:48-70), as the reference computes it: the
-// `nll_loss` column [BT,1] and the `smooth_loss` product of a [BT] vector with the [BT,1] mask broadcast to a [BT,BT] matrix, so
-//   loss = ( confidence * BT * sum_i mask_i * nll_i  +  smoothing * (sum_i mask_i) * sum_j s_j ) / B,   s_j = -mean_c log_softmax(x_j)_c
-// with s_j taken over ALL rows j (also the padded ones).  One wave per row writes (mask_i * nll_i, s_i); a single block then adds
-// the terms in a fixed order.
-__global__ __launch_bounds__(64) void seq_ls_ce_rows_kernel(const float* __restrict__ input, const long long* __restrict__ target,
-                                                            const long long* __restrict__ length, int T, int C, float* __restrict__ rows2) {
-  const int row = blockIdx.x, b = row / T, t = row - b * T, lane = threadIdx.x, n = gridDim.x;
-  const float* x = input + (size_t)row * C;
-  float m = -INFINITY, sx = 0.f;
-  for (int c = lane; c < C; c += 64) { m = fmaxf(m, x[c]); sx += x[c]; }
-  m = wave_max(m);
-  sx = wave_sum(sx);
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __expf(x[c] - m);
-  s = wave_sum(s);
-  if (lane == 0) {
-    const float lse = m + __logf(s);
-    long long y = target[row];
-    y = y < 0 ? 0 : (y >= C ? C - 1 : y);
-    rows2[row] = t < length[b] ? lse - x[y] : 0.f;
-    rows2[n + row] = lse - sx / (float)C;
-  }
-}
-
-__global__ __launch_bounds__(256) void seq_ls_ce_sum_kernel(const float* __restrict__ rows2, const long long* __restrict__ length, int B, int T,
-                                                            float confidence, float smoothing, float* __restrict__ out) {
-  __shared__ float red[3][256];
-  const int n = B * T;
-  float a = 0.f, b = 0.f, cnt = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) { a += rows2[i]; b += rows2[n + i]; }
-  for (int i = threadIdx.x; i < B; i += 256) { const long long l = length[i]; cnt += (float)(l < 0 ? 0 : (l > T ? T : l)); }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = cnt;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = (confidence * (float)n * red[0][0] + smoothing * red[2][0] * red[1][0]) / (float)B;
-}
-
-// gradient: dL/dx[i,c] = g / B * ( confidence * BT * mask_i * (p_ic - [c == y_i]) + smoothing * M * (p_ic - 1/C) ),  M = sum_i mask_i
-__global__ __launch_bounds__(64) void seq_ls_ce_bwd_kernel(const float* __restrict__ logits, int ld, const long long* __restrict__ target,
-                                                           const long long* __restrict__ length, const float* __restrict__ g, int B, int T, int C,
-                                                           float confidence, float smoothing, bf16_t* __restrict__ dlogits, int ldd) {
-  const int row = blockIdx.x, b = row / T, t = row - b * T, lane = threadIdx.x;
-  float cnt = 0.f;
-  for (int i = lane; i < B; i += 64) { const long long l = length[i]; cnt += (float)(l < 0 ? 0 : (l > T ? T : l)); }
-  cnt = wave_sum(cnt);
-  const float* x = logits + (size_t)row * ld;
-  float m = -INFINITY;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-  m = wave_max(m);
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __expf(x[c] - m);
-  s = wave_sum(s);
-  const float sc = (g ? g[0] : 1.f) / (float)B, inv = 1.f / s;
-  const float wn = t < length[b] ? confidence * (float)(B * T) : 0.f, ws = smoothing * cnt;
-  long long y = target[row];
-  y = y < 0 ? 0 : (y >= C ? C - 1 : y);
-  bf16_t* out = dlogits + (size_t)row * ldd;
-  for (int c = lane; c < ldd; c += 64) {
-    float v = 0.f;
-    if (c < C) {
-      const float p = __expf(x[c] - m) * inv;
-      v = sc * (wn * (p - (c == y ? 1.f : 0.f)) + ws * (p - 1.f / (float)C));
-    }
-    out[c] = f2bf(v);
-  }
-}
-
-// recognition_f_measure (evaluation_metric/metrics.py:83-100): per sample, the SETS of kept characters of prediction and target
-// (same cut / drop / case-fold rules as the accuracy; canon codes 1..63 -> one bit each), p = n/(|P|+1e-5), r = n/(|T|+1e-5),
-// f = 2pr/(p+r+1e-5), all in double as the reference's Python floats.
-__global__ void char_fmeasure_kernel(const long long* __restrict__ pred, const long long* __restrict__ target,
-                                     const unsigned char* __restrict__ canon, int n_classes, int eos, int B, int T,
-                                     double* __restrict__ f_out) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  unsigned long long ps = 0, ts = 0;
-  for (int i = 0; i < T; ++i) {
-    const long long v = pred[(size_t)b * T + i];
-    if (v == eos) break;
-    const unsigned char c = (v >= 0 && v < n_classes) ? canon[v] : 0;
-    if (c) ps |= 1ull << (c & 63);
-  }
-  for (int i = 0; i < T; ++i) {
-    const long long v = target[(size_t)b * T + i];
-    if (v == eos) break;
-    const unsigned char c = (v >= 0 && v < n_classes) ? canon[v] : 0;
-    if (c) ts |= 1ull << (c & 63);
-  }
-  const double n = (double)__popcll(ps & ts);
-  const double p = n / ((double)__popcll(ps) + 1e-5), r = n / ((double)__popcll(ts) + 1e-5);
-  f_out[b] = 2 * p * r / (p + r + 1e-5);
 }
 
 }  // namespace
@@ -505,70 +280,34 @@ extern "C" int dig_softmax_argmax(const float* logits, int ld, float* probs, lon
   return dig_check_launch();
 }
 
+// the arguments of the ranking, as both beam entry points check them
+static int beam_check(const float* logits, int ld, const float* seq_scores, int B, int beam_width, int max_width, int C, const long long* symbols,
+                      const long long* predecessors, const float* stored_scores) {
+  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
+  if (beam_width < 1 || beam_width > max_width || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
+  return DIG_OK;
+}
+
 extern "C" int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                              long long* predecessors, float* stored_scores, hipStream_t stream) {
-  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > 16 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
+  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 16, C, symbols, predecessors, stored_scores);
+  if (rc != DIG_OK) return rc;
   hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
                      eos, symbols, predecessors, stored_scores);
   return dig_check_launch();
-}
-
-static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
 }
 
 extern "C" int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                                      long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in,
                                      const void* sbf_in, float* s_out, void* sbf_out, int S, const float* table, int E, void* inp, int ld_inp,
                                      hipStream_t stream) {
-  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || !s_in || !sbf_in || !s_out || !sbf_out || !table || !inp || B <= 0 ||
-      C <= 0 || ld < C || S <= 0 || E <= 0 || ld_inp < E)
-    return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > 8 || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
+  if (!s_in || !sbf_in || !s_out || !sbf_out || !table || !inp || S <= 0 || E <= 0 || ld_inp < E) return DIG_ERR_ARG;
+  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 8, C, symbols, predecessors, stored_scores);
+  if (rc != DIG_OK) return rc;
   const size_t rows = (size_t)B * beam_width * S;
   if (ranges_overlap(s_in, s_out, rows * sizeof(float)) || ranges_overlap(sbf_in, sbf_out, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
   hipLaunchKernelGGL(attn_beam_advance_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
                      eos, symbols, predecessors, stored_scores, force_candidates, s_in, (const bf16_t*)sbf_in, s_out, (bf16_t*)sbf_out, S, table, E,
                      (bf16_t*)inp, ld_inp);
-  return dig_check_launch();
-}
-
-extern "C" int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
-                                int B, int T, unsigned char* match, hipStream_t stream) {
-  if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(string_match_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, match);
-  return dig_check_launch();
-}
-
-extern "C" int dig_seq_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C,
-                                     float* row_workspace, float* loss, hipStream_t stream) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(seq_ce_rows_kernel, dim3(B * T), dim3(64), 0, stream, input, target, length, T, C, row_workspace);
-  hipLaunchKernelGGL(fixed_order_sum_kernel, dim3(1), dim3(256), 0, stream, row_workspace, B * T, 1.0f / (float)B, loss);
-  return dig_check_launch();
-}
-
-extern "C" int dig_char_fmeasure(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
-                                 int B, int T, double* f_per_sample, hipStream_t stream) {
-  if (!pred || !target || !canon || !f_per_sample || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(char_fmeasure_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, f_per_sample);
-  return dig_check_launch();
-}
-
-extern "C" int dig_seq_ls_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C,
-                                        float smoothing, float* row_workspace, float* loss, hipStream_t stream) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0 || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(seq_ls_ce_rows_kernel, dim3(B * T), dim3(64), 0, stream, input, target, length, T, C, row_workspace);
-  hipLaunchKernelGGL(seq_ls_ce_sum_kernel, dim3(1), dim3(256), 0, stream, row_workspace, length, B, T, 1.f - smoothing, smoothing, loss);
-  return dig_check_launch();
-}
-
-extern "C" int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar,
-                                            int B, int T, int C, float smoothing, void* dlogits, int ldd, hipStream_t stream) {
-  if (!logits || !target || !length || !dlogits || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(seq_ls_ce_bwd_kernel, dim3(B * T), dim3(64), 0, stream, logits, ld, target, length, gscalar, B, T, C, 1.f - smoothing,
-                     smoothing, (bf16_t*)dlogits, ldd);
   return dig_check_launch();
 }

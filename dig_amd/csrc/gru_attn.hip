@@ -395,8 +395,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const long long* __rest
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)rows * cols) return;
   const int r = (int)(i / cols), c = (int)(i - (size_t)r * cols);
-  long long t = tok[r];
-  t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
+  const long long t = clamp_class(tok[r], vocab);
   out[(size_t)r * ld + c] = f2bf(table[(size_t)t * cols + c]);
 }
 

@@ -1,6 +1,6 @@
-// Evaluation metrics beside dig_string_match (evaluation_metric/metrics.py of the reference): normalised strings as code points,
-// Levenshtein distance of pairs, the lexicon search (nearest word of a range, first minimum) and the confidence of a prediction.
-// Integer VALU + LDS work; no matrix cores.
+// Evaluation metrics (evaluation_metric/metrics.py of the reference): string accuracy and character F-measure of label rows, normalised
+// strings as code points, Levenshtein distance of pairs, the lexicon search (nearest word of a range, first minimum) and the confidence
+// of a prediction.  Integer VALU + LDS work; no matrix cores.
 #include "common.h"
 
 namespace {
@@ -50,6 +50,64 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k)
 }
 
 constexpr unsigned long long LEX_NONE = ~0ull;
+
+// Accuracy (evaluation_metric/metrics.py:19-81): both label rows are cut at EOS, UNKNOWN and every class that is not a digit
+// or letter are dropped, letters compare case-insensitively.  canon[c] = canonical code of class c (0 = dropped, EOS and
+// UNKNOWN included).  One thread per sample; match[b] = 1 when the normalised strings are equal.
+__global__ void string_match_kernel(const long long* __restrict__ pred, const long long* __restrict__ target,
+                                    const unsigned char* __restrict__ canon, int n_classes, int eos, int B, int T,
+                                    unsigned char* __restrict__ match) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long long* p = pred + (size_t)b * T;
+  const long long* t = target + (size_t)b * T;
+  int i = 0, j = 0;
+  bool ok = true;
+  while (ok) {
+    unsigned char a = 0, c = 0;
+    while (i < T && p[i] != eos) {                                      // next kept character of the prediction
+      const long long v = p[i++];
+      a = (v >= 0 && v < n_classes) ? canon[v] : 0;
+      if (a) break;
+    }
+    if (i < T && p[i] == eos && !a) i = T;
+    while (j < T && t[j] != eos) {
+      const long long v = t[j++];
+      c = (v >= 0 && v < n_classes) ? canon[v] : 0;
+      if (c) break;
+    }
+    if (j < T && t[j] == eos && !c) j = T;
+    if (a != c) ok = false;
+    if (!a && !c) break;                                                // both strings ended
+  }
+  match[b] = ok ? 1 : 0;
+}
+
+// recognition_f_measure (evaluation_metric/metrics.py:83-100): per sample, the SETS of kept characters of prediction and target
+// (same cut / drop / case-fold rules as the accuracy; canon codes 1..63 -> one bit each), p = n/(|P|+1e-5), r = n/(|T|+1e-5),
+// f = 2pr/(p+r+1e-5), all in double as the reference's Python floats.
+__global__ void char_fmeasure_kernel(const long long* __restrict__ pred, const long long* __restrict__ target,
+                                     const unsigned char* __restrict__ canon, int n_classes, int eos, int B, int T,
+                                     double* __restrict__ f_out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  unsigned long long ps = 0, ts = 0;
+  for (int i = 0; i < T; ++i) {
+    const long long v = pred[(size_t)b * T + i];
+    if (v == eos) break;
+    const unsigned char c = (v >= 0 && v < n_classes) ? canon[v] : 0;
+    if (c) ps |= 1ull << (c & 63);
+  }
+  for (int i = 0; i < T; ++i) {
+    const long long v = target[(size_t)b * T + i];
+    if (v == eos) break;
+    const unsigned char c = (v >= 0 && v < n_classes) ? canon[v] : 0;
+    if (c) ts |= 1ull << (c & 63);
+  }
+  const double n = (double)__popcll(ps & ts);
+  const double p = n / ((double)__popcll(ps) + 1e-5), r = n / ((double)__popcll(ts) + 1e-5);
+  f_out[b] = 2 * p * r / (p + r + 1e-5);
+}
 
 // get_str_list + _normalize_text (metrics.py:14-64) of one tensor: one thread per row.
 __global__ void tokens_to_text_kernel(const long long* __restrict__ tokens, const unsigned char* __restrict__ canon, int n_classes, int eos,
@@ -135,6 +193,21 @@ __global__ void seq_confidence_kernel(const float* __restrict__ score, const int
 inline size_t lev_lds_bytes(int cap) { return (size_t)((cap + 1) / 2) * 64 * sizeof(unsigned); }
 
 }  // namespace
+
+// C-ABI: see include/dig_hip.h
+extern "C" int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
+                                int B, int T, unsigned char* match, hipStream_t stream) {
+  if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  hipLaunchKernelGGL(string_match_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, match);
+  return dig_check_launch();
+}
+
+extern "C" int dig_char_fmeasure(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
+                                 int B, int T, double* f_per_sample, hipStream_t stream) {
+  if (!pred || !target || !canon || !f_per_sample || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  hipLaunchKernelGGL(char_fmeasure_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, f_per_sample);
+  return dig_check_launch();
+}
 
 extern "C" int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text,
                                   int* len, hipStream_t stream) {

@@ -307,8 +307,7 @@ __global__ __launch_bounds__(256) void seq_embed_fwd_kernel(const long long* __r
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)n_tok * d) return;
   const int r = (int)(i / d), c = (int)(i - (size_t)r * d);
-  long long t = tok[r];
-  t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
+  const long long t = clamp_class(tok[r], vocab);
   x[i] = f2bf(emb[(size_t)t * d + c] + pos[(size_t)(r % T) * d + c]);
 }
 
@@ -352,29 +351,6 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_kernel(const long long* __r
   }
   if (k < n) a0 += bf2f(dx[(size_t)list[k] * d + c]);
   demb[(size_t)v * d + c] += a0 + a1;
-}
-
-// dlogits[b,t,:] = g * (softmax(logits[b,t,:]) - onehot(target)) / B for t < length[b], else 0  (gradient of SeqCrossEntropyLoss)
-__global__ __launch_bounds__(64) void seq_ce_bwd_kernel(const float* __restrict__ logits, int ld, const long long* __restrict__ target,
-                                                        const long long* __restrict__ length, const float* __restrict__ g, int T, int C,
-                                                        float inv_B, bf16_t* __restrict__ dlogits, int ldd) {
-  const int row = blockIdx.x, b = row / T, t = row - b * T, lane = threadIdx.x;
-  bf16_t* out = dlogits + (size_t)row * ldd;
-  if (t >= length[b]) {
-    for (int c = lane; c < ldd; c += 64) out[c] = 0;
-    return;
-  }
-  const float* x = logits + (size_t)row * ld;
-  float m = -INFINITY;
-  for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-  m = wave_max(m);
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += __expf(x[c] - m);
-  s = wave_sum(s);
-  const float sc = (g ? g[0] : 1.f) * inv_B, inv = 1.f / s;
-  long long y = target[row];
-  y = y < 0 ? 0 : (y >= C ? C - 1 : y);
-  for (int c = lane; c < ldd; c += 64) out[c] = c < C ? f2bf(sc * (__expf(x[c] - m) * inv - (c == y ? 1.f : 0.f))) : (bf16_t)0;
 }
 
 template <int DK> size_t lds_fwd(int Lk) { return (size_t)MAXQ * DK * 4 + (size_t)MAXQ * Lk * 4 + MAXQ * 4 + (size_t)Lk * DK * 2; }
@@ -487,12 +463,4 @@ extern "C" int dig_seq_embed_bwd_lens(const long long* tokens, const void* dx, f
 
 extern "C" int dig_seq_embed_bwd(const long long* tokens, const void* dx, float* demb, int n_tok, int d, int vocab, hipStream_t stream) {
   return dig_seq_embed_bwd_lens(tokens, dx, demb, n_tok, d, vocab, 0, nullptr, stream);
-}
-
-extern "C" int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar,
-                                         int B, int T, int C, void* dlogits, int ldd, hipStream_t stream) {
-  if (!logits || !target || !length || !dlogits || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(seq_ce_bwd_kernel, dim3(B * T), dim3(64), 0, stream, logits, ld, target, length, gscalar, T, C, 1.0f / (float)B,
-                     (bf16_t*)dlogits, ldd);
-  return dig_check_launch();
 }
