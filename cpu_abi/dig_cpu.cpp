@@ -490,6 +490,7 @@ long long dig_bn_stats_workspace_bytes(int rows, int C) { return (long long)((ro
 
 int dig_bn_stats(const void* x_, float* sums, float* workspace, int rows, int C, hipStream_t) {
   if (!x_ || !sums || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
+  if (!aligned16(x_)) return DIG_ERR_ALIGN;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
   for (int c = 0; c < C; ++c) {
@@ -505,6 +506,7 @@ int dig_bn_fwd_apply(const void* x_, const float* sums, float n_total, float eps
                      float* mean_out, float* rstd_out, int rows, int C, hipStream_t) {
   if (!x_ || !sums || !y_ || !mean_out || !rstd_out || rows <= 0 || C <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
   if ((gamma == nullptr) != (beta == nullptr)) return DIG_ERR_ARG;
+  if (!aligned16(x_) || !aligned16(y_) || !aligned16(sums) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
   const float inv_n = 1.0f / n_total;
@@ -543,6 +545,8 @@ int dig_bn_fwd_fused(const void* x_, float eps, const float* gamma, const float*
   if (!x_ || !y_ || !mean_out || !rstd_out || (gamma == nullptr) != (beta == nullptr) || (running_mean == nullptr) != (running_var == nullptr))
     return DIG_ERR_ARG;
   if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
+  if (!aligned16(x_) || !aligned16(y_) || !aligned16(mean_out) || !aligned16(rstd_out) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
+      (running_mean && (!aligned16(running_mean) || !aligned16(running_var)))) return DIG_ERR_ALIGN;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
   const float n = (float)rows, inv_n = 1.0f / n;
@@ -578,6 +582,8 @@ int dig_bn_bwd_fused(const void* dy_, const void* x_, const float* mean, const f
   if (!dy_ || !x_ || !mean || !rstd || !dx_ || (gamma == nullptr) != (beta == nullptr) || (dbeta_acc == nullptr) != (dgamma_acc == nullptr))
     return DIG_ERR_ARG;
   if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
+  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(dx_) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
+      (dbeta_acc && (!aligned16(dbeta_acc) || !aligned16(dgamma_acc)))) return DIG_ERR_ALIGN;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* dx = (bf16_t*)dx_;
@@ -622,6 +628,7 @@ int dig_bn_fwd_apply_running(const void* x, const float* sums, float n_total, fl
 int dig_bn_bwd_stats(const void* dy_, const void* x_, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                      float* sums, float* workspace, int rows, int C, hipStream_t) {
   if (!dy_ || !x_ || !mean || !rstd || !sums || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
+  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
@@ -653,6 +660,8 @@ int dig_bn_bwd_stats_acc(const void* dy, const void* x, const float* mean, const
 int dig_bn_bwd_apply(const void* dy_, const void* x_, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                      const float* sums, float n_total, void* dx_, int rows, int C, hipStream_t) {
   if (!dy_ || !x_ || !mean || !rstd || !sums || !dx_ || rows <= 0 || C <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
+  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(dx_) || !aligned16(mean) || !aligned16(rstd) || !aligned16(sums) ||
+      (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* dx = (bf16_t*)dx_;

@@ -668,7 +668,9 @@ extern "C" int dig_bn_fwd_fused(const void* x, float eps, const float* gamma, co
   if (!x || !y || !mean_out || !rstd_out || (gamma == nullptr) != (beta == nullptr) || (running_mean == nullptr) != (running_var == nullptr))
     return DIG_ERR_ARG;
   if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(x) || !aligned16(y)) return DIG_ERR_ALIGN;
+  // gamma / beta are read with 16-byte loads (load8f); the statistics and running vectors are held to the three-launch path's rule
+  if (!aligned16(x) || !aligned16(y) || !aligned16(mean_out) || !aligned16(rstd_out) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
+      (running_mean && (!aligned16(running_mean) || !aligned16(running_var)))) return DIG_ERR_ALIGN;
   hipLaunchKernelGGL(bn_fused_kernel<0>, dim3(C / BNF_COLS), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, gamma, beta, relu, eps, (bf16_t*)y, mean_out, rstd_out, momentum, running_mean, running_var,
                      (float*)nullptr, (float*)nullptr, rows, C);
@@ -680,7 +682,8 @@ extern "C" int dig_bn_bwd_fused(const void* dy, const void* x, const float* mean
   if (!dy || !x || !mean || !rstd || !dx || (gamma == nullptr) != (beta == nullptr) || (dbeta_acc == nullptr) != (dgamma_acc == nullptr))
     return DIG_ERR_ARG;
   if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(x) || !aligned16(dy) || !aligned16(dx)) return DIG_ERR_ALIGN;
+  if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
+      (dbeta_acc && (!aligned16(dbeta_acc) || !aligned16(dgamma_acc)))) return DIG_ERR_ALIGN;   // mean / rstd / gamma / beta: 16-byte loads (load8f)
   hipLaunchKernelGGL(bn_fused_kernel<1>, dim3(C / BNF_COLS), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, mean, rstd, gamma, beta,
                      relu, 0.f, (bf16_t*)dx, (float*)nullptr, (float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr, dbeta_acc, dgamma_acc, rows, C);
   return dig_check_launch();

@@ -272,7 +272,8 @@ int dig_bn_bwd_stats_acc(const void* dy, const void* x, const float* mean, const
  * (statistics over these rows, biased variance, running statistics with n / (n - 1)); the summation order over rows differs, so the two
  * paths agree to fp32 round-off.  dig_bn_fused_supported: 2 <= rows <= 4096, C a multiple of 32 and >= 256.
  * dig_bn_bwd_fused: dx = gamma rstd (g - mean_r(g) - xhat mean_r(g xhat)), g = dy under the ReLU mask; dbeta_acc / dgamma_acc (both or
- * neither) += sum g, sum g xhat. */
+ * neither) += sum g, sum g xhat.  Every fp32 vector (gamma, beta, mean, rstd, the running statistics, the accumulators) is 16-byte aligned,
+ * as in the three-launch path: DIG_ERR_ALIGN otherwise, before anything is launched. */
 int dig_bn_fused_supported(int rows, int C);
 int dig_bn_fwd_fused(const void* x, float eps, const float* gamma, const float* beta, int relu, void* y, float* mean_out, float* rstd_out,
                      float momentum, float* running_mean, float* running_var, int rows, int C, hipStream_t stream);
