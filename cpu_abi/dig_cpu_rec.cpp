@@ -1115,4 +1115,108 @@ int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int bl
   return DIG_OK;
 }
 
+// Lexicon decode, the rule of include/dig_hip.h as written: per sample the frames' log-softmax once (double differences and sum,
+// rounded to fp32), per word the device's recursion (fp32 in log space, re-centred every frame, the removed maxima summed in double),
+// and a strict "greater" scan in range order for the first best word.
+static float ctc_lse2f(float a, float b) {
+  const float m = std::max(a, b);
+  if (m == -std::numeric_limits<float>::infinity()) return m;
+  return m + std::log(std::exp(a - m) + std::exp(b - m));
+}
+static float ctc_lse3f(float a, float b, float c) {
+  const float m = std::max(std::max(a, b), c);
+  if (m == -std::numeric_limits<float>::infinity()) return m;
+  return m + std::log(std::exp(a - m) + std::exp(b - m) + std::exp(c - m));
+}
+
+// log p(word | the T x C log-softmax table lp), -inf for a word that cannot be scored
+static float ctc_lex_word_score(const float* lp, int T, int C, int blank, const int* lab, int n) {
+  const float NINF = -std::numeric_limits<float>::infinity();
+  int rep = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lab[i] < 0 || lab[i] >= C || lab[i] == blank) return NINF;
+    if (i && lab[i] == lab[i - 1]) ++rep;
+  }
+  if (n + rep > T) return NINF;
+  float ab[64], al[64], nb[64], nl[64];                                 // state 2i (the blank in front of label i; i = n: the last blank), 2i + 1
+  for (int i = 0; i <= n; ++i) ab[i] = al[i] = NINF;
+  ab[0] = lp[blank];
+  if (n) al[0] = lp[lab[0]];
+  double off = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const float* row = lp + (size_t)t * C;
+    if (t) {
+      for (int i = 0; i <= n; ++i) {
+        const float pl = i ? al[i - 1] : NINF;
+        nb[i] = ctc_lse2f(ab[i], pl) + row[blank];
+        nl[i] = i < n ? ctc_lse3f(al[i], ab[i], (i && lab[i] == lab[i - 1]) ? NINF : pl) + row[lab[i]] : NINF;
+      }
+      for (int i = 0; i <= n; ++i) { ab[i] = nb[i]; al[i] = nl[i]; }
+    }
+    float m = NINF;
+    for (int i = 0; i <= n; ++i) m = std::max(m, std::max(ab[i], al[i]));
+    for (int i = 0; i <= n; ++i) { ab[i] -= m; al[i] -= m; }
+    off += (double)m;
+  }
+  const float tail = ctc_lse2f(ab[n], n ? al[n - 1] : NINF);
+  const double logp = off + (double)tail;
+  return (tail > NINF && logp == logp && logp > -1e300) ? (float)logp : NINF;
+}
+
+static long long ctc_lex_chunks(int max_count) { return ((long long)max_count + DIG_CTC_LEX_CHUNK - 1) / DIG_CTC_LEX_CHUNK; }
+
+long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count) {
+  if (B <= 0 || T <= 0 || C <= 0 || max_count < 0) return 0;
+  return (long long)B * std::max(1LL, ctc_lex_chunks(max_count)) * 8 + (long long)B * T * C * 4;
+}
+
+int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, const int* words,
+                           const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count, int* best_index,
+                           float* logp, long long* ids, float* score, int* n, float* scores, void* workspace, long long workspace_bytes,
+                           hipStream_t) {
+  if (!logits || !words || !word_len || !lex_begin || !lex_count || !best_index || !logp || !ids || !score || !n || !workspace) return DIG_ERR_ARG;
+  if (B < 0 || T <= 0 || C <= 0 || ldw <= 0 || ld < C || blank < 0 || blank >= C || W < 0 || max_count < 0) return DIG_ERR_ARG;
+  if (T > 64 || C < 2 || C > 256 || ldw > 63 || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if (B == 0) return DIG_OK;
+  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
+  if (workspace_bytes < dig_ctc_lexicon_workspace_bytes(B, T, C, max_count)) return DIG_ERR_ARG;
+  const float NINF = -std::numeric_limits<float>::infinity();
+  std::vector<float> lp((size_t)T * C);
+  for (int b = 0; b < B; ++b) {
+    for (int t = 0; t < T; ++t) {
+      const float* row = logits + ((size_t)b * T + t) * ld;
+      float m = row[0];
+      for (int c = 1; c < C; ++c) m = std::max(m, row[c]);
+      double e = 0.0;
+      for (int c = 0; c < C; ++c) e += (double)std::exp((float)((double)row[c] - (double)m));
+      const double ls = std::log(e);
+      for (int c = 0; c < C; ++c) lp[(size_t)t * C + c] = (float)((double)row[c] - (double)m - ls);
+    }
+    const int begin = std::clamp(lex_begin[b], 0, W);
+    const int count = std::clamp(lex_count[b], 0, std::min(W - begin, max_count));
+    int best = -1;
+    float bs = NINF;
+    for (int j = 0; j < max_count; ++j) {
+      float s = NINF;
+      if (j < count) {
+        const int w = begin + j;
+        s = ctc_lex_word_score(lp.data(), T, C, blank, words + (size_t)w * ldw, std::clamp(word_len[w], 0, ldw));
+        if (s > bs) { bs = s; best = w; }                               // (strict: the first of equal scores)
+      }
+      if (scores) scores[(size_t)b * max_count + j] = s;
+    }
+    const int len = best < 0 ? 0 : std::clamp(word_len[best], 0, std::min(ldw, T));
+    long long* idr = ids + (size_t)b * (T + 1);
+    float* scr = score + (size_t)b * (T + 1);
+    for (int j = 0; j <= T; ++j) {
+      idr[j] = j < len ? (long long)words[(size_t)best * ldw + j] : (j == len ? eos : padding);
+      scr[j] = j == 0 ? (best < 0 ? 0.f : (float)std::exp((double)bs)) : 1.f;
+    }
+    best_index[b] = best;
+    logp[b] = bs;
+    n[b] = len;
+  }
+  return DIG_OK;
+}
+
 }  // extern "C"

@@ -4,6 +4,7 @@
 //   dig_ctc_loss_bwd       d loss / d logits * gscalar = gscalar / B * (softmax - posterior occupancy of the class)
 //   dig_ctc_greedy_decode  the string rule of ctc_get_str_list (evaluation_metric/metrics.py:220-227) as decoder-shaped rows
 //   dig_ctc_beam_decode    prefix beam search (`--ctc_beam_width`): the best collapsed string over all its alignments, as the same rows
+//   dig_ctc_lexicon_decode the lexicon word of highest likelihood (`--ctc_lexicon`): one alpha recursion per (sample, word), as the same rows
 //
 // One wave per sample.  The extended label sequence blank, l_0, blank, l_1, ..., l_{n-1}, blank has 2n + 1 <= 127 states: lane i owns
 // state 2i (the blank in front of label i; lane n: the final blank) and state 2i + 1 (label i), so a time step moves ONE value between
@@ -78,9 +79,11 @@ __device__ __forceinline__ void ctc_emissions(const float* __restrict__ x, int l
   }
 }
 
-// One step of the alpha recursion (t > 0) from the states of frame t - 1.
+// One step of the alpha recursion (t > 0) from the states of frame t - 1.  SEG: the lanes that hold one sample (64: the whole wave;
+// 16 / 32: the lexicon decode packs 4 / 2 short words into a wave), `lane` counted within them.
+template <int SEG = 64>
 __device__ __forceinline__ void ctc_alpha_step(float& ab, float& al, float eb, float el, const CtcSample& s, int lane) {
-  float pl = __shfl_up(al, 1, 64);                                       // the label state of lane - 1
+  float pl = __shfl_up(al, 1, SEG);                                      // the label state of lane - 1
   if (lane == 0) pl = -INFINITY;
   const float nb = lane <= s.n ? lse2(ab, pl) + eb : -INFINITY;
   const float nl = lane < s.n ? lse3(al, ab, s.rep ? -INFINITY : pl) + el : -INFINITY;
@@ -452,6 +455,178 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
   if (lane == 0) { n_out[b] = n; logp_out[b] = lp0; }
 }
 
+// ---- lexicon decode (the rule: include/dig_hip.h at dig_ctc_lexicon_decode): s(b, w) = log p(labels_w | frames of b) for every word of the
+// sample's range, and the best (s, lowest pool index) pair.  Three launches.  (1) ctc_lex_softmax_kernel: the log-softmax of every frame,
+// once per sample, as ctc_emissions takes it (differences and sum in double, rounded to fp32 once), into the workspace as [B][T][C].
+// (2) ctc_lex_score_kernel: workgroup (chunk, sample) of 4 waves copies the sample's table into LDS (dynamic, T * C floats) and walks the
+// CTC_LEX_CHUNK words of its chunk.  Lexicon words are short, so a wave carries 64 / SEG of them at once: the chunk's longest word picks
+// SEG = 16 (up to 15 labels), 32 (up to 31) or 64, each word on SEG consecutive lanes with the state layout of ctc_kernel (lane i of the
+// segment: the blank in front of label i and label i; lane n: the final blank), the same ctc_alpha_step, the same re-centring and the
+// same double offset, so a score has the bits of ctc_kernel<false>'s -nll.  A word's emissions are gathered from the LDS table by the
+// lane's label.  The chunk's best pair is kept as one 64-bit key (the score's bits made monotonic, then the complement of the pool index:
+// the larger key is the larger score, and among equal scores the lower index) and left in the workspace; keys are distinct, so their
+// maximum does not depend on the cut.  (3) ctc_lex_fold_kernel: one wave per sample takes the largest key and writes the outputs.
+// (One word per wave for every chunk was measured at 2.5 to 4 times the time: profiles/README.md.)
+constexpr int CTC_LEX_CHUNK = DIG_CTC_LEX_CHUNK, CTC_LEX_WAVES = 4;
+constexpr unsigned long long CTC_LEX_NONE = 0ull;                          // (below the key of any score above -inf)
+
+__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ unsigned long long ctc_lex_key(float s, int w) {
+  if (!(s > -INFINITY)) return CTC_LEX_NONE;
+  if (s == 0.f) s = 0.f;                                                   // (-0 and +0 are one score)
+  const unsigned u = __float_as_uint(s);
+  const unsigned mono = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)mono << 32) | (unsigned)~(unsigned)w;
+}
+__device__ __forceinline__ float ctc_lex_key_score(unsigned long long key) {
+  const unsigned mono = (unsigned)(key >> 32);
+  return __uint_as_float((mono & 0x80000000u) ? (mono & 0x7fffffffu) : ~mono);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long u = __shfl_xor(v, o, 64);
+    v = u > v ? u : v;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(64) void ctc_lex_softmax_kernel(const float* __restrict__ logits, int ld, int C, float* __restrict__ lp) {
+  const int lane = threadIdx.x;
+  const float* row = logits + (size_t)blockIdx.x * ld;                     // frame (b, t) = blockIdx.x
+  float* out = lp + (size_t)blockIdx.x * C;
+  const float m = row_max(row, C, lane);
+  double e = 0.0;
+  for (int c = lane; c < C; c += 64) e += (double)expf((float)((double)row[c] - (double)m));
+  const double ls = log(wave_sum_f64(e));
+  for (int c = lane; c < C; c += 64) out[c] = (float)((double)row[c] - (double)m - ls);
+}
+
+// The words k0 + slot, k0 + slot + 256 / SEG, ... of the chunk (slot = the thread's segment within the workgroup): returns the best key
+// of the thread's segment on its lane 0, CTC_LEX_NONE on the other lanes.
+template <int SEG>
+__device__ __forceinline__ unsigned long long ctc_lex_words(const float* __restrict__ tab, int T, int C, int blank, const int* __restrict__ words,
+                                                            const int* __restrict__ word_len, int ldw, int w0, int nw, float* __restrict__ srow) {
+  constexpr int PER = CTC_LEX_WAVES * 64 / SEG;                            // words in flight per workgroup
+  const int lane = threadIdx.x & 63, li = lane & (SEG - 1), sbase = lane & ~(SEG - 1), slot = (int)threadIdx.x / SEG;
+  const unsigned long long smask = SEG == 64 ? ~0ull : ((1ull << SEG) - 1ull);
+  unsigned long long best = CTC_LEX_NONE;
+  for (int k0 = 0; k0 < nw; k0 += PER) {
+    if (k0 + (int)(threadIdx.x >> 6) * (64 / SEG) >= nw) break;            // (wave-uniform: none of the wave's segments has a word)
+    const int k = k0 + slot;
+    const bool have = k < nw;
+    const int w = w0 + (have ? k : 0);
+    CtcSample s;
+    s.n = have ? clamp_i(word_len[w], 0, min(ldw, SEG - 1)) : 0;
+    const int l = li < s.n ? words[(size_t)w * ldw + li] : 0;
+    const bool bad = li < s.n && (l < 0 || l >= C || l == blank);
+    s.lab = bad ? 0 : l;
+    const int prev = __shfl_up(s.lab, 1, SEG);
+    s.rep = li > 0 && li < s.n && s.lab == prev;
+    const int nrep = __popcll((__ballot(s.rep) >> sbase) & smask);
+    s.ok = ((__ballot(bad) >> sbase) & smask) == 0ull && s.n + nrep <= T;
+    float ab = li == 0 ? tab[blank] : -INFINITY;
+    float al = (li == 0 && s.n > 0) ? tab[s.lab] : -INFINITY;
+    double off = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const float* row = tab + t * C;
+      if (t) ctc_alpha_step<SEG>(ab, al, row[blank], li < s.n ? row[s.lab] : -INFINITY, s, li);
+      float m = fmaxf(ab, al);
+#pragma unroll
+      for (int o = SEG / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));   // the segment's maximum: finite (the all-blank prefix)
+      ab -= m;
+      al -= m;
+      off += (double)m;
+    }
+    const float fb = __shfl(ab, s.n, SEG);
+    const float fl = s.n > 0 ? __shfl(al, s.n - 1, SEG) : -INFINITY;
+    const float tail = lse2(fb, fl);
+    const double logp = off + (double)tail;
+    const bool ok = s.ok && tail > -INFINITY && logp == logp && logp > -1e300;
+    const float sc = ok ? (float)logp : -INFINITY;
+    if (have && li == 0) {
+      if (srow) srow[k] = sc;
+      const unsigned long long key = ctc_lex_key(sc, w);
+      best = key > best ? key : best;
+    }
+  }
+  return best;
+}
+
+__global__ __launch_bounds__(CTC_LEX_WAVES * 64) void ctc_lex_score_kernel(const float* __restrict__ lp, int T, int C, int blank,
+                                                                          const int* __restrict__ words, const int* __restrict__ word_len, int ldw,
+                                                                          int W, const int* __restrict__ lex_begin, const int* __restrict__ lex_count,
+                                                                          int max_count, int n_chunks, unsigned long long* __restrict__ partial,
+                                                                          float* __restrict__ scores) {
+  extern __shared__ __attribute__((aligned(16))) float lex_tab[];          // [T][C]; filled 16 bytes at a time where the source allows
+  __shared__ unsigned long long wbest[CTC_LEX_WAVES];
+  const int tid = threadIdx.x, b = blockIdx.y, chunk = blockIdx.x;
+  const int begin = clamp_i(lex_begin[b], 0, W);
+  const int count = clamp_i(lex_count[b], 0, min(W - begin, max_count));
+  const int c0 = chunk * CTC_LEX_CHUNK;                                    // (n_chunks * CHUNK < 2^31 + CHUNK: the launcher sees to it)
+  const int nw = min(count - c0, CTC_LEX_CHUNK);                           // the chunk's words; <= 0: past the range
+  float* srow = scores ? scores + (size_t)b * max_count + c0 : nullptr;
+  if (srow)
+    for (int j = tid; j < CTC_LEX_CHUNK; j += CTC_LEX_WAVES * 64)
+      if (j >= nw && j < max_count - c0) srow[j] = -INFINITY;
+  if (nw <= 0) {                                                           // (workgroup-uniform)
+    if (tid == 0) partial[(size_t)b * n_chunks + chunk] = CTC_LEX_NONE;
+    return;
+  }
+  const int w0 = begin + c0;
+  int len = 0;
+  for (int j = tid; j < nw; j += CTC_LEX_WAVES * 64) len = max(len, clamp_i(word_len[w0 + j], 0, ldw));
+  const int over31 = __syncthreads_or(len > 31), over15 = __syncthreads_or(len > 15);
+  {
+    const float* src = lp + (size_t)b * T * C;
+    const int n = T * C;
+    if ((n & 3) == 0 && (((uintptr_t)src) & 15u) == 0) {
+      for (int i = tid; i < (n >> 2); i += CTC_LEX_WAVES * 64) ((float4*)lex_tab)[i] = ((const float4*)src)[i];
+    } else {
+      for (int i = tid; i < n; i += CTC_LEX_WAVES * 64) lex_tab[i] = src[i];
+    }
+  }
+  __syncthreads();
+  unsigned long long best;
+  if (over31) best = ctc_lex_words<64>(lex_tab, T, C, blank, words, word_len, ldw, w0, nw, srow);
+  else if (over15) best = ctc_lex_words<32>(lex_tab, T, C, blank, words, word_len, ldw, w0, nw, srow);
+  else best = ctc_lex_words<16>(lex_tab, T, C, blank, words, word_len, ldw, w0, nw, srow);
+  best = wave_max_u64(best);
+  if ((tid & 63) == 0) wbest[tid >> 6] = best;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 1; i < CTC_LEX_WAVES; ++i) best = wbest[i] > best ? wbest[i] : best;
+    partial[(size_t)b * n_chunks + chunk] = best;
+  }
+}
+
+// One wave per sample: the largest key of its chunks, then the decoder-shaped row of the chosen word (the empty row when there is none).
+__global__ __launch_bounds__(64) void ctc_lex_fold_kernel(const unsigned long long* __restrict__ partial, int n_chunks, const int* __restrict__ words,
+                                                          const int* __restrict__ word_len, int ldw, int T, int eos, int padding,
+                                                          int* __restrict__ best_index, float* __restrict__ logp, long long* __restrict__ ids,
+                                                          float* __restrict__ score, int* __restrict__ n_out) {
+  const int lane = threadIdx.x, b = blockIdx.x;
+  unsigned long long key = CTC_LEX_NONE;
+  for (int c = lane; c < n_chunks; c += 64) {
+    const unsigned long long o = partial[(size_t)b * n_chunks + c];
+    key = o > key ? o : key;
+  }
+  key = wave_max_u64(key);
+  const bool none = key == CTC_LEX_NONE;
+  const int w = none ? -1 : (int)~(unsigned)key;
+  const float lpb = none ? -INFINITY : ctc_lex_key_score(key);
+  const int n = none ? 0 : clamp_i(word_len[w], 0, min(ldw, T));           // (a scored word has n + repeats <= T)
+  long long* idr = ids + (size_t)b * (T + 1);
+  float* scr = score + (size_t)b * (T + 1);
+  for (int j = lane; j <= T; j += 64) {
+    idr[j] = j < n ? (long long)words[(size_t)w * ldw + j] : (j == n ? eos : padding);
+    scr[j] = j == 0 ? (none ? 0.f : (float)exp((double)lpb)) : 1.f;
+  }
+  if (lane == 0) { best_index[b] = w; logp[b] = lpb; n_out[b] = n; }
+}
+
 int ctc_check(const void* logits, int ld, const void* target, int ldt, const void* target_len, int B, int T, int C, int blank) {
   if (!logits || !target || !target_len || B < 0 || T <= 0 || C <= 0 || ldt <= 0 || ld < C || blank < 0 || blank >= C) return DIG_ERR_ARG;
   if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || ldt > CTC_MAX_LDT) return DIG_ERR_UNSUPPORTED;
@@ -498,5 +673,44 @@ extern "C" int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, in
   if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), (size_t)((beam_width * ((C + 63) / 64 * 64) + 255) & ~255) * sizeof(float), stream, logits, ld, T, C, blank, eos, padding,
                      beam_width, ids, score, logp, n);
+  return dig_check_launch();
+}
+
+static inline long long ctc_lex_chunks(int max_count) { return ((long long)max_count + CTC_LEX_CHUNK - 1) / CTC_LEX_CHUNK; }
+
+extern "C" long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count) {
+  if (B <= 0 || T <= 0 || C <= 0 || max_count < 0) return 0;
+  const long long keys = (long long)B * std::max(1LL, ctc_lex_chunks(max_count)) * (long long)sizeof(unsigned long long);
+  return keys + (long long)B * T * C * (long long)sizeof(float);
+}
+
+extern "C" int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, const int* words,
+                                      const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count,
+                                      int* best_index, float* logp, long long* ids, float* score, int* n, float* scores, void* workspace,
+                                      long long workspace_bytes, hipStream_t stream) {
+  if (!logits || !words || !word_len || !lex_begin || !lex_count || !best_index || !logp || !ids || !score || !n || !workspace) return DIG_ERR_ARG;
+  if (B < 0 || T <= 0 || C <= 0 || ldw <= 0 || ld < C || blank < 0 || blank >= C || W < 0 || max_count < 0) return DIG_ERR_ARG;
+  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || ldw > CTC_MAX_LDT || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if (B == 0) return DIG_OK;
+  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
+  if (workspace_bytes < dig_ctc_lexicon_workspace_bytes(B, T, C, max_count)) return DIG_ERR_ARG;
+  const int n_chunks = (int)ctc_lex_chunks(max_count);                     // 0 with max_count == 0: nothing to score
+  unsigned long long* partial = (unsigned long long*)workspace;
+  float* lp = (float*)(partial + (size_t)B * std::max(1, n_chunks));
+  if (n_chunks > 0) {
+    const size_t lds = (size_t)T * C * sizeof(float);                      // 12.5 KB at the recipe shape, 64 KB at the limits
+    static bool attr_set[DIG_MAX_DEVICES] = {};
+    const int dev = dig_device();
+    if (!attr_set[dev]) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ctc_lex_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                CTC_MAX_T * CTC_MAX_C * (int)sizeof(float));
+      attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(ctc_lex_softmax_kernel, dim3(B * T), dim3(64), 0, stream, logits, ld, C, lp);
+    hipLaunchKernelGGL(ctc_lex_score_kernel, dim3(n_chunks, B), dim3(CTC_LEX_WAVES * 64), lds, stream, (const float*)lp, T, C, blank, words, word_len,
+                       ldw, W, lex_begin, lex_count, max_count, n_chunks, partial, scores);
+  }
+  hipLaunchKernelGGL(ctc_lex_fold_kernel, dim3(B), dim3(64), 0, stream, (const unsigned long long*)partial, n_chunks, words, word_len, ldw, T, eos,
+                     padding, best_index, logp, ids, score, n);
   return dig_check_launch();
 }

@@ -11,11 +11,15 @@ EOS (`len_offset` = 1 on the datasets' lengths, which count EOS); `decode` retur
 emitting frames' softmax probabilities as scores.  `--ctc_beam_width K` (own flag, 1..32; `ctc_beam_width` here) makes the evaluation decode a
 prefix beam search of width K, which scores a string by the sum over all its alignments where greedy decoding scores the single best
 alignment; the rule is this project's (the reference has no CTC beam search) and stands in include/dig_hip.h at `dig_ctc_beam_decode`; its
-rows carry the string's probability in score[:, 0] and 1 elsewhere.  Training-mode decodes (the loop's class accuracy) stay greedy.
+rows carry the string's probability in score[:, 0] and 1 elsewhere.  `--ctc_lexicon FILE` (own flag; `ctc_lexicon` here, a `LabelLexicon`)
+makes the evaluation decode the lexicon word of highest likelihood: `dig_ctc_lexicon_decode` scores every (image, word) pair by the sum over
+all alignments, the quantity the criterion computes, where the reference's lexicon metrics snap a decoded string to the nearest word by edit
+distance; rows as the beam's.  Training-mode decodes (the loop's class accuracy) stay greedy.
 
 Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (model and step on dig_amd.finetune.EncoderTrain / _EncoderStep); the head is
 `dig_window_pool_*` (the `--use_1d_attdec` pooling), two GEMMs and the fused LayerNorm + GELU launch; loss, gradient and decode are
 csrc/ctc.hip.  There is no CPU fallback."""
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -27,7 +31,7 @@ PRE = "ctc_classifier."
 D_EMBEDDING = 512                                       # model_builder.py:13
 
 
-# ---------------------------------------------------------------------------------------------- the four entry points
+# ---------------------------------------------------------------------------------------------- the entry points
 def ctc_loss(logits, C, target, length, blank, len_offset=1):
     """dig_ctc_loss on logits fp32 [B, T, ld >= C]: (nll [B], loss [1])."""
     B, T, ld = logits.shape
@@ -74,6 +78,150 @@ def ctc_beam_decode(logits, C, blank, eos, padding, beam_width):
     L.call("dig_ctc_beam_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, int(beam_width), L.ptr(ids), L.ptr(score), L.ptr(logp), L.ptr(n),
            L.stream())
     return ids, score, logp, n
+
+
+LEX_CHUNK = L.const("DIG_CTC_LEX_CHUNK")                # words per workgroup of the lexicon decode
+MAX_LEX_WORD_LEN = 63                                   # csrc/ctc.hip: lane i of a wave owns label i, lane n the final blank
+
+
+def ctc_lexicon_workspace_bytes(B, T, C, max_count):
+    return L.query("dig_ctc_lexicon_workspace_bytes", B, T, C, max_count)
+
+
+def ctc_lexicon_decode(logits, C, blank, eos, padding, pool, lex_begin, lex_count, want_scores=False):
+    """dig_ctc_lexicon_decode (the rule in include/dig_hip.h) on logits fp32 [B, T, ld >= C]: sample b takes the word of highest CTC
+    likelihood among pool rows [lex_begin[b], lex_begin[b] + lex_count[b]).  pool: a `LabelLexicon`, or (labels int32 [W, ldw], lengths
+    int32 [W]) on the logits' device.  lex_begin / lex_count are host sequences; a range outside the pool is refused here, before upload.
+    Returns (best_index int32 [B] (-1: no word), logp fp32 [B], ids int64 [B, T + 1], score fp32 [B, T + 1] = exp(logp) then 1, n int32 [B])
+    and, with want_scores, scores fp32 [B, max(lex_count)] (log-likelihood per range position, -inf past the range)."""
+    B, T, ld = logits.shape
+    dev = logits.device
+    words, word_len = pool.device(dev) if isinstance(pool, LabelLexicon) else pool
+    W = pool.n_rows if isinstance(pool, LabelLexicon) else words.shape[0]
+    begin, count = np.asarray(lex_begin, dtype=np.int64).reshape(-1), np.asarray(lex_count, dtype=np.int64).reshape(-1)
+    if begin.shape != (B,) or count.shape != (B,):
+        raise ValueError(f"lex_begin / lex_count need one entry per sample ({B})")
+    bad = np.nonzero((begin < 0) | (count < 0) | (begin + count > W))[0]
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"lexicon range of sample {b} ([{int(begin[b])}, {int(begin[b] + count[b])})) is outside the pool of {W} words")
+    if words.shape[0] == 0:                                                # (an empty tensor has no address to hand over)
+        words, word_len = torch.zeros((1, max(words.shape[1], 1)), device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.int32)
+    max_count = int(count.max()) if B else 0
+    best_index = torch.empty(B, device=dev, dtype=torch.int32)
+    logp = torch.empty(B, device=dev, dtype=F32)
+    ids = torch.empty((B, T + 1), device=dev, dtype=torch.int64)
+    score = torch.empty((B, T + 1), device=dev, dtype=F32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    scores = torch.empty((B, max_count), device=dev, dtype=F32) if want_scores else None
+    if B:
+        ranges = torch.from_numpy(np.stack([begin, count]).astype(np.int32)).to(dev)
+        ws_bytes = ctc_lexicon_workspace_bytes(B, T, C, max_count)
+        ws = torch.empty(ws_bytes // 8 + 1, device=dev, dtype=torch.int64)
+        L.call("dig_ctc_lexicon_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, L.ptr(words), L.ptr(word_len), words.shape[1], W,
+               L.ptr(ranges[0]), L.ptr(ranges[1]), max_count, L.ptr(best_index), L.ptr(logp), L.ptr(ids), L.ptr(score), L.ptr(n),
+               L.ptr(scores) if want_scores and max_count else None, L.ptr(ws), ws_bytes, L.stream())
+    return (best_index, logp, ids, score, n, scores) if want_scores else (best_index, logp, ids, score, n)
+
+
+_VOC_BY_CLASSES = {71: "LOWERCASE", 65: "ALLCASES", 97: "ALLCASES_SYMBOLS"}     # len(datasets.find_classes(voc_type))
+
+
+class LabelLexicon:
+    """Host preparation of a lexicon for `ctc_lexicon_decode`, done once: `{name: [words]}` (per-image lexicons; identical lists are stored
+    once and share their range) or one flat list of words (name None), as rows of class ids.
+
+    A word is encoded by the datasets' `LabelEncoder` rule of `voc_type`: `normalize` applies (a LOWERCASE vocabulary folds) and a character
+    outside the vocabulary becomes UNKNOWN, an ordinary class.  For the case-sensitive vocabularies (ALLCASES, ALLCASES_SYMBOLS) a word
+    contributes up to four rows: as written, lower(), upper() and capitalize(), de-duplicated per word (`casings=False`: as written only),
+    so that an upper-case benchmark lexicon can match a model that writes lower case.  `row_word[r]` is the index into `words` (the raw
+    words of all lists, in order) of the raw word row r stands for; `word_of(r)` is that word.  A word of more than 63 labels is refused.
+
+    Row order: within a range the rows are sorted by length, then by original order (word by word, casings in the order above).  The decode
+    takes the first row among equal likelihoods, so its tie rule reads: shortest first, then first listed.  Sorting also keeps words of
+    one length in one workgroup, which lets the kernel pack four short words into a wave.  `device(dev)` uploads once per device."""
+
+    def __init__(self, words, voc_type="ALLCASES_SYMBOLS", casings=None):
+        from .datasets import LabelEncoder
+        enc = LabelEncoder(voc_type, MAX_LEX_WORD_LEN + 1, "cpu")          # (the vocabulary and `normalize` only: nothing is launched)
+        self.voc_type, self.nb_classes = voc_type, enc.nb_classes
+        self.casings = (voc_type != "LOWERCASE") if casings is None else bool(casings)
+        by_name = words if isinstance(words, dict) else {None: list(words)}
+        self.ranges, self._lists, self.words = {}, {}, []
+        rows, row_word, seen = [], [], {}
+        for name, lst in by_name.items():
+            key = tuple(lst)
+            r = seen.get(key)
+            if r is None:
+                base, mine = len(self.words), []
+                for i, w in enumerate(key):
+                    forms = (w, w.lower(), w.upper(), w.capitalize()) if self.casings else (w,)
+                    done = set()
+                    for f in forms:
+                        labels = tuple(enc.class_to_idx.get(c, enc.unknown) for c in enc.normalize(f))
+                        if len(labels) > MAX_LEX_WORD_LEN:
+                            raise ValueError(f"lexicon word longer than {MAX_LEX_WORD_LEN} labels ({len(labels)}) in {name!r}: {w!r}")
+                        if labels not in done:
+                            done.add(labels)
+                            mine.append((len(labels), len(mine), labels, base + i))
+                mine.sort(key=lambda t: t[:2])
+                r = seen[key] = (len(rows), len(mine), list(key))
+                rows.extend(t[2] for t in mine)
+                row_word.extend(t[3] for t in mine)
+                self.words.extend(key)
+            self.ranges[name] = r[:2]
+            self._lists[name] = r[2]
+        self.n_rows = len(rows)
+        ld = max([len(r) for r in rows] + [1])
+        self.labels, self.label_len = np.zeros((max(self.n_rows, 1), ld), dtype=np.int32), np.zeros(max(self.n_rows, 1), dtype=np.int32)
+        for i, r in enumerate(rows):
+            self.labels[i, :len(r)] = r
+            self.label_len[i] = len(r)
+        self.row_word = np.asarray(row_word, dtype=np.int64)
+        self._dev, self._norm_host, self._norm_dev = {}, None, {}
+
+    def __getitem__(self, name):
+        return self._lists[name]
+
+    def __contains__(self, name):
+        return name in self._lists
+
+    def __len__(self):
+        return len(self._lists)
+
+    def keys(self):
+        return self._lists.keys()
+
+    def word_of(self, row):
+        """The raw word pool row `row` stands for; None for -1 (no word)."""
+        return None if row < 0 else self.words[int(self.row_word[row])]
+
+    def device(self, dev):
+        """(labels int32 [max(n_rows, 1), ld], lengths int32) on `dev`."""
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = (torch.from_numpy(self.labels).to(dev), torch.from_numpy(self.label_len).to(dev))
+        return t
+
+    def normalized_words(self, dev):
+        """What the lexicon metrics compare with a normalised target, on `dev` (built once, uploaded once per device): the raw words under
+        evaluation_metric._normalize_text as code-point rows (int32 [max(len(words), 1), ld]) with their lengths (int32), indexed like
+        `words`, and `row_word` as int32 [n_rows]."""
+        from .evaluation_metric import _normalize_text, _pool
+        dev = torch.device(dev)
+        t = self._norm_dev.get(dev)
+        if t is None:
+            if self._norm_host is None:
+                self._norm_host = _pool([_normalize_text(w) for w in self.words]) + (self.row_word.astype(np.int32),)
+            t = self._norm_dev[dev] = tuple(torch.from_numpy(a).to(dev) for a in self._norm_host)
+        return t
+
+
+def read_lexicon_file(path):
+    """The words of a UTF-8 file with one word per line; empty lines are skipped."""
+    with open(path, encoding="utf-8") as f:
+        return [w for w in (line.strip() for line in f) if w]
 
 
 def match_widths(pred, target, padding):
@@ -176,16 +324,22 @@ class _CTCTrainStep(_EncoderStep):
 class CTCRecModelTrain(EncoderTrain):
     """models.model_builder.CTCRecModel: `.train()` forward = (logits [B, 32, nb_classes + 1] fp32, None, None, None) with autograd,
     `.eval()` forward = the same logits from the walk without dropout; `decode(logits)` = the CTC strings as decoder-shaped rows, greedy or,
-    with `ctc_beam_width` K > 0 (args.ctc_beam_width) in eval mode, by prefix beam search of width K."""
+    with `ctc_beam_width` K > 0 (args.ctc_beam_width) in eval mode, by prefix beam search of width K, or, with `ctc_lexicon` set (a
+    `LabelLexicon` over one flat list; args.ctc_lexicon: such an object, a list of words or a word file), in eval mode the lexicon word
+    of highest likelihood for every sample."""
     _step_cls = _CTCTrainStep
     is_ctc = True
     _LAYER_NORMS = (PRE + "1.",)                        # (the head keeps PyTorch's defaults: CTCRecModel applies no init of its own)
 
-    def __init__(self, args=None, *, ctc_beam_width=None, **kw):
+    def __init__(self, args=None, *, ctc_beam_width=None, ctc_lexicon=None, **kw):
         if ctc_beam_width is None:
             ctc_beam_width = getattr(args, "ctc_beam_width", 0) or 0
         if not 0 <= int(ctc_beam_width) <= MAX_BEAM_WIDTH:
             raise ValueError(f"ctc_beam_width {ctc_beam_width}: 0 (greedy) or a prefix beam search of width 1..{MAX_BEAM_WIDTH}")
+        if ctc_lexicon is None:
+            ctc_lexicon = getattr(args, "ctc_lexicon", None) or None
+        if ctc_lexicon is not None and int(ctc_beam_width) > 0:
+            raise ValueError("ctc_lexicon with ctc_beam_width > 0: an evaluation decodes by one rule")
         super().__init__(args, **kw)
         nb_classes = self.nb_classes
         if nb_classes + 1 > CLS_PAD:
@@ -195,6 +349,17 @@ class CTCRecModelTrain(EncoderTrain):
         self.blank = nb_classes                                             # blank_label = len(classes) (metrics.py:211)
         self.eos, self.padding = nb_classes - 3, nb_classes - 2             # a vocabulary ends in EOS, PADDING, UNKNOWN (datasets.find_classes)
         self.ctc_beam_width = int(ctc_beam_width)                           # what `decode` runs in eval mode: 0 = greedy
+        if ctc_lexicon is not None and not isinstance(ctc_lexicon, LabelLexicon):
+            voc_type = getattr(args, "voc_type", None) or _VOC_BY_CLASSES.get(nb_classes)
+            if voc_type is None:
+                raise ValueError(f"ctc_lexicon: no vocabulary type has {nb_classes} classes; pass a LabelLexicon")
+            ctc_lexicon = LabelLexicon(read_lexicon_file(ctc_lexicon) if isinstance(ctc_lexicon, str) else list(ctc_lexicon), voc_type)
+        if ctc_lexicon is not None:
+            if None not in ctc_lexicon or len(ctc_lexicon) != 1:
+                raise ValueError("ctc_lexicon: a LabelLexicon over one flat list of words")
+            if ctc_lexicon.nb_classes != nb_classes:
+                raise ValueError(f"ctc_lexicon is encoded for {ctc_lexicon.nb_classes} classes ({ctc_lexicon.voc_type}), the model has {nb_classes}")
+        self.ctc_lexicon = ctc_lexicon                                      # eval-mode `decode`: the most probable word of this list
 
     def head_shapes(self):
         o = {PRE + "0.weight": (D_EMBEDDING, self.D), PRE + "0.bias": (D_EMBEDDING,), PRE + "1.weight": (D_EMBEDDING,), PRE + "1.bias": (D_EMBEDDING,)}
@@ -212,10 +377,16 @@ class CTCRecModelTrain(EncoderTrain):
         """(ids int64 [B, 33], score fp32 [B, 33], n int32 [B]) of logits [B, 32, nb_classes + 1].  beam_width 0: csrc/ctc.hip's greedy
         rule (scores: the emitting frames' probabilities); K > 0: its prefix beam search of width K (score[:, 0]: the probability of the
         string over all its alignments).  None: `ctc_beam_width` in eval mode and 0 while training (the class accuracy of the training loop
-        stays the greedy one)."""
+        stays the greedy one).  With `ctc_lexicon` set, beam_width None in eval mode is csrc/ctc.hip's lexicon decode: every sample gets
+        the word of the list with the highest likelihood (rows as the beam's; the empty row when no word can be aligned)."""
+        x = logits.detach().float().contiguous()
+        lex = getattr(self, "ctc_lexicon", None)
+        if beam_width is None and not self.training and lex is not None:
+            begin, count = lex.ranges[None]
+            _, _, ids, score, n = ctc_lexicon_decode(x, x.shape[2], self.blank, self.eos, self.padding, lex, [begin] * x.shape[0], [count] * x.shape[0])
+            return ids, score, n
         if beam_width is None:
             beam_width = 0 if self.training else self.ctc_beam_width
-        x = logits.detach().float().contiguous()
         if beam_width == 0:
             return ctc_greedy_decode(x, x.shape[2], self.blank, self.eos, self.padding)
         ids, score, _, n = ctc_beam_decode(x, x.shape[2], self.blank, self.eos, self.padding, beam_width)

@@ -20,6 +20,10 @@ lexicon of `file_names[0]` is empty -- only the first file name is looked at, an
 arg-max [B, T] of the CTC head (dig_amd/ctc_recognizer.py), collapsed by the device rule of `dig_ctc_greedy_decode` into decoder-shaped rows,
 which `dig_string_match` / `dig_tokens_to_text` then read like any other prediction; a target narrower than T + 1 is padded with PADDING.
 
+`CTCAccuracy_with_lexicon` and `CTCEditDistance_with_lexicon` are this project's own (no `factory()` keys: the reference has no such metric):
+they take the CTC head's logits and decode each image to the lexicon word of highest likelihood (`dig_ctc_lexicon_decode`, one launch per
+lexicon level) where the mirrored lexicon metrics snap a decoded string to the nearest word; they compare normalised with normalised.
+
 Two keys of the reference's factory are left out of `factory()`: `ctc_accuracy` (the function is here, as `CTCAccuracy`; the five keys are what
 the reference's fine-tune path can reach) and `multi_label_fmeasure` (no model emits multi-label outputs; not built)."""
 import string
@@ -287,6 +291,81 @@ def CTCAccuracy(output, target, dataset=None):
     ids, targ = ids.contiguous(), targ.contiguous()
     L.call("dig_string_match", L.ptr(ids), L.ptr(targ), L.ptr(canon), len(voc), voc.index("EOS"), B, T, L.ptr(match), L.stream())
     return 1.0 * int(match.sum().item()) / B                                   # (the count divided on the host, in double as the reference does)
+
+
+def _label_lexicon(dataset, attr, voc):
+    """The `LabelLexicon` of a lexicon level of `dataset` (built and cached on first use, like `_lexicon`) with, beside it, the normalised
+    raw words as a code-point pool."""
+    from .ctc_recognizer import LabelLexicon, _VOC_BY_CLASSES
+    lex = getattr(dataset, attr)
+    if not isinstance(lex, LabelLexicon):
+        cache = getattr(dataset, "_dig_label_lexicons", None)
+        if cache is None:
+            cache = {}
+            setattr(dataset, "_dig_label_lexicons", cache)
+        ent = cache.get(attr)
+        if ent is None or ent[0] is not lex:
+            voc_type = getattr(dataset, "voc_type", None) or _VOC_BY_CLASSES.get(len(voc))
+            if voc_type is None:
+                raise ValueError(f"no vocabulary type has {len(voc)} classes: give the dataset a `voc_type` or `LabelLexicon` levels")
+            ent = cache[attr] = (lex, LabelLexicon(lex, voc_type))
+        lex = ent[1]
+    return lex
+
+
+def _ctc_with_lexicon(logits, target, dataset, file_names):
+    """`_with_lexicon` for a CTC head's logits [B, T, len(voc) + 1]: per level None or the int32 [n] distances between the NORMALISED
+    chosen raw word and the normalised target, then the greedy collapse's distances [B]; all read back in one copy."""
+    from .ctc_recognizer import ctc_greedy_decode, ctc_lexicon_decode
+    voc = _voc(dataset)
+    C = len(voc) + 1
+    assert logits.dim() == 3 and logits.shape[2] == C, f"logits [B, T, {C}] (the blank is class {C - 1})"
+    x = logits.detach().float().contiguous()
+    dev = x.device
+    blank, eos, padding = C - 1, voc.index("EOS"), voc.index("PADDING")
+    pred, pred_len = tokens_to_text(ctc_greedy_decode(x, C, blank, eos, padding)[0], voc)
+    targ, targ_len = tokens_to_text(target.to(dev), voc)
+    B = x.shape[0]
+    parts = [edit_distance(pred, pred_len, targ, targ_len)]
+    n = min(len(file_names), B)
+    used = []
+    for attr in _LEVELS:
+        if len(file_names) == 0:
+            continue
+        lex = _label_lexicon(dataset, attr, voc)
+        if len(lex[file_names[0]]) == 0:
+            continue
+        rng = [lex.ranges[f] for f in file_names[:n]]
+        empty = [f for f, r in zip(file_names[:n], rng) if r[1] == 0]
+        if empty:
+            raise ValueError(f"attempt to get argmax of an empty sequence: the {attr} lexicon of {empty[0]!r} is empty")
+        best = ctc_lexicon_decode(x[:n], C, blank, eos, padding, lex, [r[0] for r in rng], [r[1] for r in rng])[0]
+        norm, norm_len, row_word = lex.normalized_words(dev)
+        word = torch.where(best >= 0, row_word[best.clamp(min=0).long()], torch.full_like(best, -1))     # (-1, no word: the empty string)
+        parts.append(edit_distance(norm, norm_len, targ[:n].contiguous(), targ_len[:n].contiguous(), a_index=word.contiguous()))
+        used.append(attr)
+    vals = torch.cat(parts).tolist()                                                                       # the one host read
+    out = {"none": vals[:B]}
+    for i, attr in enumerate(used):
+        out[attr] = vals[B + i * n:B + (i + 1) * n]
+    return out
+
+
+def CTCAccuracy_with_lexicon(logits, target, dataset=None, file_names=None):
+    """[none, lexicons50, lexicons1k, lexiconsfull] accuracies of a CTC head's `logits` [B, T, len(voc) + 1]: `none` is the greedy
+    collapse; a level decodes image i to the most probable word of the lexicon of file_names[i] (one dig_ctc_lexicon_decode launch per
+    level, casings as `LabelLexicon` adds them).  The reference has no such metric, and the comparison is this project's own: the
+    NORMALISED chosen raw word against the normalised target (the reference's lexicon functions, mirrored in `Accuracy_with_lexicon`,
+    compare the raw word, so an upper-case lexicon word is never correct there).  Its conventions are kept: a level reports 0 when
+    `file_names` is empty or the lexicon of file_names[0] is empty; an empty lexicon further down raises."""
+    d = _ctc_with_lexicon(logits, target, dataset, file_names if file_names is not None else [])
+    return [1.0 * sum(v == 0 for v in d[k]) / len(d[k]) if k in d else 0 for k in ("none",) + _LEVELS]
+
+
+def CTCEditDistance_with_lexicon(logits, target, dataset=None, file_names=None):
+    """The summed edit distances of the same decodes (see `CTCAccuracy_with_lexicon`): [none, lexicons50, lexicons1k, lexiconsfull]."""
+    d = _ctc_with_lexicon(logits, target, dataset, file_names if file_names is not None else [])
+    return [sum(d[k]) if k in d else 0 for k in ("none",) + _LEVELS]
 
 
 __factory = {

@@ -654,6 +654,38 @@ int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int 
                           int* n, hipStream_t stream);
 int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width, long long* ids,
                         float* score, float* logp, int* n, hipStream_t stream);
+/* dig_ctc_lexicon_decode: the lexicon word of highest CTC likelihood (`--ctc_lexicon`; this project's own rule, the reference only
+ * snaps a decoded string to the nearest word by edit distance, dig_lexicon_search).
+ * Inputs: logits / ld as dig_ctc_loss.  words [W][ldw] int32 class ids + word_len [W] (clamped to [0, ldw]): a pool laid out like
+ *   dig_lexicon_search's.  Sample b is scored against the pool rows [lex_begin[b], lex_begin[b] + lex_count[b]); ranges may coincide,
+ *   overlap, be disjoint or be empty; the kernel clamps them to the pool and to max_count (>= every lex_count: it sizes the grid).
+ * Scoring: s(b, w) = log p(labels_w | frames of b), the alpha recursion over the log-softmax of each frame with the arithmetic of
+ *   dig_ctc_loss (fp32 log space, re-centred every frame, the removed maxima summed in double; the frame normaliser from double
+ *   differences and a double sum, rounded to fp32 once): on the device s has the bits of -nll of dig_ctc_loss.  s = -inf when the
+ *   word has no alignment (len + adjacent equal labels > T), when it holds a label outside [0, C) or equal to `blank` (no index is
+ *   formed from such a label), or when its probability underflowed.  A word of length 0 is valid: the all-blank path.
+ * Selection: best_index[b] = the pool index of the largest s in the range, the FIRST such row on a tie; logp[b] = that s.  An empty
+ *   range, or one whose words all score -inf: best_index[b] = -1, logp[b] = -inf.
+ * Rows: ids [B][T+1] int64 = the chosen word's labels, then `eos`, then `padding`; n [B] = its length; score [B][T+1]: score[b][0] =
+ *   exp(logp[b]), every other cell 1.0 (the row shape of dig_ctc_beam_decode).  best_index -1: the empty row with score[b][0] = 0.
+ * scores (nullable) [B][max_count]: s of range position j at [b][j], -inf for j >= lex_count[b].
+ * Launches: the frames' log-softmax once per sample into the workspace ([B][T][C] fp32); one workgroup per (chunk of
+ *   DIG_CTC_LEX_CHUNK words, sample) with the sample's table in LDS, which leaves its best (s, index) pair in the workspace; one wave
+ *   per sample takes the best pair.  Pairs are distinct and totally ordered (larger s, then lower index): the result does not depend
+ *   on the cut.  No floating-point atomics: two launches on the same input give the same bits.
+ * DIG_CTC_LEX_CHUNK = 64: 4 waves carry 16 / 8 / 4 words at once (longest word of the chunk up to 15 / 31 / 63 labels), so a chunk
+ *   is 4 / 8 / 16 rounds per copy of the table.
+ * workspace: 8-byte aligned (else DIG_ERR_ALIGN), dig_ctc_lexicon_workspace_bytes(B, T, C, max_count) = B * max(1, ceil(max_count /
+ *   DIG_CTC_LEX_CHUNK)) * 8 + B * T * C * 4 bytes (0 for a non-positive B, T or C or a negative max_count); no initialisation needed.
+ * Null pointer other than scores, non-positive dimension, B < 0, ld < C, blank outside [0, C), W < 0, max_count < 0, short
+ * workspace: DIG_ERR_ARG.  Outside 1 <= T <= 64, 2 <= C <= 256, ldw <= 63, B <= 65535: DIG_ERR_UNSUPPORTED.  B == 0: DIG_OK without
+ * a launch.  max_count == 0 is legal: every sample gets -1.  A refused call writes nothing. */
+#define DIG_CTC_LEX_CHUNK 64
+long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count);
+int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, const int* words,
+                           const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count,
+                           int* best_index, float* logp, long long* ids, float* score, int* n, float* scores /* nullable */,
+                           void* workspace, long long workspace_bytes, hipStream_t stream);
 
 /* ---- dropout / stochastic depth of the fine-tune step (README.md:100-118: --drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1; the
  * recognition decoder's hard-wired dropout = 0.1, models/decoder.py:141).  Replaces nn.Dropout (modeling_finetune.py:51,83-85,271;

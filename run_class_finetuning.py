@@ -41,7 +41,8 @@ What is different, on purpose:
     head carries `beam_search`; here `evaluate` decodes by that method (said once), with its `predecessors` an integer division;
   * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`), --ctc_beam_width K
     (with --decoder_type ctc: `evaluate` decodes by CTC prefix beam search of width K <= 32, said once; 0, the default, is the greedy collapse;
-    the training loop's class accuracy stays greedy).
+    the training loop's class accuracy stays greedy), --ctc_lexicon FILE (with --decoder_type ctc: a UTF-8 file, one word per line;
+    `evaluate` decodes each image to the word of FILE with the highest CTC likelihood, said once; not together with --ctc_beam_width).
 
 Multi-rank runs are wired (samplers, FlatGradComm, the meters' all-reduce) but only the single-rank path is tested."""
 import argparse
@@ -113,6 +114,8 @@ def get_args(argv=None):
     a("--smoothing", type=float, default=0.1)
     a("--beam_width", type=int, default=0)
     a("--ctc_beam_width", type=int, default=0, help="with --decoder_type ctc: evaluate with a CTC prefix beam search of this width (1..32); 0 = greedy")
+    a("--ctc_lexicon", type=str, default=None, metavar="FILE",
+      help="with --decoder_type ctc: evaluate by decoding each image to the most probable word of FILE (UTF-8, one word per line)")
     # fine-tuning
     a("--finetune", default="", help="pre-training checkpoint to start from")
     a("--model_key", default="model|module", type=str)
@@ -211,6 +214,18 @@ def refuse_unbuilt(args):
                          "(--decoder_type ctc); the transformer decoder's beam is --beam_width")
     if not 0 <= args.ctc_beam_width <= 32:
         raise SystemExit(f"--ctc_beam_width {args.ctc_beam_width}: 0 (greedy) or a width of 1..32")
+    if args.ctc_lexicon is not None:
+        if args.decoder_type != "ctc":
+            raise SystemExit(f"--ctc_lexicon with --decoder_type {args.decoder_type}: the lexicon decode scores every word by the CTC head's frames "
+                             "(--decoder_type ctc); the other heads have no likelihood of a whole word built")
+        if args.ctc_beam_width > 0:
+            raise SystemExit("--ctc_lexicon with --ctc_beam_width: an evaluation decodes by one rule, the most probable lexicon word or the prefix "
+                             "beam search; give one of the two")
+        if not os.path.isfile(args.ctc_lexicon):
+            raise SystemExit(f"--ctc_lexicon {args.ctc_lexicon}: no such file (UTF-8, one word per line)")
+        from dig_amd.ctc_recognizer import read_lexicon_file
+        if not read_lexicon_file(args.ctc_lexicon):
+            raise SystemExit(f"--ctc_lexicon {args.ctc_lexicon}: the file holds no word (one per line; empty lines are skipped)")
     if (args.input_h, args.input_w) != (32, 128):
         raise SystemExit(f"--input_h {args.input_h} --input_w {args.input_w}: the encoders are built for 32 x 128 crops")
     paths = [args.data_path] if isinstance(args.data_path, str) else list(args.data_path)
@@ -355,6 +370,9 @@ def main(args):
         criterion = SeqCTCLoss(blank=model.blank)
         if model.ctc_beam_width > 0:
             print(f"evaluation decoder = CTC prefix beam search, width {model.ctc_beam_width} (--ctc_beam_width); the training loop's accuracy decodes greedily")
+        if model.ctc_lexicon is not None:
+            print(f"evaluation decoder = the most probable of the {len(model.ctc_lexicon.words)} words of {args.ctc_lexicon} by CTC likelihood "
+                  f"({model.ctc_lexicon.n_rows} label rows; --ctc_lexicon); the training loop's accuracy decodes greedily")
     elif args.smoothing > 0.:
         criterion = SeqLabelSmoothingCrossEntropyLoss(smoothing=args.smoothing)
         criterion.ignore_index = dataset_train.class_to_idx["PADDING"]
