@@ -219,7 +219,7 @@ int dig_decode_cross_attn(const void* q_, const void* kv_mem, void* out_, float*
                           int slots_per_mem, hipStream_t) {
   if (!q_ || !kv_mem || !out_ || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
   if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(kv_mem)) return DIG_ERR_ALIGN;
+  if (!aligned16(kv_mem) || !aligned16(q_)) return DIG_ERR_ALIGN;
   const bf16_t* q = (const bf16_t*)q_;
   const bf16_t* kv = (const bf16_t*)kv_mem;
   bf16_t* out = (bf16_t*)out_;
@@ -262,7 +262,7 @@ int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tok
     for (int c = 0; c < C; ++c) s += std::exp(row[c] - m);
     const float inv = 1.f / s;
     for (int c = 0; c < C; ++c) probs[(size_t)b * C + c] = std::exp(row[c] - m) * inv;
-    tokens[b] = am;
+    tokens[b] = am == 0x7fffffff ? 0 : am;                    // no entry above -inf: index 0, as torch.max
   }
   return DIG_OK;
 }
@@ -601,8 +601,8 @@ int dig_seq_attn_fwd_hd(const void* q_, int ldq, const void* k_, int ldk, const 
           sum += e;
           S[j] = dropping ? (drop_keep(drop->k0, drop->k1, ((unsigned)i << 16) | (unsigned)j, (unsigned)(b * heads + h), drop->thr) ? e * drop->scale : 0.f) : e;
         }
-        const float inv = 1.f / sum;
-        lse[((size_t)b * heads + h) * Lq + i] = m + std::log(sum);
+        const float inv = sum > 0.f ? 1.f / sum : 0.f;          // a fully masked row: out = 0, lse = -inf
+        lse[((size_t)b * heads + h) * Lq + i] = sum > 0.f ? m + std::log(sum) : NEG_INF;
         for (int c = 0; c < head_dim; ++c) {
           float a = 0.f;
           for (int j = 0; j < Lk; ++j) a += S[j] * bf2f(v[((size_t)b * Lk + j) * ldv + h * head_dim + c]);
@@ -628,7 +628,9 @@ int dig_seq_attn_bwd_hd(const void* q_, int ldq, const void* k_, int ldk, const 
                         const long long* lens, const dig_dropout_t* drop, int head_dim, hipStream_t) {
   if (!q_ || !k_ || !v_ || !dout_ || !lse || !dq_ || !dk_ || !dv_ || B <= 0 || heads <= 0 || Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
   if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if (256 * head_dim + Lk * (256 + 2 * head_dim) > DIG_SEQ_ATTN_BWD_LDS_LIMIT) return DIG_ERR_UNSUPPORTED;
   if ((ldk & 7) || (ldv & 7) || !aligned16(k_) || !aligned16(v_)) return DIG_ERR_ALIGN;
+  if ((lddk & 7) || (lddv & 7) || !aligned16(dk_) || !aligned16(dv_)) return DIG_ERR_ALIGN;
   const bf16_t* q = (const bf16_t*)q_; const bf16_t* k = (const bf16_t*)k_; const bf16_t* v = (const bf16_t*)v_;
   const bf16_t* dout = (const bf16_t*)dout_;
   bf16_t* dq = (bf16_t*)dq_; bf16_t* dk = (bf16_t*)dk_; bf16_t* dv = (bf16_t*)dv_;
@@ -711,7 +713,7 @@ int dig_seq_embed_bwd_lens(const long long* tokens, const void* dx_, float* demb
   for (int v = 0; v < vocab; ++v) {
     std::vector<int> list;                                             // matching rows, ascending: a fixed summation order
     for (int r = 0; r < n_tok; ++r)
-      if (tokens[r] == v && (!lens || (r % T) < lens[r / T])) list.push_back(r);
+      if (clamp_tok(tokens[r], vocab) == v && (!lens || (r % T) < lens[r / T])) list.push_back(r);
     const int n = (int)list.size();
     if (!n) continue;
     for (int c = 0; c < d; ++c) {

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void softmax_argmax_kernel(const float* __restr
   row_argmax_first(row, C, lane, m, am);
   const float inv = 1.f / row_exp_sum(row, C, lane, m);
   for (int c = lane; c < C; c += 64) probs[(size_t)b * C + c] = __expf(row[c] - m) * inv;
-  if (lane == 0) token[b] = am;
+  if (lane == 0) token[b] = am == 0x7fffffff ? 0 : am;                  // no entry above -inf: index 0, as torch.max
 }
 
 // The ranking of one beam-search step for one sample (TFDecoder.beam_search, decoder.py:283-307), the one copy both kernels below run:
@@ -263,7 +263,7 @@ extern "C" int dig_decode_cross_attn(const void* q, const void* kv_mem, void* ou
                                      int head_dim, float scale, int slots_per_mem, hipStream_t stream) {
   if (!q || !kv_mem || !out || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
   if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(kv_mem)) return DIG_ERR_ALIGN;
+  if (!aligned16(kv_mem) || !aligned16(q)) return DIG_ERR_ALIGN;           // 16-byte reads of both
   const size_t lds = (size_t)std::max(n_mem, 4 * head_dim) * sizeof(float);
   const bf16_t* qp = (const bf16_t*)q;
   const bf16_t* kv = (const bf16_t*)kv_mem;

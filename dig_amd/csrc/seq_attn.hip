@@ -7,6 +7,7 @@
 // parameter: 64 (`tf_decoder`, `small_tf_decoder`, `corres_base_tf_decoder`), 48 (`corres_small_tf_decoder`) and 24 (`corres_tiny_tf_decoder`);
 // heads are NOT padded to 64 (that would multiply the K|V projection of the memory and its bytes by up to 2.7).
 // logits = (q . k) * scale; masked logits -> probability 0; lse saved for the backward, which recomputes the probabilities.
+// A fully masked row (lens[sample] <= 0) has out = 0 and lse = -inf, and the backward gives it exact zeros: it has no allowed key.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -179,8 +180,8 @@ __global__ __launch_bounds__(256) void seq_attn_fwd_kernel(SeqAttnParams p, bf16
     }
     s = wave_sum(s);
     if (lane == 0) {
-      rowinv[i] = 1.f / s;                                              // (drop_factor already carries 1/(1-p))
-      lse[((size_t)b * gridDim.y + h) * p.Lq + i] = m + __logf(s);
+      rowinv[i] = s > 0.f ? 1.f / s : 0.f;                              // (drop_factor already carries 1/(1-p)); a fully masked row: out = 0
+      lse[((size_t)b * gridDim.y + h) * p.Lq + i] = s > 0.f ? m + __logf(s) : -INFINITY;
     }
   }
   __syncthreads();
@@ -327,7 +328,7 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_kernel(const long long* __r
   __syncthreads();
   for (int r0 = 0; r0 < n_tok; r0 += 256) {
     const int r = r0 + tid;
-    bool hit = r < n_tok && tok[r] == v;
+    bool hit = r < n_tok && clamp_class(tok[r], (int)gridDim.x) == v;         // the clamped token: the row the forward read
     if (hit && lens) hit = (r % T) < lens[r / T];
     const unsigned long long bal = __ballot(hit);
     if (lane == 0) wcount[wave] = __popcll(bal);
@@ -356,17 +357,28 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_kernel(const long long* __r
 template <int DK> size_t lds_fwd(int Lk) { return (size_t)MAXQ * DK * 4 + (size_t)MAXQ * Lk * 4 + MAXQ * 4 + (size_t)Lk * DK * 2; }
 template <int DK> size_t lds_bwd(int Lk) { return (size_t)2 * MAXQ * DK * 4 + (size_t)2 * MAXQ * Lk * 4 + (size_t)Lk * DK * 2; }
 
+// raise a kernel's dynamic LDS limit to `lds` bytes when it is above the high-water mark, which moves only when the runtime agreed
+bool grant_lds(const void* kernel, size_t lds, size_t& mark) {
+  if (lds <= mark) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  mark = lds;
+  return true;
+}
+
 template <int DK>
 int launch_fwd(const SeqAttnParams& p, void* out, int ldo, float* lse, int B, int heads, hipStream_t stream) {
   const size_t lds = lds_fwd<DK>(p.Lk);
   static size_t attr = 0;
   static size_t attr8 = 0;
   if (p.Lk <= 64) {                                                          // few keys: 8 lanes per key
-    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
+    if (!grant_lds(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, true>), lds, attr8)) return DIG_ERR_LAUNCH;
     hipLaunchKernelGGL((seq_attn_fwd_kernel<DK, true>), dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
     return dig_check_launch();
   }
-  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
+  if (!grant_lds(reinterpret_cast<const void*>(seq_attn_fwd_kernel<DK, false>), lds, attr)) return DIG_ERR_LAUNCH;
   hipLaunchKernelGGL((seq_attn_fwd_kernel<DK, false>), dim3(B, heads), dim3(256), lds, stream, p, (bf16_t*)out, ldo, lse);
   return dig_check_launch();
 }
@@ -377,13 +389,13 @@ int launch_bwd(const SeqAttnParams& p, const void* dout, int ldo, const float* l
   const size_t lds = lds_bwd<DK>(p.Lk);
   static size_t attr = 0;
   static size_t attr8 = 0;
-  if (p.Lk <= 64 && !(lddk & 7) && !(lddv & 7) && aligned16(dk) && aligned16(dv)) {   // few keys: 8 lanes per key (16-byte dK / dV stores)
-    if (lds > attr8) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr8 = lds; }
+  if (p.Lk <= 64) {                                                          // few keys: 8 lanes per key
+    if (!grant_lds(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, true>), lds, attr8)) return DIG_ERR_LAUNCH;
     hipLaunchKernelGGL((seq_attn_bwd_kernel<DK, true>), dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq,
                        (bf16_t*)dk, lddk, (bf16_t*)dv, lddv);
     return dig_check_launch();
   }
-  if (lds > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
+  if (!grant_lds(reinterpret_cast<const void*>(seq_attn_bwd_kernel<DK, false>), lds, attr)) return DIG_ERR_LAUNCH;
   hipLaunchKernelGGL((seq_attn_bwd_kernel<DK, false>), dim3(B, heads), dim3(256), lds, stream, p, (const bf16_t*)dout, ldo, lse, (bf16_t*)dq, lddq, (bf16_t*)dk,
                      lddk, (bf16_t*)dv, lddv);
   return dig_check_launch();
@@ -421,7 +433,9 @@ extern "C" int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ld
                                    hipStream_t stream) {
   if (!q || !k || !v || !dout || !lse || !dq || !dk || !dv || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
   if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if (256 * head_dim + Lk * (256 + 2 * head_dim) > DIG_SEQ_ATTN_BWD_LDS_LIMIT) return DIG_ERR_UNSUPPORTED;   // lds_bwd: Lk <= 384 / 430 / 512 at head dim 64 / 48 / 24
   if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
+  if ((lddk & 7) || (lddv & 7) || !aligned16(dk) || !aligned16(dv)) return DIG_ERR_ALIGN;   // 16-byte dK / dV row stores, on both paths
   SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
   if (head_dim == 24) return launch_bwd<24>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
   if (head_dim == 48) return launch_bwd<48>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);

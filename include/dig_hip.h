@@ -519,7 +519,9 @@ int dig_encode_labels(const int* chars, const int* offsets, const int* class_of,
  * place), dig_decode_self_attn (row t against rows 0..t), dig_decode_cross_attn (against [B, n_mem, 2*heads*head_dim] = k|v of the
  * encoder memory, projected once; `weights` optional [B, heads, n_mem] fp32), and dig_softmax_argmax on the classifier logits.
  * head_dim is 24, 48 or 64 (heads are not padded: head h sits at columns [head_dim*h, head_dim*(h+1))); any other value returns
- * DIG_ERR_UNSUPPORTED before anything is launched. */
+ * DIG_ERR_UNSUPPORTED before anything is launched.  dig_decode_cross_attn reads q and kv_mem in 16-byte pieces: either one not 16-byte
+ * aligned returns DIG_ERR_ALIGN before anything is launched; n_mem above 8192: DIG_ERR_UNSUPPORTED.  A token outside [0, vocab) reads the
+ * nearest row of the table. */
 int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_row, void* x, int B, int d, int vocab,
                      hipStream_t stream);
 int dig_decode_self_attn(const void* qkv_cache, void* out, int B, int T, int heads, int head_dim, int t, float scale,
@@ -533,6 +535,8 @@ int dig_decode_cross_attn(const void* q, const void* kv_mem, void* out, float* w
  * [B*beam_width]) and stored_scores (the un-masked top-k scores, what the final back-tracking reads). */
 int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                   long long* predecessors, float* stored_scores, hipStream_t stream);
+/* probs[b, :C] = softmax(logits[b, :C]), tokens[b] = the first index of the row's maximum (torch.max); a row with no entry above -inf
+ * returns token 0 (its probabilities are NaN, as torch.softmax gives them). */
 int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tokens, int B, int C, hipStream_t stream);
 /* Accuracy of evaluation_metric/metrics.py:19-81 on the device: rows of pred / target ([B][T] int64 class ids) are cut at `eos`;
  * canon[c] (uint8, n_classes entries) is the canonical code of class c -- 0 for classes the metric drops (UNKNOWN, anything that
@@ -583,7 +587,14 @@ int dig_seq_confidence(const float* score, const int* text_len, int B, int T, do
  * models/decoder.py:173-222): per (sample, head), Lq <= 32 queries against Lk <= 512 keys, logits = q.k * scale,
  * mask = (causal ? key <= query : 1) & (lens ? key < lens[sample] : 1).  q / k / v / out rows are (sample, position) with the
  * given leading dimensions (elements), head h at columns [head_dim*h, head_dim*(h+1)); lse: fp32 [B][heads][Lq].  These two entry
- * points are head dim 64 (dig_seq_attn_fwd_hd / _bwd_hd below with head_dim = 64 and no dropout). */
+ * points are head dim 64 (dig_seq_attn_fwd_hd / _bwd_hd below with head_dim = 64 and no dropout).
+ * A fully masked row (lens[sample] <= 0) has out = 0 and lse = -inf and contributes exactly zero to dq / dk / dv.
+ * k, v, dk, dv are read / written in 16-byte pieces: a pointer that is not 16-byte aligned or a leading dimension that is not a multiple
+ * of 8 returns DIG_ERR_ALIGN before anything is launched.
+ * The backward keeps 256*head_dim + Lk*(256 + 2*head_dim) bytes of LDS per workgroup; a shape that needs more than
+ * DIG_SEQ_ATTN_BWD_LDS_LIMIT (the 160 KiB of a CU: Lk <= 384 / 430 / 512 at head dim 64 / 48 / 24) returns DIG_ERR_UNSUPPORTED before
+ * anything is launched, on both builds.  A refused LDS size request returns DIG_ERR_LAUNCH. */
+#define DIG_SEQ_ATTN_BWD_LDS_LIMIT 163840
 int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
                      int heads, int Lq, int Lk, float scale, int causal, const long long* lens, hipStream_t stream);
 int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* dout, int ldo, const float* lse,
@@ -591,7 +602,8 @@ int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void*
                      const long long* lens, hipStream_t stream);
 /* Token embedding + positional table for whole sequences (decoder.py:173-181) and its (deterministic) gradient into the fp32
  * embedding-gradient table; gradient of SeqCrossEntropyLoss w.r.t. the logits (bf16 rows of ldd >= C columns, pad columns zero),
- * scaled by the device scalar *gscalar (null = 1). */
+ * scaled by the device scalar *gscalar (null = 1).  A token outside [0, vocab) reads the nearest row of the table, and its gradient
+ * goes to that row: the backward follows the clamped token.  n_tok above 15360: DIG_ERR_UNSUPPORTED. */
 int dig_seq_embed_fwd(const long long* tokens, const float* emb, const float* pos_table, void* x, int B, int T, int d, int vocab,
                       hipStream_t stream);
 int dig_seq_embed_bwd(const long long* tokens, const void* dx, float* demb, int n_tok, int d, int vocab, hipStream_t stream);
