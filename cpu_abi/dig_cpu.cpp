@@ -44,39 +44,15 @@ constexpr int BR = 64, N_TOK = 256, DH = 64;
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------------------------ GEMM
-int dig_gemm_effective_splits(int R, int splits) {
-  if (R <= 0 || splits < 1) return 0;
-  const int rtiles = (R + BR - 1) / BR;
-  const int per = ((rtiles + splits - 1) / splits) * BR;
-  return (R + per - 1) / per;
-}
-
 int dig_gemm_bf16_dropout(const void* A_, const void* B_, void* C_, int I, int J, int R, int lda, int ldb, int ldc, int trans_a,
                           int trans_b, int out_kind, const float* bias, const void* resid_, int ldr, void* pre_, int ldp, float alpha,
                           int alpha_cols, int act, int splits, int a_rows, int b_rows, int bk, float* colsum_partials,
                           const dig_dropout_t* drop, hipStream_t) {
-  if (!A_ || !B_ || !C_ || I <= 0 || J <= 0 || R <= 0 || splits < 1) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gemm_bf16_dropout(A_, B_, C_, I, J, R, lda, ldb, ldc, trans_a, trans_b, out_kind, bias, resid_, ldr, pre_, ldp, alpha,
+                                            alpha_cols, act, splits, a_rows, b_rows, bk, colsum_partials, drop))
+    return rc;
   const bool dropping = drop && (drop->thr || drop->pthr);
-  if (dropping) {
-    if (out_kind != 0 || trans_a || !(bk == 0 || bk == 32 || bk == 64 || ((bk == 244 || bk == 264) && !trans_b))) return DIG_ERR_UNSUPPORTED;
-    if ((size_t)I * (size_t)J >= (1ull << 32) || (drop->pthr && drop->rows_per_sample <= 0)) return DIG_ERR_ARG;
-  }
-  if (bias && !aligned16(bias)) return DIG_ERR_ALIGN;
-  if (out_kind < 0 || out_kind > 2 || act < 0 || act > 2 ||
-      (bk != 0 && bk != 32 && bk != 64 && bk != 244 && bk != 264 && bk != 212 && bk != 221 && bk != 544 && bk != 564))
-    return DIG_ERR_ARG;
-  if (act == 2 && !resid_) return DIG_ERR_ARG;
-  if (!aligned16(A_) || !aligned16(B_) || !aligned16(C_) || (lda & 7) || (ldb & 7)) return DIG_ERR_ALIGN;
-  if ((J & 7) || (ldc & 7) || (resid_ && ((ldr & 7) || !aligned16(resid_))) || (pre_ && ((ldp & 7) || !aligned16(pre_)))) return DIG_ERR_ALIGN;
-  if (!trans_a && (R % BR)) return DIG_ERR_ARG;
-  if (!trans_b && (R % BR)) return DIG_ERR_ARG;
-  if (out_kind == 2 && (bias || resid_ || act)) return DIG_ERR_ARG;
-  if (out_kind != 2 && splits != 1) return DIG_ERR_ARG;
-  if (out_kind == 2 && ldc != J) return DIG_ERR_ARG;
-  if (colsum_partials && !(act == 2 && out_kind == 0 && trans_b && !trans_a)) return DIG_ERR_UNSUPPORTED;
-  const int rtiles = (R + BR - 1) / BR;
-  const int per = ((rtiles + splits - 1) / splits) * BR;
-  if ((R + per - 1) / per != splits) return DIG_ERR_ARG;
+  const int per = (int)dig_rules::gemm_rows_per_split(R, splits);
   const bf16_t* A = (const bf16_t*)A_;
   const bf16_t* B = (const bf16_t*)B_;
   const bf16_t* resid = (const bf16_t*)resid_;
@@ -152,7 +128,7 @@ int dig_gemm_bf16(const void* A, const void* B, void* C, int I, int J, int R, in
 }
 
 int dig_reduce_partials_bf16(const float* partials, int splits, long long n, void* out_, hipStream_t) {
-  if (!partials || !out_ || splits < 1 || n <= 0 || (n & 3)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::reduce_partials_bf16(partials, splits, n, out_)) return rc;
   bf16_t* out = (bf16_t*)out_;
   for (long long e = 0; e < n; ++e) {
     float a = 0.f;
@@ -162,8 +138,7 @@ int dig_reduce_partials_bf16(const float* partials, int splits, long long n, voi
   return DIG_OK;
 }
 int dig_reduce_partials(const float* partials, int splits, long long n, float* out, int accumulate, hipStream_t) {
-  if (!partials || !out || splits < 1 || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(partials) || !aligned16(out)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::reduce_partials(partials, splits, n, out, accumulate)) return rc;
 #pragma omp parallel for
   for (long long e = 0; e < n; ++e) {
     float acc = accumulate ? out[e] : 0.f;
@@ -174,7 +149,7 @@ int dig_reduce_partials(const float* partials, int splits, long long n, float* o
 }
 
 int dig_reduce_partials_multi(const dig_reduce_seg_t* segs, int n_segs, hipStream_t stream) {
-  if (!segs || n_segs < 1 || n_segs > DIG_REDUCE_MAX_SEGS) return DIG_ERR_ARG;
+  if (int rc = dig_rules::reduce_partials_multi(segs, n_segs)) return rc;
   for (int k = 0; k < n_segs; ++k) {
     const int rc = dig_reduce_partials(segs[k].partials, segs[k].splits, segs[k].n, segs[k].out, 1, stream);
     if (rc) return rc;
@@ -183,11 +158,9 @@ int dig_reduce_partials_multi(const dig_reduce_seg_t* segs, int n_segs, hipStrea
 }
 
 int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_segs, hipStream_t) {
-  if (!segs || n_segs < 1 || n_segs > DIG_COLSUM_MAX_SEGS) return DIG_ERR_ARG;
+  if (int rc = dig_rules::colsum_partials_multi(segs, n_segs)) return rc;
   for (int k = 0; k < n_segs; ++k) {
     const dig_colsum_seg_t& g = segs[k];
-    if (!g.partials || !g.out || g.n_parts <= 0 || g.C <= 0 || (g.C & 7) || g.stride < g.C || (g.stride & 3)) return DIG_ERR_ARG;
-    if (!aligned16(g.partials)) return DIG_ERR_ALIGN;
     for (int c = 0; c < g.C; ++c) {
       float a = 0.f;
       for (int b = 0; b < g.n_parts; ++b) a += g.partials[(size_t)b * g.stride + c];
@@ -200,8 +173,7 @@ int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_segs, hipStrea
 // ------------------------------------------------------------------------------------------------------------------ attention
 int dig_attn_fwd_dropout(const void* qkv_, void* ctx_, float* lse, int n_img, int heads, int embed_dim, const dig_dropout_t* drop,
                          int q_rows, hipStream_t) {
-  if (!qkv_ || !ctx_ || !lse || n_img <= 0 || heads <= 0 || embed_dim != heads * DH || q_rows < 1 || q_rows > N_TOK) return DIG_ERR_ARG;
-  if (!aligned16(qkv_) || !aligned16(ctx_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::attn_fwd_dropout(qkv_, ctx_, lse, n_img, heads, embed_dim, drop, q_rows)) return rc;
   const bf16_t* qkv = (const bf16_t*)qkv_;
   bf16_t* ctx = (bf16_t*)ctx_;
   const int D = embed_dim, ld = 3 * D, nq = (q_rows + 31) / 32 * 32;
@@ -248,12 +220,9 @@ int dig_attn_bwd_store(int) { return 0; }   // (one store form in the CPU build)
 
 // the attention sub-block in one call (HIP: csrc/attn_block.hip): here the same three steps, one after the other.  qkv / lse null: the
 // momentum branch keeps nothing (the q | k | v rows then live in a temporary)
-int dig_attn_block_supported(int heads, int embed_dim) { return (heads == 6 && embed_dim == 384) ? 1 : 0; }
 int dig_attn_block_fwd(const void* ln1, const void* x, const void* qkv_w, const float* qkv_b, const void* proj_w, const float* proj_b,
                        void* qkv, void* ctx, float* lse, void* x_mid, int n_img, int heads, int embed_dim, float scale, hipStream_t stream) {
-  if (!ln1 || !x || !qkv_w || !proj_w || !ctx || !x_mid || n_img <= 0) return DIG_ERR_ARG;
-  if ((qkv == nullptr) != (lse == nullptr)) return DIG_ERR_ARG;
-  if (!dig_attn_block_supported(heads, embed_dim)) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::attn_block_fwd(ln1, x, qkv_w, qkv_b, proj_w, proj_b, qkv, ctx, lse, x_mid, n_img, heads, embed_dim, scale)) return rc;
   const int D = embed_dim, R = n_img * N_TOK;
   std::vector<bf16_t> tq;
   std::vector<float> tl;
@@ -272,11 +241,9 @@ int dig_attn_block_fwd(const void* ln1, const void* x, const void* qkv_w, const 
 
 int dig_attn_bwd_dropout(const void* qkv_, const void* ctx_, const void* dctx_, const float* lse, void* dqkv_, int n_img, int heads,
                          int embed_dim, float scale, float* q_colsum, float* v_colsum, const dig_dropout_t* drop, int q_rows, hipStream_t) {
-  if (!qkv_ || !ctx_ || !dctx_ || !lse || !dqkv_ || n_img <= 0 || heads <= 0 || embed_dim != heads * DH || q_rows < 1 || q_rows > N_TOK) return DIG_ERR_ARG;
+  if (int rc = dig_rules::attn_bwd_dropout(qkv_, ctx_, dctx_, lse, dqkv_, n_img, heads, embed_dim, scale, q_colsum, v_colsum, drop, q_rows))
+    return rc;
   const int nqb = (q_rows + 31) / 32;
-  if (nqb < 8 && q_colsum) return DIG_ERR_UNSUPPORTED;
-  if ((q_colsum == nullptr) != (v_colsum == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(qkv_) || !aligned16(ctx_) || !aligned16(dctx_) || !aligned16(dqkv_)) return DIG_ERR_ALIGN;
   const bf16_t* qkv = (const bf16_t*)qkv_;
   const bf16_t* ctx = (const bf16_t*)ctx_;
   const bf16_t* dctx = (const bf16_t*)dctx_;
@@ -348,8 +315,7 @@ int dig_attn_bwd(const void* qkv, const void* ctx, const void* dctx, const float
 // the projection's data gradient in front of the backward: d(ctx) = bf16(dy Wproj) with fp32 accumulation, then the plain backward
 int dig_attn_bwd_proj(const void* qkv, const void* ctx, const void* dy_, const void* projt_, const float* lse, void* dqkv, int n_img, int heads,
                       int embed_dim, float scale, float* q_colsum, float* v_colsum, hipStream_t stream) {
-  if (!qkv || !ctx || !dy_ || !projt_ || !lse || !dqkv || n_img <= 0 || heads <= 0) return DIG_ERR_ARG;
-  if (embed_dim != heads * 64 || (embed_dim & 127) || embed_dim > 512) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::attn_bwd_proj(qkv, ctx, dy_, projt_, lse, dqkv, n_img, heads, embed_dim, scale, q_colsum, v_colsum)) return rc;
   const int D = embed_dim;
   const long R = (long)n_img * N_TOK;
   const uint16_t* dy = (const uint16_t*)dy_;
@@ -371,13 +337,10 @@ int dig_attn_bwd_proj(const void* qkv, const void* ctx, const void* dy_, const v
 }
 
 // ------------------------------------------------------------------------------------------------------------------ LayerNorm
-static bool ln_dim_ok(int D) { return D == 64 || D == 128 || D == 192 || D == 256 || D == 384 || D == 512; }
 
 int dig_layernorm_fwd(const void* x_, const float* gamma, const float* beta, void* y_, float* mean, float* rstd, int rows, int D, float eps,
                       int fuse_gelu, hipStream_t) {
-  if (!x_ || !gamma || !beta || !y_ || !mean || !rstd || rows <= 0) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(y_)) return DIG_ERR_ALIGN;
-  if (!ln_dim_ok(D)) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::layernorm_fwd(x_, gamma, beta, y_, mean, rstd, rows, D, eps, fuse_gelu)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
 #pragma omp parallel for
@@ -399,21 +362,16 @@ int dig_layernorm_fwd(const void* x_, const float* gamma, const float* beta, voi
   return DIG_OK;
 }
 
-int dig_layernorm_bwd_parts(int rows) { return std::max(1, std::min(1024, (rows + 15) / 16)); }
-long long dig_layernorm_bwd_workspace_bytes(int rows, int D) { return (long long)dig_layernorm_bwd_parts(rows) * 3 * D * sizeof(float); }
 
 // the partial rows are the sums over the row slices part p owns (rows p, p + parts, ...); their total is what finalize adds
 int dig_layernorm_bwd_partials(const void* dy_, const void* x_, const float* gamma, const float* beta, const float* mean, const float* rstd,
                                const void* dres_, void* dx_, float* workspace, int rows, int D, int fuse_gelu, hipStream_t) {
-  if (!dy_ || !x_ || !gamma || !mean || !rstd || !dx_ || !workspace || rows <= 0) return DIG_ERR_ARG;
-  if (fuse_gelu && !beta) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(dx_) || (dres_ && !aligned16(dres_))) return DIG_ERR_ALIGN;
-  if (!ln_dim_ok(D)) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::layernorm_bwd_partials(dy_, x_, gamma, beta, mean, rstd, dres_, dx_, workspace, rows, D, fuse_gelu)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
   const bf16_t* dres = (const bf16_t*)dres_;
   bf16_t* dx = (bf16_t*)dx_;
-  const int parts = dig_layernorm_bwd_parts(rows);
+  const int parts = dig_rules::layernorm_bwd_parts(rows);
   std::memset(workspace, 0, (size_t)parts * 3 * D * sizeof(float));
 #pragma omp parallel for
   for (int p = 0; p < parts; ++p) {
@@ -444,8 +402,8 @@ int dig_layernorm_bwd_partials(const void* dy_, const void* x_, const float* gam
 }
 
 int dig_layernorm_bwd_finalize(const float* workspace, int rows, int D, float* dgamma, float* dbeta, float* dcolsum, hipStream_t) {
-  if (!workspace || !dgamma || !dbeta || rows <= 0 || D <= 0 || (D & 15)) return DIG_ERR_ARG;
-  const int parts = dig_layernorm_bwd_parts(rows);
+  if (int rc = dig_rules::layernorm_bwd_finalize(workspace, rows, D, dgamma, dbeta, dcolsum)) return rc;
+  const int parts = dig_rules::layernorm_bwd_parts(rows);
   for (int c = 0; c < D; ++c) {
     float a = 0.f, b = 0.f, e = 0.f;
     for (int p = 0; p < parts; ++p) {
@@ -461,7 +419,7 @@ int dig_layernorm_bwd_finalize(const float* workspace, int rows, int D, float* d
 }
 
 int dig_layernorm_bwd_finalize_parts(const float* workspace, int parts, int D, float* dgamma, float* dbeta, float* dcolsum, hipStream_t) {
-  if (!workspace || !dgamma || !dbeta || parts <= 0 || D <= 0 || (D & 15)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::layernorm_bwd_finalize_parts(workspace, parts, D, dgamma, dbeta, dcolsum)) return rc;
   for (int c = 0; c < D; ++c) {
     float a = 0.f, b = 0.f, e = 0.f;
     for (int p = 0; p < parts; ++p) {
@@ -479,7 +437,7 @@ int dig_layernorm_bwd_finalize_parts(const float* workspace, int parts, int D, f
 int dig_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean, const float* rstd,
                       const void* dres, void* dx, float* dgamma, float* dbeta, float* dcolsum, float* workspace, int rows, int D,
                       int fuse_gelu, hipStream_t stream) {
-  if (!dgamma || !dbeta || (dcolsum && !dres)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::layernorm_bwd(dy, x, gamma, beta, mean, rstd, dres, dx, dgamma, dbeta, dcolsum, workspace, rows, D, fuse_gelu)) return rc;
   const int rc = dig_layernorm_bwd_partials(dy, x, gamma, beta, mean, rstd, dres, dx, workspace, rows, D, fuse_gelu, stream);
   if (rc != DIG_OK) return rc;
   return dig_layernorm_bwd_finalize(workspace, rows, D, dgamma, dbeta, dcolsum, stream);
@@ -489,8 +447,7 @@ int dig_layernorm_bwd(const void* dy, const void* x, const float* gamma, const f
 long long dig_bn_stats_workspace_bytes(int rows, int C) { return (long long)((rows + 63) / 64) * 2 * C * sizeof(float); }
 
 int dig_bn_stats(const void* x_, float* sums, float* workspace, int rows, int C, hipStream_t) {
-  if (!x_ || !sums || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_stats(x_, sums, workspace, rows, C)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
   for (int c = 0; c < C; ++c) {
@@ -504,9 +461,8 @@ int dig_bn_stats(const void* x_, float* sums, float* workspace, int rows, int C,
 
 int dig_bn_fwd_apply(const void* x_, const float* sums, float n_total, float eps, const float* gamma, const float* beta, int relu, void* y_,
                      float* mean_out, float* rstd_out, int rows, int C, hipStream_t) {
-  if (!x_ || !sums || !y_ || !mean_out || !rstd_out || rows <= 0 || C <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
-  if ((gamma == nullptr) != (beta == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(y_) || !aligned16(sums) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_fwd_apply_running(x_, sums, n_total, eps, gamma, beta, relu, y_, mean_out, rstd_out, 0.f, nullptr, nullptr, rows, C))
+    return rc;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
   const float inv_n = 1.0f / n_total;
@@ -528,7 +484,7 @@ int dig_bn_fwd_apply(const void* x_, const float* sums, float n_total, float eps
 }
 
 int dig_bn_update_running(const float* sums, float n_total, float momentum, float* running_mean, float* running_var, int C, hipStream_t) {
-  if (!sums || !running_mean || !running_var || C <= 0 || n_total <= 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::bn_update_running(sums, n_total, momentum, running_mean, running_var, C)) return rc;
   for (int c = 0; c < C; ++c) {
     const float mu = sums[c] / n_total;
     const float var = std::max(sums[C + c] / n_total - mu * mu, 0.f);
@@ -538,15 +494,10 @@ int dig_bn_update_running(const float* sums, float n_total, float momentum, floa
   return DIG_OK;
 }
 
-int dig_bn_fused_supported(int rows, int C) { return rows >= 2 && rows <= 4096 && C >= 256 && (C % 32) == 0; }
 
 int dig_bn_fwd_fused(const void* x_, float eps, const float* gamma, const float* beta, int relu, void* y_, float* mean_out, float* rstd_out,
                      float momentum, float* running_mean, float* running_var, int rows, int C, hipStream_t) {
-  if (!x_ || !y_ || !mean_out || !rstd_out || (gamma == nullptr) != (beta == nullptr) || (running_mean == nullptr) != (running_var == nullptr))
-    return DIG_ERR_ARG;
-  if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(x_) || !aligned16(y_) || !aligned16(mean_out) || !aligned16(rstd_out) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
-      (running_mean && (!aligned16(running_mean) || !aligned16(running_var)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_fwd_fused(x_, eps, gamma, beta, relu, y_, mean_out, rstd_out, momentum, running_mean, running_var, rows, C)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
   const float n = (float)rows, inv_n = 1.0f / n;
@@ -579,11 +530,7 @@ int dig_bn_fwd_fused(const void* x_, float eps, const float* gamma, const float*
 
 int dig_bn_bwd_fused(const void* dy_, const void* x_, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                      float* dbeta_acc, float* dgamma_acc, void* dx_, int rows, int C, hipStream_t) {
-  if (!dy_ || !x_ || !mean || !rstd || !dx_ || (gamma == nullptr) != (beta == nullptr) || (dbeta_acc == nullptr) != (dgamma_acc == nullptr))
-    return DIG_ERR_ARG;
-  if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(dx_) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
-      (dbeta_acc && (!aligned16(dbeta_acc) || !aligned16(dgamma_acc)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_bwd_fused(dy_, x_, mean, rstd, gamma, beta, relu, dbeta_acc, dgamma_acc, dx_, rows, C)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* dx = (bf16_t*)dx_;
@@ -619,7 +566,9 @@ int dig_bn_bwd_fused(const void* dy_, const void* x_, const float* mean, const f
 int dig_bn_fwd_apply_running(const void* x, const float* sums, float n_total, float eps, const float* gamma, const float* beta, int relu, void* y,
                              float* mean_out, float* rstd_out, float momentum, float* running_mean, float* running_var, int rows, int C,
                              hipStream_t st) {
-  if ((running_mean == nullptr) != (running_var == nullptr) || (running_mean && n_total <= 1.f)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::bn_fwd_apply_running(x, sums, n_total, eps, gamma, beta, relu, y, mean_out, rstd_out, momentum, running_mean, running_var,
+                                               rows, C))
+    return rc;
   const int rc = dig_bn_fwd_apply(x, sums, n_total, eps, gamma, beta, relu, y, mean_out, rstd_out, rows, C, st);
   if (rc || !running_mean) return rc;
   return dig_bn_update_running(sums, n_total, momentum, running_mean, running_var, C, st);
@@ -627,8 +576,7 @@ int dig_bn_fwd_apply_running(const void* x, const float* sums, float n_total, fl
 
 int dig_bn_bwd_stats(const void* dy_, const void* x_, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                      float* sums, float* workspace, int rows, int C, hipStream_t) {
-  if (!dy_ || !x_ || !mean || !rstd || !sums || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_bwd_stats_acc(dy_, x_, mean, rstd, gamma, beta, relu, sums, nullptr, nullptr, workspace, rows, C)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
@@ -650,7 +598,7 @@ int dig_bn_bwd_stats(const void* dy_, const void* x_, const float* mean, const f
 
 int dig_bn_bwd_stats_acc(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                          float* sums, float* dbeta_acc, float* dgamma_acc, float* workspace, int rows, int C, hipStream_t st) {
-  if ((dbeta_acc == nullptr) != (dgamma_acc == nullptr)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::bn_bwd_stats_acc(dy, x, mean, rstd, gamma, beta, relu, sums, dbeta_acc, dgamma_acc, workspace, rows, C)) return rc;
   const int rc = dig_bn_bwd_stats(dy, x, mean, rstd, gamma, beta, relu, sums, workspace, rows, C, st);
   if (rc || !dbeta_acc) return rc;
   for (int c = 0; c < C; ++c) { dbeta_acc[c] += sums[c]; dgamma_acc[c] += sums[C + c]; }
@@ -659,9 +607,7 @@ int dig_bn_bwd_stats_acc(const void* dy, const void* x, const float* mean, const
 
 int dig_bn_bwd_apply(const void* dy_, const void* x_, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu,
                      const float* sums, float n_total, void* dx_, int rows, int C, hipStream_t) {
-  if (!dy_ || !x_ || !mean || !rstd || !sums || !dx_ || rows <= 0 || C <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(dy_) || !aligned16(dx_) || !aligned16(mean) || !aligned16(rstd) || !aligned16(sums) ||
-      (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_bwd_apply(dy_, x_, mean, rstd, gamma, beta, relu, sums, n_total, dx_, rows, C)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* dx = (bf16_t*)dx_;
@@ -683,7 +629,7 @@ int dig_bn_bwd_apply(const void* dy_, const void* x_, const float* mean, const f
 // ------------------------------------------------------------------------------------------------------------------ patch embedding
 int dig_patch_embed_fwd(const float* img, const float* W, const float* bias, const unsigned char* mask, const float* mask_token,
                         const float* pos, void* out_, int n_img, int gh, int gw, int D, hipStream_t) {
-  if (!img || !W || !bias || !mask_token || !pos || !out_ || n_img <= 0 || D <= 0 || D > 1024 || (D & 63)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::patch_embed_fwd(img, W, bias, mask, mask_token, pos, out_, n_img, gh, gw, D)) return rc;
   bf16_t* out = (bf16_t*)out_;
   const int ntok = gh * gw, Himg = gh * 4, Wimg = gw * 4;
 #pragma omp parallel for
@@ -706,7 +652,7 @@ int dig_patch_embed_fwd(const float* img, const float* W, const float* bias, con
 
 int dig_patch_embed_bwd(const void* dy_, const float* img, const unsigned char* mask, float* dW, float* dbias, float* dmask_token, int n_img,
                         int gh, int gw, int D, hipStream_t) {
-  if (!dy_ || !img || !dW || !dbias || !dmask_token || n_img <= 0 || D <= 0 || D > 1024 || (D & 63)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::patch_embed_bwd(dy_, img, mask, dW, dbias, dmask_token, n_img, gh, gw, D)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   const int ntok = gh * gw, Himg = gh * 4, Wimg = gw * 4;
 #pragma omp parallel for
@@ -731,8 +677,7 @@ int dig_patch_embed_bwd(const void* dy_, const float* img, const unsigned char* 
 }
 
 int dig_patchify_bf16(const float* img, const unsigned char* mask, void* out_, int n_img, int gh, int gw, hipStream_t) {
-  if (!img || !out_ || n_img <= 0) return DIG_ERR_ARG;
-  if (!aligned16(img) || !aligned16(out_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::patchify_bf16(img, mask, out_, n_img, gh, gw)) return rc;
   bf16_t* out = (bf16_t*)out_;
   const int ntok = gh * gw, Himg = gh * 4, Wimg = gw * 4;
 #pragma omp parallel for
@@ -755,8 +700,7 @@ long long dig_colsum_workspace_bytes(int rows, int C) { return (long long)((rows
 
 int dig_colsum_masked(const void* x_, const unsigned char* mask, float* out_unmasked, float* out_masked, float* workspace, int rows, int C,
                       hipStream_t) {
-  if (!x_ || !mask || !out_unmasked || !out_masked || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum_masked(x_, mask, out_unmasked, out_masked, workspace, rows, C)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
   for (int c = 0; c < C; ++c) {
@@ -775,7 +719,7 @@ static inline void pool_window(int win, int gw, int nwin, int& c_lo, int& wlen) 
 }
 
 int dig_window_pool_fwd(const void* x_, void* out, int out_is_f32, int n_img, int gh, int gw, int nwin, int D, hipStream_t) {
-  if (!x_ || !out || n_img <= 0 || nwin <= 0 || gh <= 0 || gw <= 0 || (D & 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::window_pool_fwd(x_, out, out_is_f32, n_img, gh, gw, nwin, D)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
   for (int idx = 0; idx < n_img * nwin; ++idx) {
@@ -795,7 +739,7 @@ int dig_window_pool_fwd(const void* x_, void* out, int out_is_f32, int n_img, in
 }
 
 int dig_window_pool_bwd(const void* dpool_, void* dx_, int n_img, int gh, int gw, int nwin, int D, int accumulate, hipStream_t) {
-  if (!dpool_ || !dx_ || n_img <= 0 || nwin <= 0 || gh <= 0 || gw <= 0 || (D & 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::window_pool_bwd(dpool_, dx_, n_img, gh, gw, nwin, D, accumulate)) return rc;
   const bf16_t* dpool = (const bf16_t*)dpool_;
   bf16_t* dx = (bf16_t*)dx_;
   const int ntok = gh * gw;
@@ -819,7 +763,7 @@ int dig_window_pool_bwd(const void* dpool_, void* dx_, int n_img, int gh, int gw
 
 // ------------------------------------------------------------------------------------------------------------------ ConvPatchNet data movement
 int dig_im2col3x3(const void* x_, void* col_, int n_img, int H, int W, int C, int ldc, hipStream_t) {
-  if (!x_ || !col_ || n_img <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || ldc < 9 * C || (ldc & 7)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::im2col3x3(x_, col_, n_img, H, W, C, ldc)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* col = (bf16_t*)col_;
   const long rows = (long)n_img * H * W;
@@ -839,7 +783,7 @@ int dig_im2col3x3(const void* x_, void* col_, int n_img, int H, int W, int C, in
 }
 
 int dig_conv3x3_weight_flip(const void* w_, void* wt_, int c_out, int c_in, hipStream_t) {
-  if (!w_ || !wt_ || c_out <= 0 || c_in <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::conv3x3_weight_flip(w_, wt_, c_out, c_in)) return rc;
   const bf16_t* w = (const bf16_t*)w_;
   bf16_t* wt = (bf16_t*)wt_;
   for (int co = 0; co < c_out; ++co)
@@ -849,7 +793,7 @@ int dig_conv3x3_weight_flip(const void* w_, void* wt_, int c_out, int c_in, hipS
 }
 
 int dig_maxpool2x2_fwd(const void* x_, void* y_, unsigned char* idx, int n_img, int H, int W, int C, hipStream_t) {
-  if (!x_ || !y_ || !idx || n_img <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || (C & 7)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::maxpool2x2_fwd(x_, y_, idx, n_img, H, W, C)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
   bf16_t* y = (bf16_t*)y_;
   const int Ho = H / 2, Wo = W / 2;
@@ -874,7 +818,7 @@ int dig_maxpool2x2_fwd(const void* x_, void* y_, unsigned char* idx, int n_img, 
 }
 
 int dig_maxpool2x2_bwd(const void* dy_, const unsigned char* idx, void* dx_, int n_img, int H, int W, int C, hipStream_t) {
-  if (!dy_ || !dx_ || !idx || n_img <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || (C & 7)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::maxpool2x2_bwd(dy_, idx, dx_, n_img, H, W, C)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_;
   bf16_t* dx = (bf16_t*)dx_;
   const int Ho = H / 2, Wo = W / 2;
@@ -899,19 +843,19 @@ static void mask_views_u8_host(const T* mask, unsigned char* out, int B, int V, 
 }
 extern "C" {
 int dig_mask_views_u8(const void* mask, int elem_kind, int B, int V, int N, int keep_views, unsigned char* out, hipStream_t) {
-  if (!mask || !out || B <= 0 || V <= 0 || N <= 0 || keep_views < 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mask_views_u8(mask, elem_kind, B, V, N, keep_views, out)) return rc;
   switch (elem_kind) {
     case 0: mask_views_u8_host((const unsigned char*)mask, out, B, V, N, keep_views); break;
     case 1: mask_views_u8_host((const float*)mask, out, B, V, N, keep_views); break;
     case 2: mask_views_u8_host((const double*)mask, out, B, V, N, keep_views); break;
     case 3: mask_views_u8_host((const int*)mask, out, B, V, N, keep_views); break;
     case 4: mask_views_u8_host((const long long*)mask, out, B, V, N, keep_views); break;
-    default: return DIG_ERR_UNSUPPORTED;
+    default: break;                                                        // (the rule admits kinds 0..4 only)
   }
   return DIG_OK;
 }
 int dig_mask_to_index(const unsigned char* mask, int* idx, int* count, int B, int N, int max_per_sample, hipStream_t) {
-  if (!mask || !idx || !count || B <= 0 || N <= 0 || max_per_sample <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mask_to_index(mask, idx, count, B, N, max_per_sample)) return rc;
   for (int b = 0; b < B; ++b) {
     int k = 0;
     for (int n = 0; n < N; ++n)
@@ -925,8 +869,7 @@ int dig_mask_to_index(const unsigned char* mask, int* idx, int* count, int B, in
 }
 
 int dig_gather_rows(const void* src_, const int* idx, void* dst_, int M, int M_pad, int D, hipStream_t) {
-  if (!src_ || !idx || !dst_ || M <= 0 || M_pad < M || (D & 7)) return DIG_ERR_ARG;
-  if (!aligned16(src_) || !aligned16(dst_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::gather_rows(src_, idx, dst_, M, M_pad, D)) return rc;
   const bf16_t* src = (const bf16_t*)src_;
   bf16_t* dst = (bf16_t*)dst_;
   for (int m = 0; m < M_pad; ++m) {
@@ -937,8 +880,7 @@ int dig_gather_rows(const void* src_, const int* idx, void* dst_, int M, int M_p
 }
 
 int dig_scatter_rows_add(const void* src_, const int* idx, void* dst_, int M, int D, hipStream_t) {
-  if (!src_ || !idx || !dst_ || M <= 0 || (D & 7)) return DIG_ERR_ARG;
-  if (!aligned16(src_) || !aligned16(dst_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::scatter_rows_add(src_, idx, dst_, M, D)) return rc;
   const bf16_t* src = (const bf16_t*)src_;
   bf16_t* dst = (bf16_t*)dst_;
   for (int m = 0; m < M; ++m)
@@ -947,7 +889,7 @@ int dig_scatter_rows_add(const void* src_, const int* idx, void* dst_, int M, in
 }
 
 int dig_mim_target(const float* img, const int* idx, float* target, int M, int gh, int gw, int normalize, hipStream_t) {
-  if (!img || !idx || !target || M <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mim_target(img, idx, target, M, gh, gw, normalize)) return rc;
   const int ntok = gh * gw, Himg = gh * 4, Wimg = gw * 4;
   for (int m = 0; m < M; ++m) {
     const int t = idx[m], b = t / ntok, n = t % ntok, ph = n / gw, pw = n % gw;
@@ -972,7 +914,7 @@ int dig_mse_fwd_bwd_ws(const float* pred, int ld_pred, const float* target, int 
 }
 int dig_mse_fwd_bwd(const float* pred, int ld_pred, const float* target, int M, int C, float gscale, float* loss, void* dpred_, int ld_dpred,
                     hipStream_t) {
-  if (!pred || !target || M <= 0 || C <= 0 || ld_pred < C || (dpred_ && ld_dpred < C)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mse_fwd_bwd_ws(pred, ld_pred, target, M, C, gscale, loss, dpred_, ld_dpred, nullptr)) return rc;
   bf16_t* dpred = (bf16_t*)dpred_;
   const float inv = 1.0f / ((float)M * (float)C);
   double acc = 0.0;
@@ -992,7 +934,7 @@ int dig_mse_fwd_bwd(const float* pred, int ld_pred, const float* target, int M, 
 
 // ------------------------------------------------------------------------------------------------------------------ InfoNCE
 int dig_l2norm_fwd(const float* x, float* y, float* inv_norm, int n, int C, float eps, hipStream_t) {
-  if (!x || !y || !inv_norm || n <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::l2norm_fwd(x, y, inv_norm, n, C, eps)) return rc;
   for (int r = 0; r < n; ++r) {
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += x[(size_t)r * C + c] * x[(size_t)r * C + c];
@@ -1004,7 +946,7 @@ int dig_l2norm_fwd(const float* x, float* y, float* inv_norm, int n, int C, floa
 }
 
 int dig_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, float* dx, int n, int C, hipStream_t) {
-  if (!dy || !y || !inv_norm || !dx || n <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::l2norm_bwd(dy, y, inv_norm, dx, n, C)) return rc;
   for (int r = 0; r < n; ++r) {
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += y[(size_t)r * C + c] * dy[(size_t)r * C + c];
@@ -1015,9 +957,8 @@ int dig_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, float
 
 int dig_sgemm(const float* A, const float* B, float* C, int I, int J, int R, int lda, int ldb, int ldc, int trans_b, float alpha,
               int r_splits, hipStream_t) {
-  if (!A || !B || !C || I <= 0 || J <= 0 || R <= 0 || r_splits < 1) return DIG_ERR_ARG;
+  if (int rc = dig_rules::sgemm(A, B, C, I, J, R, lda, ldb, ldc, trans_b, alpha, r_splits)) return rc;
   const int per = ((R + r_splits - 1) / r_splits + 63) / 64 * 64;
-  if ((R + per - 1) / per != r_splits) return DIG_ERR_ARG;
 #pragma omp parallel for collapse(2)
   for (int s = 0; s < r_splits; ++s)
     for (int i = 0; i < I; ++i)
@@ -1034,14 +975,14 @@ int dig_ce_rows_ws(float* logits, int n, int m, int label_offset, float gscale, 
   return dig_ce_rows(logits, n, m, label_offset, gscale, out3, st);         // (the host build sums in row order anyway)
 }
 int dig_infonce_finish(const float* stats6, float loss_scale, float acc_scale, float* contra, float* accs4, hipStream_t) {
-  if (!stats6 || !contra || !accs4) return DIG_ERR_ARG;
+  if (int rc = dig_rules::infonce_finish(stats6, loss_scale, acc_scale, contra, accs4)) return rc;
   contra[0] = (stats6[0] + stats6[3]) * loss_scale;
   for (int k = 0; k < 4; ++k) accs4[k] = stats6[(k >> 1) * 3 + 1 + (k & 1)] * acc_scale;
   return DIG_OK;
 }
 int dig_step_meters(const float* loss, const float* contra, const float* pixel, const float* accs4, const int* counts, int n_counts,
                     const float* grad_norm, float* out10, hipStream_t) {
-  if (!loss || !contra || !pixel || !accs4 || !counts || n_counts <= 0 || !out10) return DIG_ERR_ARG;
+  if (int rc = dig_rules::step_meters(loss, contra, pixel, accs4, counts, n_counts, grad_norm, out10)) return rc;
   int lo = counts[0], hi = counts[0];
   for (int i = 1; i < n_counts; ++i) { lo = std::min(lo, counts[i]); hi = std::max(hi, counts[i]); }
   out10[0] = loss[0]; out10[1] = contra[0]; out10[2] = pixel[0];
@@ -1050,7 +991,7 @@ int dig_step_meters(const float* loss, const float* contra, const float* pixel, 
   return DIG_OK;
 }
 int dig_ce_rows(float* logits, int n, int m, int label_offset, float gscale, float* out3, hipStream_t) {
-  if (!logits || !out3 || n <= 0 || m <= 0 || label_offset < 0 || label_offset + n > m) return DIG_ERR_ARG;
+  if (int rc = dig_rules::ce_rows_ws(logits, n, m, label_offset, gscale, out3, nullptr)) return rc;
   for (int i = 0; i < n; ++i) {
     float* row = logits + (size_t)i * m;
     const int label = i + label_offset;
@@ -1094,7 +1035,7 @@ static int adamw_core(float* p, const float* g, float* m, float* v, bf16_t* shad
 }
 
 int dig_adamw_bias_corrections(float beta1, float beta2, int step, float* out2) {
-  if (!out2 || step < 1) return DIG_ERR_ARG;
+  if (int rc = dig_rules::adamw_bias_corrections(beta1, beta2, step, out2)) return rc;
   out2[0] = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)step)));
   out2[1] = (float)(1.0 / std::sqrt(1.0 - std::pow((double)beta2, (double)step)));
   return DIG_OK;
@@ -1105,8 +1046,9 @@ struct AdamTrMat { long long off, dst_off; int rows, cols, tile0, pad; };
 int dig_adamw_step_tr(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n, const unsigned char* group_flags, float lr0,
                       float wd0, float lr1, float wd1, float beta1, float beta2, float eps, int step, float grad_scale, const float* finite_gate,
                       const void* mats, int n_mats, int n_tiles, void* tr_out, hipStream_t) {
-  if (!p || !g || !m || !v || !group_flags || n <= 0 || (n & 255) || step < 1 || !mats || n_mats < 1 || n_tiles < 1 || !tr_out) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_tr(p, g, m, v, bf16_shadow, n, group_flags, lr0, wd0, lr1, wd1, beta1, beta2, eps, step, grad_scale,
+                                        finite_gate, mats, n_mats, n_tiles, tr_out))
+    return rc;
   if (finite_gate && !std::isfinite(finite_gate[0])) return DIG_OK;
   float bc[2];
   dig_adamw_bias_corrections(beta1, beta2, step, bc);
@@ -1123,8 +1065,8 @@ int dig_adamw_step_tr(float* p, const float* g, float* m, float* v, void* bf16_s
 int dig_adamw_step(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n, const unsigned char* group_flags, float lr0,
                    float wd0, float lr1, float wd1, float beta1, float beta2, float eps, int step, float grad_scale, const float* finite_gate,
                    hipStream_t) {
-  if (!p || !g || !m || !v || !group_flags || n <= 0 || (n & 255) || step < 1) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step(p, g, m, v, bf16_shadow, n, group_flags, lr0, wd0, lr1, wd1, beta1, beta2, eps, step, grad_scale, finite_gate))
+    return rc;
   float bc[2];
   dig_adamw_bias_corrections(beta1, beta2, step, bc);
   return adamw_core(p, g, m, v, (bf16_t*)bf16_shadow, n, group_flags, lr0, wd0, lr1, wd1, beta1, beta2, eps, bc[0], bc[1], grad_scale, finite_gate);
@@ -1132,8 +1074,7 @@ int dig_adamw_step(float* p, const float* g, float* m, float* v, void* bf16_shad
 
 int dig_adamw_step_dev(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n, const unsigned char* group_flags,
                        const float* s6, float beta1, float beta2, float eps, float grad_scale, const float* finite_gate, hipStream_t) {
-  if (!p || !g || !m || !v || !group_flags || !s6 || n <= 0 || (n & 255)) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_dev(p, g, m, v, bf16_shadow, n, group_flags, s6, beta1, beta2, eps, grad_scale, finite_gate)) return rc;
   return adamw_core(p, g, m, v, (bf16_t*)bf16_shadow, n, group_flags, s6[0], s6[1], s6[2], s6[3], beta1, beta2, eps, s6[4], s6[5], grad_scale, finite_gate);
 }
 
@@ -1141,8 +1082,8 @@ int dig_adamw_step_dev(float* p, const float* g, float* m, float* v, void* bf16_
 int dig_adamw_step_groups(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n, const unsigned char* group_idx,
                           const float* lr_tab, const float* wd_tab, float beta1, float beta2, float eps, int step, float grad_scale,
                           const float* finite_gate, hipStream_t) {
-  if (!p || !g || !m || !v || !group_idx || !lr_tab || !wd_tab || n <= 0 || (n & 255) || step < 1) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_groups(p, g, m, v, bf16_shadow, n, group_idx, lr_tab, wd_tab, beta1, beta2, eps, step, grad_scale, finite_gate))
+    return rc;
   if (finite_gate && !std::isfinite(finite_gate[0])) return DIG_OK;
   float bc[2];
   dig_adamw_bias_corrections(beta1, beta2, step, bc);
@@ -1172,20 +1113,16 @@ static int ema_core(float* pm, const float* p, bf16_t* shadow, long long n, floa
   return DIG_OK;
 }
 int dig_ema_update(float* pm, const float* p, void* bf16_shadow, long long n, float m, hipStream_t) {
-  if (!pm || !p || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(pm) || !aligned16(p)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::ema_update(pm, p, bf16_shadow, n, m)) return rc;
   return ema_core(pm, p, (bf16_t*)bf16_shadow, n, m, (float)(1.0 - (double)m));
 }
 int dig_ema_update_dev(float* pm, const float* p, void* bf16_shadow, long long n, const float* mm, hipStream_t) {
-  if (!pm || !p || !mm || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(pm) || !aligned16(p)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::ema_update_dev(pm, p, bf16_shadow, n, mm)) return rc;
   return ema_core(pm, p, (bf16_t*)bf16_shadow, n, mm[0], mm[1]);
 }
 
-long long dig_sumsq_workspace_bytes(long long) { return 1024 * sizeof(float); }
 int dig_sumsq(const float* x, long long n, float* workspace, float* out, hipStream_t) {
-  if (!x || !workspace || !out || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::sumsq(x, n, workspace, out)) return rc;
   double acc = 0.0;
   for (long long i = 0; i < n; ++i) acc += (double)x[i] * x[i];
   out[0] = (float)acc;
@@ -1194,8 +1131,7 @@ int dig_sumsq(const float* x, long long n, float* workspace, float* out, hipStre
 
 // ------------------------------------------------------------------------------------------------------------------ helpers
 int dig_colsum(const void* x_, float* out, float* workspace, int rows, int C, int ld, hipStream_t) {
-  if (!x_ || !out || !workspace || rows <= 0 || C <= 0 || (C & 7) || (ld & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum(x_, out, workspace, rows, C, ld)) return rc;
   const bf16_t* x = (const bf16_t*)x_;
 #pragma omp parallel for
   for (int c = 0; c < C; ++c) {
@@ -1207,8 +1143,7 @@ int dig_colsum(const void* x_, float* out, float* workspace, int rows, int C, in
 }
 
 int dig_colsum_partials(const float* partials, int n_parts, int C, float* out, hipStream_t) {
-  if (!partials || !out || n_parts <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(partials)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum_partials(partials, n_parts, C, out)) return rc;
   for (int c = 0; c < C; ++c) {
     float a = 0.f;
     for (int b = 0; b < n_parts; ++b) a += partials[(size_t)b * C + c];
@@ -1219,16 +1154,9 @@ int dig_colsum_partials(const float* partials, int n_parts, int C, float* out, h
 
 // ---- fused MLP chain (include/dig_hip.h; csrc/mlp_chain.hip): the same arithmetic as plain loops -- fp32 accumulation, the hidden
 // values rounded to bf16 between the two layers, bias and residual added in fp32 before the final rounding
-int dig_mlp_chain_supported(int D, int F) { return D == 384 && F >= 128 && F % 128 == 0 && F <= 6144; }
-int dig_mlp_chain_colsum_rows(int R) { return ((R + 127) / 128) * 4; }
-
 // drop (or null): out = resid + drop_path(dropout(fc2(.) + b2)), the mask rule of dig_gemm_bf16_dropout (element index r * D + j)
 static int chain_fwd_cpu(const void* x_, const void* w1_, const float* b1, const void* w2_, const float* b2, const void* resid_, void* out_,
                          void* pre_out_, void* act_out_, int R, int D, int F, const dig_dropout_t* drop) {
-  if (!x_ || !w1_ || !w2_ || !out_ || R <= 0) return DIG_ERR_ARG;
-  if (!dig_mlp_chain_supported(D, F)) return DIG_ERR_UNSUPPORTED;
-  if ((pre_out_ == nullptr) != (act_out_ == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(x_) || !aligned16(w1_) || !aligned16(w2_) || !aligned16(out_)) return DIG_ERR_ALIGN;
   const bf16_t* x = (const bf16_t*)x_; const bf16_t* w1 = (const bf16_t*)w1_; const bf16_t* w2 = (const bf16_t*)w2_;
   const bf16_t* resid = (const bf16_t*)resid_;
   bf16_t* out = (bf16_t*)out_; bf16_t* pre_out = (bf16_t*)pre_out_; bf16_t* act_out = (bf16_t*)act_out_;
@@ -1263,6 +1191,7 @@ static int chain_fwd_cpu(const void* x_, const void* w1_, const float* b1, const
 
 int dig_mlp_chain_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* resid, void* out,
                       void* pre_out, void* act_out, int R, int D, int F, hipStream_t) {
+  if (int rc = dig_rules::mlp_chain_fwd(x, w1, b1, w2, b2, resid, out, pre_out, act_out, R, D, F)) return rc;
   return chain_fwd_cpu(x, w1, b1, w2, b2, resid, out, pre_out, act_out, R, D, F, nullptr);
 }
 
@@ -1283,13 +1212,10 @@ int dig_mlp_chain_fwd_ln_dropout(const void* x, const void* resid, const float* 
                                  float* ln_rstd, const void* w1, const float* b1, const void* w2, const float* b2, void* out, void* pre_out,
                                  void* act_out, const float* nln_g, const float* nln_b, void* nln_out, float* nln_mean, float* nln_rstd, int R, int D,
                                  int F, const dig_dropout_t* drop, hipStream_t st) {
+  if (int rc = dig_rules::mlp_chain_fwd_ln_dropout(x, resid, ln_g, ln_b, eps, ln_out, ln_mean, ln_rstd, w1, b1, w2, b2, out, pre_out, act_out, nln_g,
+                                                   nln_b, nln_out, nln_mean, nln_rstd, R, D, F, drop))
+    return rc;
   if (drop && !(drop->thr || drop->pthr)) drop = nullptr;
-  if (drop && ((drop->pthr && drop->rows_per_sample <= 0) || (size_t)R * D >= (1ull << 32))) return DIG_ERR_ARG;
-  if (!x || !w1 || !w2 || !out || R <= 0) return DIG_ERR_ARG;
-  if (!dig_mlp_chain_supported(D, F) || F > 2048) return DIG_ERR_UNSUPPORTED;
-  if ((ln_g == nullptr) != (ln_b == nullptr) || (nln_g == nullptr) != (nln_b == nullptr) || (nln_g == nullptr) != (nln_out == nullptr)) return DIG_ERR_ARG;
-  if ((ln_mean == nullptr) != (ln_rstd == nullptr) || (nln_mean == nullptr) != (nln_rstd == nullptr)) return DIG_ERR_ARG;
-  if (!ln_g && (ln_out || ln_mean)) return DIG_ERR_ARG;
   std::vector<bf16_t> tmp;
   const bf16_t* ln = (const bf16_t*)x;
   if (ln_g) {
@@ -1315,9 +1241,7 @@ int dig_mlp_chain_fwd_ln(const void* x, const void* resid, const float* ln_g, co
 
 int dig_mlp_chain_bwd(const void* dy_, const void* w2t_, const void* pre_, const void* w1t_, void* dpre_out_, void* dx_out_,
                       float* colsum_partials, int R, int D, int F, hipStream_t) {
-  if (!dy_ || !w2t_ || !pre_ || !w1t_ || !dpre_out_ || !dx_out_ || R <= 0) return DIG_ERR_ARG;
-  if (!dig_mlp_chain_supported(D, F)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(dy_) || !aligned16(w2t_) || !aligned16(pre_) || !aligned16(w1t_) || !aligned16(dpre_out_) || !aligned16(dx_out_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::mlp_chain_bwd(dy_, w2t_, pre_, w1t_, dpre_out_, dx_out_, colsum_partials, R, D, F)) return rc;
   const bf16_t* dy = (const bf16_t*)dy_; const bf16_t* w2t = (const bf16_t*)w2t_; const bf16_t* w1t = (const bf16_t*)w1t_;
   const bf16_t* pre = (const bf16_t*)pre_;
   bf16_t* dpre = (bf16_t*)dpre_out_; bf16_t* dx = (bf16_t*)dx_out_;
@@ -1346,7 +1270,7 @@ int dig_mlp_chain_bwd(const void* dy_, const void* w2t_, const void* pre_, const
     }
   }
   if (colsum_partials) {                                  // partial row p = 32-row block p (the rounded values, as the device sums them)
-    const int np = dig_mlp_chain_colsum_rows(R);
+    const int np = dig_rules::mlp_chain_colsum_rows(R);
 #pragma omp parallel for
     for (int pr = 0; pr < np; ++pr)
       for (int f = 0; f < F; ++f) {
@@ -1358,19 +1282,18 @@ int dig_mlp_chain_bwd(const void* dy_, const void* w2t_, const void* pre_, const
   return DIG_OK;
 }
 
-int dig_mlp_chain_ln_parts(int R) { return (R + 127) / 128; }
-
 // dig_mlp_chain_bwd, then norm2's backward on its result: partial row p = 128-row block p
 int dig_mlp_chain_bwd_ln(const void* dy_, const void* w2t, const void* pre, const void* w1t, void* dpre_out, const void* x_mid_,
                          const float* ln_g, const float* ln_mean, const float* ln_rstd, void* dx_mid_out, float* colsum_partials,
                          float* ln_partials, int R, int D, int F, hipStream_t stream) {
-  if (!x_mid_ || !ln_g || !ln_mean || !ln_rstd || !ln_partials || !dx_mid_out) return DIG_ERR_ARG;
-  if (!aligned16(x_mid_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::mlp_chain_bwd_ln_proj(dy_, w2t, pre, w1t, dpre_out, x_mid_, ln_g, ln_mean, ln_rstd, dx_mid_out, colsum_partials,
+                                                ln_partials, nullptr, nullptr, R, D, F))
+    return rc;
   const int rc = dig_mlp_chain_bwd(dy_, w2t, pre, w1t, dpre_out, dx_mid_out, colsum_partials, R, D, F, stream);
   if (rc != DIG_OK) return rc;
   const bf16_t* dy = (const bf16_t*)dy_; const bf16_t* x = (const bf16_t*)x_mid_;
   bf16_t* dx = (bf16_t*)dx_mid_out;
-  const int np = dig_mlp_chain_ln_parts(R);
+  const int np = dig_rules::mlp_chain_ln_parts(R);
 #pragma omp parallel for
   for (int pr = 0; pr < np; ++pr) {
     float* w = ln_partials + (size_t)pr * 3 * D;
@@ -1402,11 +1325,12 @@ int dig_mlp_chain_bwd_ln(const void* dy_, const void* w2t, const void* pre, cons
 int dig_mlp_chain_bwd_ln_proj(const void* dy, const void* w2t, const void* pre, const void* w1t, void* dpre_out, const void* x_mid,
                               const float* ln_g, const float* ln_mean, const float* ln_rstd, void* dx_mid_out, float* colsum_partials,
                               float* ln_partials, const void* projt_, void* dctx_out_, int R, int D, int F, hipStream_t stream) {
-  if ((projt_ == nullptr) != (dctx_out_ == nullptr)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mlp_chain_bwd_ln_proj(dy, w2t, pre, w1t, dpre_out, x_mid, ln_g, ln_mean, ln_rstd, dx_mid_out, colsum_partials, ln_partials,
+                                                projt_, dctx_out_, R, D, F))
+    return rc;
   const int rc = dig_mlp_chain_bwd_ln(dy, w2t, pre, w1t, dpre_out, x_mid, ln_g, ln_mean, ln_rstd, dx_mid_out, colsum_partials, ln_partials, R, D, F,
                                       stream);
   if (rc != DIG_OK || !projt_) return rc;
-  if (!aligned16(projt_) || !aligned16(dctx_out_)) return DIG_ERR_ALIGN;
   const bf16_t* dx = (const bf16_t*)dx_mid_out; const bf16_t* pt = (const bf16_t*)projt_;
   bf16_t* dc = (bf16_t*)dctx_out_;
   std::vector<float> W((size_t)D * D);
@@ -1429,7 +1353,7 @@ int dig_mlp_chain_bwd_ln_proj(const void* dy, const void* w2t, const void* pre, 
 }
 
 int dig_transpose_bf16(const void* src_, void* dst_, int rows, int cols, hipStream_t) {
-  if (!src_ || !dst_ || rows <= 0 || cols <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::transpose_bf16(src_, dst_, rows, cols)) return rc;
   const bf16_t* src = (const bf16_t*)src_; bf16_t* dst = (bf16_t*)dst_;
 #pragma omp parallel for
   for (int r = 0; r < rows; ++r)
@@ -1438,7 +1362,7 @@ int dig_transpose_bf16(const void* src_, void* dst_, int rows, int cols, hipStre
 }
 
 int dig_transpose_bf16_multi(const void* const* srcs, void* const* dsts, int count, int rows, int cols, hipStream_t st) {
-  if (!srcs || !dsts || count < 1 || count > 32 || rows <= 0 || cols <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::transpose_bf16_multi(srcs, dsts, count, rows, cols)) return rc;
   for (int k = 0; k < count; ++k) {
     const int rc = dig_transpose_bf16(srcs[k], dsts[k], rows, cols, st);
     if (rc) return rc;
@@ -1447,8 +1371,7 @@ int dig_transpose_bf16_multi(const void* const* srcs, void* const* dsts, int cou
 }
 
 int dig_gelu_bwd(const void* dact_, const void* pre_, void* dpre_, long long n, hipStream_t) {
-  if (!dact_ || !pre_ || !dpre_ || n <= 0 || (n & 7)) return DIG_ERR_ARG;
-  if (!aligned16(dact_) || !aligned16(pre_) || !aligned16(dpre_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::gelu_bwd(dact_, pre_, dpre_, n)) return rc;
   const bf16_t* dact = (const bf16_t*)dact_;
   const bf16_t* pre = (const bf16_t*)pre_;
   bf16_t* dpre = (bf16_t*)dpre_;
@@ -1458,8 +1381,7 @@ int dig_gelu_bwd(const void* dact_, const void* pre_, void* dpre_, long long n, 
 }
 
 int dig_add_bf16(const void* a_, const void* b_, void* out_, long long n, hipStream_t) {
-  if (!a_ || !b_ || !out_ || n <= 0 || (n & 7)) return DIG_ERR_ARG;
-  if (!aligned16(a_) || !aligned16(b_) || !aligned16(out_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::add_bf16(a_, b_, out_, n)) return rc;
   const bf16_t* a = (const bf16_t*)a_;
   const bf16_t* b = (const bf16_t*)b_;
   bf16_t* o = (bf16_t*)out_;
@@ -1468,21 +1390,19 @@ int dig_add_bf16(const void* a_, const void* b_, void* out_, long long n, hipStr
 }
 
 int dig_cast_f32_to_bf16(const float* x, void* y, long long n, hipStream_t) {
-  if (!x || !y || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x) || (((uintptr_t)y) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::cast_f32_to_bf16(x, y, n)) return rc;
   for (long long i = 0; i < n; ++i) ((bf16_t*)y)[i] = f2bf(x[i]);
   return DIG_OK;
 }
 
 int dig_cast_bf16_to_f32(const void* x, float* y, long long n, hipStream_t) {
-  if (!x || !y || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(y) || (((uintptr_t)x) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::cast_bf16_to_f32(x, y, n)) return rc;
   for (long long i = 0; i < n; ++i) y[i] = bf2f(((const bf16_t*)x)[i]);
   return DIG_OK;
 }
 
 int dig_pad_cast_rows(const float* src, void* dst_, int M, int C, int M_pad, int ld, hipStream_t) {
-  if (!src || !dst_ || M <= 0 || C <= 0 || M_pad < M || ld < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::pad_cast_rows(src, dst_, M, C, M_pad, ld)) return rc;
   bf16_t* dst = (bf16_t*)dst_;
   for (int r = 0; r < M_pad; ++r)
     for (int c = 0; c < ld; ++c) dst[(size_t)r * ld + c] = (r < M && c < C) ? f2bf(src[(size_t)r * C + c]) : (bf16_t)0;
@@ -1490,36 +1410,32 @@ int dig_pad_cast_rows(const float* src, void* dst_, int M, int C, int M_pad, int
 }
 
 int dig_fill_f32(float* x, long long n, float value, hipStream_t) {
-  if (!x || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::fill_f32(x, n, value)) return rc;
   std::fill(x, x + n, value);
   return DIG_OK;
 }
 
 int dig_scale_f32(float* x, long long n, float s, hipStream_t) {
-  if (!x || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::scale_f32(x, n, s)) return rc;
   for (long long i = 0; i < n; ++i) x[i] *= s;
   return DIG_OK;
 }
 
 int dig_scale_by_device_scalar(float* x, long long n, const float* scalar, float extra, hipStream_t) {
-  if (!x || !scalar || n <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::scale_by_device_scalar(x, n, scalar, extra)) return rc;
   const float s = scalar[0] * extra;
   for (long long i = 0; i < n; ++i) x[i] *= s;
   return DIG_OK;
 }
 
 int dig_axpy_f32(float* y, const float* x, long long n, float a, hipStream_t) {
-  if (!y || !x || n <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::axpy_f32(y, x, n, a)) return rc;
   for (long long i = 0; i < n; ++i) y[i] += a * x[i];
   return DIG_OK;
 }
 
 int dig_dropout_apply(const void* in_, void* out_, long long rows, int cols, const dig_dropout_t* drop, hipStream_t) {
-  if (!in_ || !out_ || !drop || rows <= 0 || cols <= 0 || (cols & 7) || rows * cols >= (1ll << 32)) return DIG_ERR_ARG;
-  if (drop->pthr && drop->rows_per_sample <= 0) return DIG_ERR_ARG;
-  if (!aligned16(in_) || !aligned16(out_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::dropout_apply(in_, out_, rows, cols, drop)) return rc;
   const bf16_t* in = (const bf16_t*)in_;
   bf16_t* out = (bf16_t*)out_;
 #pragma omp parallel for
@@ -1530,89 +1446,16 @@ int dig_dropout_apply(const void* in_, void* out_, long long rows, int cols, con
 
 // ---- grouped weight gradients (csrc/wgrad.hip): same host-side planning and the same two-call protocol (partial slabs now, their
 // sum folded into the gradients by the next call); the slab layout is this build's own ([tile][split][128][128 fn], row-major)
-int dig_wgrad_group_supported(int I, int J, int R) {
-  return (I > 0 && J > 0 && R >= 64 && I % 128 == 0 && (J % 384 == 0 || J % 256 == 0) && R % 64 == 0) ? 1 : 0;
-}
-int dig_wgrad_group_fn(int J) { return J % 384 == 0 ? 3 : (J % 256 == 0 ? 2 : 0); }
-int dig_wgrad_group_rows_per_split(int R, int splits) {
-  if (R <= 0 || splits < 1 || R % 64) return 0;
-  return ((R / 64 + splits - 1) / splits) * 64;
-}
-int dig_wgrad_group_effective_splits(int R, int splits) {
-  const int per = dig_wgrad_group_rows_per_split(R, splits);
-  return per ? (R + per - 1) / per : 0;
-}
-long long dig_wgrad_group_slab_bytes(int total_tiles, int splits, int fn, int wa) { return (long long)total_tiles * splits * 128 * wa * 128 * fn * 4; }
-int dig_wgrad_group_tiles(int I, int J, int fn, int wa) {
-  if (I <= 0 || J <= 0 || (fn != 2 && fn != 3) || (wa != 1 && wa != 2) || (I % 128) || (J % (128 * fn))) return 0;
-  return ((I + 128 * wa - 1) / (128 * wa)) * (J / (128 * fn));
-}
-int dig_wgrad_group_plan(const int* tiles_per_prob, int n_probs, int R, int max_wg, int* splits_out, unsigned* map_out, int max_out) {
-  if (!tiles_per_prob || !map_out || !splits_out || n_probs < 1 || n_probs > DIG_WGRAD_MAX_PROBS || R < 64 || (R % 64) || max_wg < 8) return DIG_ERR_ARG;
-  int tiles = 0;
-  for (int k = 0; k < n_probs; ++k) {
-    if (tiles_per_prob[k] < 1) return DIG_ERR_ARG;
-    tiles += tiles_per_prob[k];
-  }
-  if (tiles > 65535) return DIG_ERR_ARG;
-  struct Grp { int tile0, n, split; };
-  int last_eff = -1;
-  for (int want = std::max(1, std::min(max_wg / tiles, R / 64));; --want) {
-    const int S = dig_wgrad_group_effective_splits(R, want);
-    if (S == last_eff && want > 1) continue;
-    last_eff = S;
-    std::vector<Grp> groups;
-    int tile0 = 0;
-    for (int k = 0; k < n_probs; ++k) {
-      for (int s = 0; s < S; ++s) groups.push_back({tile0, tiles_per_prob[k], s});
-      tile0 += tiles_per_prob[k];
-    }
-    std::stable_sort(groups.begin(), groups.end(), [](const Grp& a, const Grp& b) { return a.n > b.n; });
-    std::vector<unsigned> bins[8];
-    for (const Grp& g : groups) {
-      int best = 0;
-      for (int x = 1; x < 8; ++x)
-        if (bins[x].size() < bins[best].size()) best = x;
-      for (int t = 0; t < g.n; ++t) bins[best].push_back((unsigned)(g.tile0 + t) | ((unsigned)g.split << 16));
-    }
-    size_t len = 0;
-    for (int x = 0; x < 8; ++x) len = std::max(len, bins[x].size());
-    if ((long long)len * 8 > max_wg && want > 1) continue;
-    if ((long long)len * 8 > max_out || S > 65535) return DIG_ERR_ARG;
-    for (size_t k = 0; k < len; ++k)
-      for (int x = 0; x < 8; ++x) map_out[k * 8 + x] = k < bins[x].size() ? bins[x][k] : 0xffffffffu;
-    *splits_out = S;
-    return (int)(len * 8);
-  }
-}
 int dig_wgrad_group(const dig_wgrad_prob_t* probs, int n_probs, const dig_wgrad_prob_t* fold_probs, int n_fold, int R, int splits,
                     const unsigned* wg_map, int n_wg, float* slabs, const float* fold_slabs, int fold_splits, int fn, int wa, hipStream_t) {
-  if (n_probs < 0 || n_probs > DIG_WGRAD_MAX_PROBS || n_fold < 0 || n_fold > DIG_WGRAD_MAX_PROBS || (n_probs == 0 && n_fold == 0)) return DIG_ERR_ARG;
-  if ((fn != 2 && fn != 3) || (wa != 1 && wa != 2)) return DIG_ERR_UNSUPPORTED;
-  if (n_wg < 1 || (n_probs > 0 && (!probs || !wg_map || !slabs || R < 64 || (R % 64) || splits < 1))) return DIG_ERR_ARG;
-  if (n_fold > 0 && (!fold_probs || !fold_slabs || fold_splits < 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::wgrad_group(probs, n_probs, fold_probs, n_fold, R, splits, wg_map, n_wg, slabs, fold_slabs, fold_splits, fn, wa)) return rc;
   const int TJ = 128 * fn, TI = 128 * wa;
-  auto check = [&](const dig_wgrad_prob_t* q, int n, bool operands, std::vector<int>& tile0) {
-    int tiles = 0;
-    for (int k = 0; k < n; ++k) {
-      if (!q[k].out || q[k].I <= 0 || q[k].J <= 0 || (q[k].I % 128) || (q[k].J % TJ)) return (int)DIG_ERR_ARG;
-      if ((q[k].ldo & 3) || !aligned16(q[k].out)) return (int)DIG_ERR_ALIGN;
-      if (operands) {
-        if (!q[k].A || !q[k].B) return (int)DIG_ERR_ARG;
-        if (!aligned16(q[k].A) || !aligned16(q[k].B) || (q[k].lda & 7) || (q[k].ldb & 7) || q[k].lda < q[k].I || q[k].ldb < q[k].J) return (int)DIG_ERR_ALIGN;
-      }
-      tile0.push_back(tiles);
-      tiles += ((q[k].I + TI - 1) / TI) * (q[k].J / TJ);
-    }
-    tile0.push_back(tiles);
-    return (int)DIG_OK;
+  auto first_tiles = [&](const dig_wgrad_prob_t* q, int n) {              // first tile of every problem, then the table's tile count
+    std::vector<int> tile0(1, 0);
+    for (int k = 0; k < n; ++k) tile0.push_back(tile0.back() + ((q[k].I + TI - 1) / TI) * (q[k].J / TJ));
+    return tile0;
   };
-  std::vector<int> t0, f0;
-  int rc = check(probs, n_probs, true, t0);
-  if (rc) return rc;
-  rc = check(fold_probs, n_fold, false, f0);
-  if (rc) return rc;
-  if (n_probs && dig_wgrad_group_effective_splits(R, splits) != splits) return DIG_ERR_ARG;
+  const std::vector<int> t0 = first_tiles(probs, n_probs), f0 = first_tiles(fold_probs, n_fold);
   const size_t SLAB = (size_t)TI * TJ;
   // fold of the previous call's slabs (split order)
   for (int k = 0; k < n_fold; ++k) {
@@ -1632,14 +1475,14 @@ int dig_wgrad_group(const dig_wgrad_prob_t* probs, int n_probs, const dig_wgrad_
     }
   }
   if (!n_probs) return DIG_OK;
-  const int per = dig_wgrad_group_rows_per_split(R, splits);
+  const int per = dig_rules::wgrad_group_rows_per_split(R, splits);
   for (int w = 0; w < n_wg; ++w) {
     const unsigned item = wg_map[w];
     if (item == 0xffffffffu) continue;
     const int tile = (int)(item & 0xffffu), split = (int)(item >> 16);
     int pi = 0;
     while (pi + 1 < n_probs && tile >= t0[pi + 1]) ++pi;
-    if (tile >= t0[n_probs] || split >= splits) return DIG_ERR_ARG;
+    if (tile >= t0[n_probs] || split >= splits) continue;                  // (an entry dig_wgrad_group_plan never writes: no slab is its)
     const dig_wgrad_prob_t& q = probs[pi];
     const bf16_t* A = (const bf16_t*)q.A;
     const bf16_t* B = (const bf16_t*)q.B;
@@ -1669,4 +1512,5 @@ int dig_probe_stop(float*, int) { return 0; }
 
 // one call per encoder block: the same sequences as the HIP build (every call here is synchronous, so the hand-over to the side stream is empty)
 #define DIG_BLOCK_HANDOVER(main, side) 0
+#include "../dig_amd/csrc/abi_queries.inc"
 #include "../dig_amd/csrc/encoder_block.inc"

@@ -12,11 +12,6 @@ namespace {
 
 constexpr long long AB_MAX_PIX = 1LL << 26;
 
-bool run_ok(const dig_abi_run* r) {
-  return r && r->geom_type >= 0 && r->geom_type <= 2 && r->noise_var >= 0 && r->mb_size >= 1 && r->mb_size <= DIG_ABI_MB_MAX &&
-         r->rescale_factor >= 0 && r->rescale_factor <= 4;
-}
-
 bool table_ok(const dig_abi_params& P, const dig_abi_run& R, long long work_bytes) {
   if (P.wh < 1 || P.ww < 1 || (long long)P.wh * P.ww > AB_MAX_PIX || P.ws_off < 0) return false;
   return P.ws_off + dig_abi::image_bytes(P.geom, P.det, P.wh, P.ww, R.rescale_factor) <= work_bytes;
@@ -28,7 +23,7 @@ extern "C" {
 
 int dig_abiaug_sample(dig_abi_params* params, long long* info, const int* heights, const int* widths, int n_img, const dig_abi_run* run,
                       unsigned long long seed, unsigned step, hipStream_t) {
-  if (!params || !info || !heights || !widths || n_img <= 0 || !run_ok(run)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_sample(params, info, heights, widths, n_img, run, seed, step)) return rc;
 #pragma omp parallel for
   for (int i = 0; i < n_img; ++i) dig_abi::sample_one(params + i, i, std::max(heights[i], 1), std::max(widths[i], 1), *run, seed, step);
   long long total = 0, mh = 0, mw = 0, cnt = 0;
@@ -46,16 +41,14 @@ int dig_abiaug_sample(dig_abi_params* params, long long* info, const int* height
 }
 
 long long dig_abiaug_workspace_bytes(int geom, int det, int wh, int ww, const dig_abi_run* run) {
-  if (!run_ok(run) || wh <= 0 || ww <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_workspace_bytes(geom, det, wh, ww, run)) return rc;
   return dig_abi::image_bytes(geom, det, wh, ww, run->rescale_factor);
 }
 
 int dig_abiaug_warp_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                        const dig_abi_params* params, const dig_abi_run* run, unsigned char* work, long long work_bytes, int max_wh, int max_ww,
                        hipStream_t) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || n_img <= 0 || max_wh <= 0 || max_ww <= 0 ||
-      work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_warp_u8(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, max_wh, max_ww)) return rc;
   if (work_bytes == 0) return DIG_OK;
 #pragma omp parallel for schedule(dynamic)
   for (int img = 0; img < n_img; ++img) {
@@ -71,9 +64,7 @@ int dig_abiaug_warp_u8(const unsigned char* packed, const long long* offsets, co
 int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                               const dig_abi_params* params, const dig_abi_run* run, unsigned char* work, long long work_bytes, int max_wh,
                               int max_ww, hipStream_t) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || n_img <= 0 || max_wh <= 0 || max_ww <= 0 ||
-      work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_deteriorate_u8(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, max_wh, max_ww)) return rc;
   if (work_bytes == 0) return DIG_OK;
   const dig_abi_run R = *run;
 #pragma omp parallel for schedule(dynamic)
@@ -117,11 +108,10 @@ int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long long* offs
 int dig_abiaug_tail(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                     const dig_abi_params* params, const dig_abi_run* run, const unsigned char* work, long long work_bytes, float* out, int out_h,
                     int out_w, float mean, float std_, int max_wh, int max_ww, hipStream_t) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || !out || n_img <= 0 || out_h <= 0 || out_w <= 0 ||
-      max_wh <= 0 || max_ww <= 0 || std_ == 0.f || work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_tail(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, out, out_h, out_w, mean, std_, max_wh,
+                                      max_ww))
+    return rc;
   const int ksh = dig_pillow::ksize_for(max_ww, out_w), ksv = dig_pillow::ksize_for(max_wh, out_h);
-  if (dig_kv::stage_b_lds_bytes(out_h, out_w, ksh, ksv) - 3 * (size_t)out_h * out_w > 160 * 1024) return DIG_ERR_UNSUPPORTED;
 #pragma omp parallel for
   for (int img = 0; img < n_img; ++img) {
     const dig_abi_params& P = params[img];

@@ -13,22 +13,20 @@ extern "C" {
 
 int dig_keyview_sample(dig_kv_params* params, const int* heights, const int* widths, int n_img, unsigned long long seed, unsigned step,
                        hipStream_t) {
-  if (!params || !heights || !widths || n_img <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::keyview_sample(params, heights, widths, n_img, seed, step)) return rc;
 #pragma omp parallel for
   for (int i = 0; i < n_img; ++i) dig_kv::sample_one(params + i, i, std::max(heights[i], 1), std::max(widths[i], 1), seed, step);
   return DIG_OK;
 }
 
 long long dig_keyview_workspace_bytes(long long packed_bytes, int n_img) {
-  if (packed_bytes <= 0 || n_img <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::keyview_workspace_bytes(packed_bytes, n_img)) return rc;
   return 2 * ((packed_bytes + 255) / 256 * 256);
 }
 
 int dig_keyview_stage_a_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                            const dig_kv_params* params, unsigned char* work, long long work_bytes, int max_h, int max_w, hipStream_t) {
-  if (!packed || !offsets || !heights || !widths || !params || !work || n_img <= 0 || max_h <= 0 || max_w <= 0 || work_bytes <= 0 ||
-      work_bytes % 512 != 0 || (long long)max_h * max_w * 3 > work_bytes / 2)
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::keyview_stage_a_u8(packed, offsets, heights, widths, n_img, params, work, work_bytes, max_h, max_w)) return rc;
   const long long half = work_bytes / 2;
   for (int L = 0; L < dig_kv::N_LAUNCH; ++L) {
 #pragma omp parallel for schedule(dynamic)
@@ -53,11 +51,8 @@ int dig_keyview_stage_a_u8(const unsigned char* packed, const long long* offsets
 
 int dig_keyview_stage_b(const unsigned char* stage_a, const long long* offsets, const int* heights, const int* widths, int n_img,
                         const dig_kv_params* params, float* out, int out_h, int out_w, float mean, float std_, int max_h, int max_w, hipStream_t) {
-  if (!stage_a || !offsets || !heights || !widths || !params || !out || n_img <= 0 || out_h <= 0 || out_w <= 0 || max_h <= 0 || max_w <= 0 ||
-      std_ == 0.f)
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::keyview_stage_b(stage_a, offsets, heights, widths, n_img, params, out, out_h, out_w, mean, std_, max_h, max_w)) return rc;
   const int ksh = dig_pillow::ksize_for(max_w, out_w), ksv = dig_pillow::ksize_for(max_h, out_h);
-  if (dig_kv::stage_b_lds_bytes(out_h, out_w, ksh, ksv) > 160 * 1024) return DIG_ERR_UNSUPPORTED;   // (the HIP build's LDS bound)
 #pragma omp parallel for
   for (int img = 0; img < n_img; ++img) {
     const dig_kv_params& P = params[img];

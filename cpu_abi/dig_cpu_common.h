@@ -1,11 +1,14 @@
 // What every file of libdig_cpu.so shares: the ABI itself (include/dig_hip.h -- its types, limits and error codes; every entry point
-// defined here is compiled against its declaration, so a definition whose argument list drifts from the header does not build) and the
-// storage helpers of the HIP build's common.h in plain C++.
+// defined here is compiled against its declaration, so a definition whose argument list drifts from the header does not build), the
+// argument rules of the ABI (dig_amd/csrc/abi_rules.h -- the very text the HIP build compiles: every entry point here opens with its
+// dig_rules:: call and holds no refusal of its own, so a refusal test that passes on this build speaks for the product) and the storage
+// helpers of the HIP build's common.h in plain C++.  The arithmetic behind the rules stays this build's own: it is the second opinion.
 #pragma once
 #include <cstdint>
 #include <cstring>
 
 #include "../include/dig_hip.h"
+#include "../dig_amd/csrc/abi_rules.h"   // aligned16 / ranges_overlap, the limits, dig_rules::NAME for every entry point
 
 typedef uint16_t bf16_t;
 
@@ -21,11 +24,6 @@ inline bf16_t f2bf(float f) {                       // round to nearest even, as
   if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)((u >> 16) | 0x40);
   u += 0x7fffu + ((u >> 16) & 1u);
   return (bf16_t)(u >> 16);
-}
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {      // [a, a + bytes) and [b, b + bytes) share a byte
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
 }
 inline unsigned drop_hash(unsigned k0, unsigned k1, unsigned a, unsigned b) {
   unsigned x = a ^ k0;

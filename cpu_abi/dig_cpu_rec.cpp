@@ -62,11 +62,7 @@ inline int clip8(int v) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-int ksize_for(int in_size, int out_size) {
-  double fs = (double)in_size / out_size;
-  if (fs < 1.0) fs = 1.0;
-  return (int)std::ceil(2.0 * fs) * 2 + 1;
-}
+using dig_rules::ksize_for;   // (the LDS rule of the resize needs the tap count too)
 
 inline unsigned philox_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
   for (int r = 0; r < 10; ++r) {
@@ -111,10 +107,9 @@ extern "C" {
 
 int dig_resize_bicubic_normalize_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                                     float* out, int out_h, int out_w, float mean, float std_, int max_h, int max_w, hipStream_t) {
-  if (!packed || !offsets || !heights || !widths || !out || n_img <= 0 || out_h <= 0 || out_w <= 0 || max_h <= 0 || max_w <= 0 || std_ == 0.f)
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::resize_bicubic_normalize_u8(packed, offsets, heights, widths, n_img, out, out_h, out_w, mean, std_, max_h, max_w))
+    return rc;
   const int ksh = ksize_for(max_w, out_w), ksv = ksize_for(max_h, out_h);
-  if (((size_t)out_w * (ksh + 2) + (size_t)out_h * (ksv + 2)) * sizeof(int) > 160 * 1024) return DIG_ERR_UNSUPPORTED;
 #pragma omp parallel for
   for (int img = 0; img < n_img; ++img) {
     const int h = heights[img], w = widths[img];
@@ -159,7 +154,7 @@ int dig_resize_bicubic_normalize_u8(const unsigned char* packed, const long long
 }
 
 int dig_random_masks(unsigned char* mask, int n_rows, int n_patches, int num_mask, unsigned long long seed, unsigned step, hipStream_t) {
-  if (!mask || n_rows <= 0 || n_patches <= 0 || n_patches > 16384 || num_mask < 0 || num_mask > n_patches) return DIG_ERR_ARG;
+  if (int rc = dig_rules::random_masks(mask, n_rows, n_patches, num_mask, seed, step)) return rc;
   const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
 #pragma omp parallel for
   for (int r = 0; r < n_rows; ++r) {
@@ -176,7 +171,7 @@ int dig_random_masks(unsigned char* mask, int n_rows, int n_patches, int num_mas
 
 // ---------------------------------------------------------------------------------------------------------------- decode (N4)
 int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_row, void* x_, int B, int d, int vocab, hipStream_t) {
-  if (!tokens || !emb || !pe_row || !x_ || B <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::decode_embed(tokens, emb, pe_row, x_, B, d, vocab)) return rc;
   bf16_t* x = (bf16_t*)x_;
   for (int b = 0; b < B; ++b) {
     const long long t = clamp_tok(tokens[b], vocab);
@@ -186,8 +181,7 @@ int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_
 }
 
 int dig_decode_self_attn(const void* qkv_cache, void* out_, int B, int T, int heads, int head_dim, int t, float scale, hipStream_t) {
-  if (!qkv_cache || !out_ || B <= 0 || heads <= 0 || t < 0 || t >= T) return DIG_ERR_ARG;
-  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::decode_self_attn(qkv_cache, out_, B, T, heads, head_dim, t, scale)) return rc;
   const bf16_t* qkv = (const bf16_t*)qkv_cache;
   bf16_t* out = (bf16_t*)out_;
   const int hk = heads * head_dim;
@@ -217,9 +211,7 @@ int dig_decode_self_attn(const void* qkv_cache, void* out_, int B, int T, int he
 
 int dig_decode_cross_attn(const void* q_, const void* kv_mem, void* out_, float* weights, int B, int n_mem, int heads, int head_dim, float scale,
                           int slots_per_mem, hipStream_t) {
-  if (!q_ || !kv_mem || !out_ || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
-  if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(kv_mem) || !aligned16(q_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::decode_cross_attn(q_, kv_mem, out_, weights, B, n_mem, heads, head_dim, scale, slots_per_mem)) return rc;
   const bf16_t* q = (const bf16_t*)q_;
   const bf16_t* kv = (const bf16_t*)kv_mem;
   bf16_t* out = (bf16_t*)out_;
@@ -251,7 +243,7 @@ int dig_decode_cross_attn(const void* q_, const void* kv_mem, void* out_, float*
 }
 
 int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tokens, int B, int C, hipStream_t) {
-  if (!logits || !probs || !tokens || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::softmax_argmax(logits, ld, probs, tokens, B, C)) return rc;
   for (int b = 0; b < B; ++b) {
     const float* row = logits + (size_t)b * ld;
     float m = NEG_INF;
@@ -264,14 +256,6 @@ int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tok
     for (int c = 0; c < C; ++c) probs[(size_t)b * C + c] = std::exp(row[c] - m) * inv;
     tokens[b] = am == 0x7fffffff ? 0 : am;                    // no entry above -inf: index 0, as torch.max
   }
-  return DIG_OK;
-}
-
-// the arguments of the ranking, as both beam entry points check them
-static int beam_check(const float* logits, int ld, const float* seq_scores, int B, int beam_width, int max_width, int C, const long long* symbols,
-                      const long long* predecessors, const float* stored_scores) {
-  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > max_width || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
   return DIG_OK;
 }
 
@@ -312,8 +296,7 @@ static void beam_rank(const float* logits, int ld, float* seq_scores, int B, int
 
 int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                   long long* predecessors, float* stored_scores, hipStream_t) {
-  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 16, C, symbols, predecessors, stored_scores);
-  if (rc != DIG_OK) return rc;
+  if (int rc = dig_rules::beam_step(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores)) return rc;
   beam_rank(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores, nullptr);
   return DIG_OK;
 }
@@ -322,11 +305,9 @@ int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int bea
 int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                           long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in, const void* sbf_in_,
                           float* s_out, void* sbf_out_, int S, const float* table, int E, void* inp_, int ld_inp, hipStream_t) {
-  if (!s_in || !sbf_in_ || !s_out || !sbf_out_ || !table || !inp_ || S <= 0 || E <= 0 || ld_inp < E) return DIG_ERR_ARG;
-  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 8, C, symbols, predecessors, stored_scores);
-  if (rc != DIG_OK) return rc;
-  const size_t rows = (size_t)B * beam_width * S;
-  if (ranges_overlap(s_in, s_out, rows * sizeof(float)) || ranges_overlap(sbf_in_, sbf_out_, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
+  if (int rc = dig_rules::attn_beam_advance(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores, force_candidates,
+                                            s_in, sbf_in_, s_out, sbf_out_, S, table, E, inp_, ld_inp))
+    return rc;
   const bf16_t* sbf_in = (const bf16_t*)sbf_in_;
   bf16_t* sbf_out = (bf16_t*)sbf_out_;
   bf16_t* inp = (bf16_t*)inp_;
@@ -342,7 +323,7 @@ int dig_attn_beam_advance(const float* logits, int ld, float* seq_scores, int B,
 // ---------------------------------------------------------------------------------------------------------------- strings (csrc/metrics.hip)
 int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos, int B, int T,
                      unsigned char* match, hipStream_t) {
-  if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::string_match(pred, target, canon, n_classes, eos, B, T, match)) return rc;
   for (int b = 0; b < B; ++b) {
     // the kept characters of both rows (cut at eos, dropped classes removed), compared as strings
     std::vector<unsigned char> ps, ts;
@@ -361,7 +342,7 @@ int dig_string_match(const long long* pred, const long long* target, const unsig
 
 int dig_char_fmeasure(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos, int B, int T,
                       double* f_per_sample, hipStream_t) {
-  if (!pred || !target || !canon || !f_per_sample || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::char_fmeasure(pred, target, canon, n_classes, eos, B, T, f_per_sample)) return rc;
   for (int b = 0; b < B; ++b) {
     unsigned long long ps = 0, ts = 0;
     for (int i = 0; i < T; ++i) {
@@ -385,7 +366,7 @@ int dig_char_fmeasure(const long long* pred, const long long* target, const unsi
 
 int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text, int* len,
                        hipStream_t) {
-  if (!tokens || !canon || !text || !len || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::tokens_to_text(tokens, canon, n_classes, eos, B, T, text, len)) return rc;
   for (int b = 0; b < B; ++b) {
     int n = 0;
     for (int i = 0; i < T && tokens[(size_t)b * T + i] != eos; ++i) {
@@ -401,9 +382,8 @@ int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int 
 // ---------------------------------------------------------------------------------------------------------------- labels (csrc/labels.hip)
 int dig_encode_labels(const int* chars, const int* offsets, const int* class_of, int eos, int padding, int unknown, int max_len, int B,
                       long long* labels, long long* lens, hipStream_t) {
-  if (!chars || !offsets || !class_of || !labels || !lens || max_len < 1 || B < 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::encode_labels(chars, offsets, class_of, eos, padding, unknown, max_len, B, labels, lens)) return rc;
   if (B == 0) return DIG_OK;
-  if ((long long)B * max_len > 0x7fffffffLL) return DIG_ERR_UNSUPPORTED;
   for (int b = 0; b < B; ++b) {
     const int begin = offsets[b], n = std::clamp(offsets[b + 1] - begin, 0, max_len - 1);
     long long* row = labels + (size_t)b * max_len;
@@ -423,9 +403,7 @@ int dig_encode_labels(const int* chars, const int* offsets, const int* class_of,
 
 int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const int* a_index, const int* b, const int* b_len, int ldb,
                       int n, int* dist, hipStream_t) {
-  if (!a || !a_len || !b || !b_len || !dist || lda <= 0 || ldb <= 0 || n <= 0 || a_rows <= 0) return DIG_ERR_ARG;
-  if (!a_index && a_rows < n) return DIG_ERR_ARG;
-  if (lda > DIG_LEV_MAX_LEN || ldb > DIG_LEV_MAX_LEN) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::edit_distance(a, a_len, lda, a_rows, a_index, b, b_len, ldb, n, dist)) return rc;
   for (int i = 0; i < n; ++i) {
     const int r = a_index ? a_index[i] : i;
     const bool have = r >= 0 && r < a_rows;
@@ -435,19 +413,13 @@ int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const
   return DIG_OK;
 }
 
-long long dig_lexicon_search_workspace_bytes(int B, int max_count) {
-  if (B <= 0 || max_count < 0) return 0;
-  return (long long)B * std::max(1LL, ((long long)max_count + DIG_LEXICON_CHUNK - 1) / DIG_LEXICON_CHUNK) * 8;
-}
 
 int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, const int* words, const int* word_len, int ldw, int W,
                        const int* lex_begin, const int* lex_count, int max_count, int* best_index, int* best_dist, void* workspace,
                        long long workspace_bytes, hipStream_t) {
-  if (!query || !query_len || !words || !word_len || !lex_begin || !lex_count || !best_index || !best_dist || !workspace) return DIG_ERR_ARG;
-  if (ldq <= 0 || ldw <= 0 || B <= 0 || W <= 0 || max_count < 0) return DIG_ERR_ARG;
-  if (ldq > DIG_LEV_MAX_LEN || ldw > DIG_LEV_MAX_LEN || B > 65535) return DIG_ERR_UNSUPPORTED;
-  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
-  if (workspace_bytes < dig_lexicon_search_workspace_bytes(B, max_count)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::lexicon_search(query, query_len, ldq, B, words, word_len, ldw, W, lex_begin, lex_count, max_count, best_index, best_dist,
+                                         workspace, workspace_bytes))
+    return rc;
   for (int q = 0; q < B; ++q) {
     const int begin = std::clamp(lex_begin[q], 0, W);
     const int count = std::clamp(lex_count[q], 0, std::min(W - begin, max_count));
@@ -464,7 +436,7 @@ int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, c
 }
 
 int dig_seq_confidence(const float* score, const int* text_len, int B, int T, double* conf, hipStream_t) {
-  if (!score || !text_len || !conf || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_confidence(score, text_len, B, T, conf)) return rc;
   for (int b = 0; b < B; ++b) {
     const int n = text_len[b] < 0 ? 0 : (text_len[b] >= T ? T : text_len[b] + 1);
     double s = 0.0;
@@ -477,7 +449,7 @@ int dig_seq_confidence(const float* score, const int* text_len, int B, int T, do
 // ---------------------------------------------------------------------------------------------------------------- sequence losses (csrc/seq_loss.hip)
 int dig_seq_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C, float* row_workspace,
                           float* loss, hipStream_t) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_cross_entropy(input, target, length, B, T, C, row_workspace, loss)) return rc;
   double total = 0.0;
   for (int row = 0; row < B * T; ++row) {
     const int b = row / T, t = row - b * T;
@@ -498,7 +470,7 @@ int dig_seq_cross_entropy(const float* input, const long long* target, const lon
 
 int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar, int B, int T,
                               int C, void* dlogits_, int ldd, hipStream_t) {
-  if (!logits || !target || !length || !dlogits_ || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_cross_entropy_bwd(logits, ld, target, length, gscalar, B, T, C, dlogits_, ldd)) return rc;
   bf16_t* dlogits = (bf16_t*)dlogits_;
   const float sc = (gscalar ? gscalar[0] : 1.f) * (1.0f / (float)B);
   for (int row = 0; row < B * T; ++row) {
@@ -517,7 +489,7 @@ int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* targ
 
 int dig_seq_ls_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C, float smoothing,
                              float* row_workspace, float* loss, hipStream_t) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0 || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_ls_cross_entropy(input, target, length, B, T, C, smoothing, row_workspace, loss)) return rc;
   const int n = B * T;
   double a = 0.0, sj = 0.0, cnt = 0.0;
   for (int row = 0; row < n; ++row) {
@@ -540,7 +512,7 @@ int dig_seq_ls_cross_entropy(const float* input, const long long* target, const 
 
 int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar, int B,
                                  int T, int C, float smoothing, void* dlogits_, int ldd, hipStream_t) {
-  if (!logits || !target || !length || !dlogits_ || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_ls_cross_entropy_bwd(logits, ld, target, length, gscalar, B, T, C, smoothing, dlogits_, ldd)) return rc;
   bf16_t* dlogits = (bf16_t*)dlogits_;
   float cnt = 0.f;
   for (int b = 0; b < B; ++b) { const long long l = length[b]; cnt += (float)(l < 0 ? 0 : (l > T ? T : l)); }
@@ -570,9 +542,8 @@ int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* t
 int dig_seq_attn_fwd_hd(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, void* out_, int ldo, float* lse, int B,
                         int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, int head_dim,
                         hipStream_t) {
-  if (!q_ || !k_ || !v_ || !out_ || !lse || B <= 0 || heads <= 0 || Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k_) || !aligned16(v_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::seq_attn_fwd_hd(q_, ldq, k_, ldk, v_, ldv, out_, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, drop, head_dim))
+    return rc;
   const bf16_t* q = (const bf16_t*)q_; const bf16_t* k = (const bf16_t*)k_; const bf16_t* v = (const bf16_t*)v_;
   bf16_t* out = (bf16_t*)out_;
   const bool dropping = drop && drop->thr;
@@ -626,11 +597,9 @@ int dig_seq_attn_fwd(const void* q, int ldq, const void* k, int ldk, const void*
 int dig_seq_attn_bwd_hd(const void* q_, int ldq, const void* k_, int ldk, const void* v_, int ldv, const void* dout_, int ldo, const float* lse,
                         void* dq_, int lddq, void* dk_, int lddk, void* dv_, int lddv, int B, int heads, int Lq, int Lk, float scale, int causal,
                         const long long* lens, const dig_dropout_t* drop, int head_dim, hipStream_t) {
-  if (!q_ || !k_ || !v_ || !dout_ || !lse || !dq_ || !dk_ || !dv_ || B <= 0 || heads <= 0 || Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
-  if (256 * head_dim + Lk * (256 + 2 * head_dim) > DIG_SEQ_ATTN_BWD_LDS_LIMIT) return DIG_ERR_UNSUPPORTED;
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k_) || !aligned16(v_)) return DIG_ERR_ALIGN;
-  if ((lddk & 7) || (lddv & 7) || !aligned16(dk_) || !aligned16(dv_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::seq_attn_bwd_hd(q_, ldq, k_, ldk, v_, ldv, dout_, ldo, lse, dq_, lddq, dk_, lddk, dv_, lddv, B, heads, Lq, Lk, scale,
+                                          causal, lens, drop, head_dim))
+    return rc;
   const bf16_t* q = (const bf16_t*)q_; const bf16_t* k = (const bf16_t*)k_; const bf16_t* v = (const bf16_t*)v_;
   const bf16_t* dout = (const bf16_t*)dout_;
   bf16_t* dq = (bf16_t*)dq_; bf16_t* dk = (bf16_t*)dk_; bf16_t* dv = (bf16_t*)dv_;
@@ -695,7 +664,7 @@ int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void*
 }
 
 int dig_seq_embed_fwd(const long long* tokens, const float* emb, const float* pos_table, void* x_, int B, int T, int d, int vocab, hipStream_t) {
-  if (!tokens || !emb || !pos_table || !x_ || B <= 0 || T <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_embed_fwd(tokens, emb, pos_table, x_, B, T, d, vocab)) return rc;
   bf16_t* x = (bf16_t*)x_;
   for (int r = 0; r < B * T; ++r) {
     const long long t = clamp_tok(tokens[r], vocab);
@@ -706,9 +675,7 @@ int dig_seq_embed_fwd(const long long* tokens, const float* emb, const float* po
 
 int dig_seq_embed_bwd_lens(const long long* tokens, const void* dx_, float* demb, int n_tok, int d, int vocab, int T, const long long* lens,
                            hipStream_t) {
-  if (!tokens || !dx_ || !demb || n_tok <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
-  if (lens && (T <= 0 || n_tok % T)) return DIG_ERR_ARG;
-  if ((size_t)n_tok * sizeof(int) > 60 * 1024) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::seq_embed_bwd_lens(tokens, dx_, demb, n_tok, d, vocab, T, lens)) return rc;
   const bf16_t* dx = (const bf16_t*)dx_;
   for (int v = 0; v < vocab; ++v) {
     std::vector<int> list;                                             // matching rows, ascending: a fixed summation order
@@ -735,9 +702,7 @@ int dig_seq_embed_bwd(const long long* tokens, const void* dx, float* demb, int 
 // (csrc/gru_attn.hip; tanh / sigmoid in libm here, the device uses exp-based forms: fp32 round-off class)
 int dig_addattn_fwd(const void* xproj_, const void* sproj_, const float* w, const void* x_, float* alpha, void* ctx_, int ldc, int B, int N, int A,
                     int X, hipStream_t) {
-  if (!xproj_ || !sproj_ || !w || !x_ || !alpha || !ctx_ || B <= 0 || N <= 0 || N > 512 || A <= 0 || A > 1024 || (A & 7) || X <= 0 || (X & 1) || (ldc & 1))
-    return DIG_ERR_ARG;
-  if (!aligned16(xproj_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_fwd(xproj_, sproj_, w, x_, alpha, ctx_, ldc, B, N, A, X)) return rc;
   const bf16_t* xproj = (const bf16_t*)xproj_; const bf16_t* sproj = (const bf16_t*)sproj_; const bf16_t* x = (const bf16_t*)x_;
   bf16_t* ctx = (bf16_t*)ctx_;
 #pragma omp parallel for
@@ -766,9 +731,7 @@ int dig_addattn_fwd(const void* xproj_, const void* sproj_, const float* w, cons
 // dig_addattn_fwd's loops for the K slots of a sample (sproj row / alpha row / context row b*K + k, tokens of sample b)
 int dig_addattn_fwd_slots(const void* xproj_, const void* sproj_, const float* w, const void* x_, float* alpha, void* ctx_, int ldc, int B, int N,
                           int A, int X, int slots, hipStream_t) {
-  if (!xproj_ || !sproj_ || !w || !x_ || !ctx_ || B <= 0 || N <= 0 || A <= 0 || X <= 0 || (X & 1) || (ldc & 1)) return DIG_ERR_ARG;
-  if (N > 512 || A > 1024 || (A & 7) || slots < 1 || slots > 8) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(xproj_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_fwd_slots(xproj_, sproj_, w, x_, alpha, ctx_, ldc, B, N, A, X, slots)) return rc;
   const bf16_t* xproj = (const bf16_t*)xproj_; const bf16_t* sproj = (const bf16_t*)sproj_; const bf16_t* x = (const bf16_t*)x_;
   bf16_t* ctx = (bf16_t*)ctx_;
   const int K = slots;
@@ -798,10 +761,7 @@ int dig_addattn_fwd_slots(const void* xproj_, const void* sproj_, const float* w
 
 int dig_addattn_bwd(const void* xproj_, const void* sproj_, const float* w, const void* x_, const float* alpha, const void* dctx_, int ldd, float* dv,
                     void* dsproj_, float* dw_acc, int B, int N, int A, int X, hipStream_t) {
-  if (!xproj_ || !sproj_ || !w || !x_ || !alpha || !dctx_ || !dv || !dsproj_ || !dw_acc || B <= 0 || N <= 0 || N > 512 || A <= 0 || A > 1024 || (A & 7) ||
-      X <= 0 || X > 1024 || (X & 7))
-    return DIG_ERR_ARG;
-  if (!aligned16(xproj_) || !aligned16(x_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_bwd(xproj_, sproj_, w, x_, alpha, dctx_, ldd, dv, dsproj_, dw_acc, B, N, A, X)) return rc;
   const bf16_t* xproj = (const bf16_t*)xproj_; const bf16_t* sproj = (const bf16_t*)sproj_; const bf16_t* x = (const bf16_t*)x_;
   const bf16_t* dctx = (const bf16_t*)dctx_;
   bf16_t* dsproj = (bf16_t*)dsproj_;
@@ -833,10 +793,7 @@ int dig_addattn_bwd(const void* xproj_, const void* sproj_, const float* w, cons
 
 int dig_addattn_bwd_tokens(const void* xproj_, const void* sproj_all_, const float* w, const float* dv_all, const float* alpha_all,
                            const void* dctx_all_, int ldd, void* dxproj_, void* dx_, int T, int B, int N, int A, int X, hipStream_t) {
-  if (!xproj_ || !sproj_all_ || !w || !dv_all || !alpha_all || !dctx_all_ || !dxproj_ || !dx_ || T <= 0 || B <= 0 || N <= 0 || A <= 0 || (A & 1) || X <= 0 ||
-      (X & 1))
-    return DIG_ERR_ARG;
-  if (((size_t)T * A + (size_t)T * 64) * 4 > 150 * 1024 || ((size_t)T * X + (size_t)T * 64) * 4 > 150 * 1024) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::addattn_bwd_tokens(xproj_, sproj_all_, w, dv_all, alpha_all, dctx_all_, ldd, dxproj_, dx_, T, B, N, A, X)) return rc;
   const bf16_t* xproj = (const bf16_t*)xproj_; const bf16_t* sproj_all = (const bf16_t*)sproj_all_; const bf16_t* dctx_all = (const bf16_t*)dctx_all_;
   bf16_t* dxproj = (bf16_t*)dxproj_; bf16_t* dx = (bf16_t*)dx_;
 #pragma omp parallel for collapse(2)
@@ -861,7 +818,7 @@ int dig_addattn_bwd_tokens(const void* xproj_, const void* sproj_all_, const flo
 }
 
 int dig_gru_cell_fwd(const void* gi_, const void* gh_, const float* s_prev, float* s, void* s_bf16, float* gates, int B, int S, hipStream_t) {
-  if (!gi_ || !gh_ || !s || !s_bf16 || !gates || B <= 0 || S <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gru_cell_fwd(gi_, gh_, s_prev, s, s_bf16, gates, B, S)) return rc;
   const bf16_t* gi = (const bf16_t*)gi_; const bf16_t* gh = (const bf16_t*)gh_;
   bf16_t* sb = (bf16_t*)s_bf16;
   auto sig = [](float x) { return 1.f / (1.f + std::exp(-x)); };
@@ -884,7 +841,7 @@ int dig_gru_cell_fwd(const void* gi_, const void* gh_, const float* s_prev, floa
 
 int dig_gru_cell_bwd(const float* ds_a, const float* ds_b, const float* ds_c, const float* ds_d, const float* gates, const float* s_prev, void* dgi_,
                      void* dgh_, float* ds_prev, int B, int S, hipStream_t) {
-  if (!ds_a || !gates || !dgi_ || !dgh_ || !ds_prev || B <= 0 || S <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gru_cell_bwd(ds_a, ds_b, ds_c, ds_d, gates, s_prev, dgi_, dgh_, ds_prev, B, S)) return rc;
   bf16_t* dgi = (bf16_t*)dgi_; bf16_t* dgh = (bf16_t*)dgh_;
   for (int i = 0; i < B * S; ++i) {
     const int b = i / S, k = i - b * S;
@@ -908,7 +865,7 @@ int dig_gru_cell_bwd(const float* ds_a, const float* ds_b, const float* ds_c, co
 }
 
 int dig_embed_rows(const long long* tokens, const float* table, void* out_, int ld, int rows, int cols, int vocab, hipStream_t) {
-  if (!tokens || !table || !out_ || rows <= 0 || cols <= 0 || vocab <= 0 || ld < cols) return DIG_ERR_ARG;
+  if (int rc = dig_rules::embed_rows(tokens, table, out_, ld, rows, cols, vocab)) return rc;
   bf16_t* out = (bf16_t*)out_;
   for (int r = 0; r < rows; ++r) {
     const long long t = clamp_tok(tokens[r], vocab);
@@ -920,11 +877,6 @@ int dig_embed_rows(const long long* tokens, const float* table, void* out_, int 
 // ---------------------------------------------------------------------------------------------------------------- CTC head (csrc/ctc.hip)
 // The textbook recursions over the 2n + 1 states of the extended label sequence, in double and in log space (the device works in fp32
 // re-centred every step: fp32 round-off class).
-static int ctc_check(const void* logits, int ld, const void* target, int ldt, const void* target_len, int B, int T, int C, int blank) {
-  if (!logits || !target || !target_len || B < 0 || T <= 0 || C <= 0 || ldt <= 0 || ld < C || blank < 0 || blank >= C) return DIG_ERR_ARG;
-  if (T > 64 || C < 2 || C > 256 || ldt > 63) return DIG_ERR_UNSUPPORTED;
-  return DIG_OK;
-}
 
 static double ctc_lse(double a, double b) {
   const double m = std::max(a, b);
@@ -973,9 +925,8 @@ static bool ctc_forward(const float* x, int ld, const long long* tgt, long long 
 
 int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
                  int C, int blank, float* nll, float* loss, hipStream_t) {
-  if (!nll || !loss) return DIG_ERR_ARG;
-  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
-  if (rc != DIG_OK || B == 0) return rc;
+  if (int rc = dig_rules::ctc_loss(logits, ld, target, ldt, target_len, len_offset, B, T, C, blank, nll, loss)) return rc;
+  if (B == 0) return DIG_OK;
   std::vector<int> ext;
   std::vector<double> lp, alpha;
   double total = 0.0;
@@ -992,9 +943,9 @@ int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, 
 
 int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset,
                      const float* gscalar, int B, int T, int C, int blank, void* dlogits, int ldd, int dlogits_is_f32, hipStream_t) {
-  if (!dlogits || ldd < C) return DIG_ERR_ARG;
-  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
-  if (rc != DIG_OK || B == 0) return rc;
+  if (int rc = dig_rules::ctc_loss_bwd(logits, ld, target, ldt, target_len, len_offset, gscalar, B, T, C, blank, dlogits, ldd, dlogits_is_f32)) return
+      rc;
+  if (B == 0) return DIG_OK;
   const double NINF = -std::numeric_limits<double>::infinity();
   const float sc = (gscalar ? gscalar[0] : 1.f) * (1.0f / (float)B);
   std::vector<int> ext;
@@ -1036,8 +987,7 @@ int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int l
 
 int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids, float* score,
                           int* n, hipStream_t) {
-  if (!logits || !ids || !score || !n || B < 0 || T <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (T > 64 || C < 2 || C > 256) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_greedy_decode(logits, ld, B, T, C, blank, eos, padding, ids, score, n)) return rc;
   for (int b = 0; b < B; ++b) {
     long long* idr = ids + (size_t)b * (T + 1);
     float* scr = score + (size_t)b * (T + 1);
@@ -1062,8 +1012,7 @@ int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int 
 // bytes to its row; rows in creation order), double recursions, a stable sort by tot for the selection.
 int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width, long long* ids,
                         float* score, float* logp, int* n, hipStream_t) {
-  if (!logits || !ids || !score || !logp || !n || B < 0 || T <= 0 || C <= 0 || ld < C || blank < 0 || blank >= C || beam_width <= 0) return DIG_ERR_ARG;
-  if (T > 64 || C < 2 || C > 256 || beam_width > 32) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_beam_decode(logits, ld, B, T, C, blank, eos, padding, beam_width, ids, score, logp, n)) return rc;
   const double NINF = -std::numeric_limits<double>::infinity();
   struct Hyp { std::string p; double lb, ln, tot; };
   std::vector<double> lp(C);
@@ -1165,23 +1114,16 @@ static float ctc_lex_word_score(const float* lp, int T, int C, int blank, const 
   return (tail > NINF && logp == logp && logp > -1e300) ? (float)logp : NINF;
 }
 
-static long long ctc_lex_chunks(int max_count) { return ((long long)max_count + DIG_CTC_LEX_CHUNK - 1) / DIG_CTC_LEX_CHUNK; }
-
-long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count) {
-  if (B <= 0 || T <= 0 || C <= 0 || max_count < 0) return 0;
-  return (long long)B * std::max(1LL, ctc_lex_chunks(max_count)) * 8 + (long long)B * T * C * 4;
-}
+using dig_rules::ctc_lex_chunks;
 
 int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, const int* words,
                            const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count, int* best_index,
                            float* logp, long long* ids, float* score, int* n, float* scores, void* workspace, long long workspace_bytes,
                            hipStream_t) {
-  if (!logits || !words || !word_len || !lex_begin || !lex_count || !best_index || !logp || !ids || !score || !n || !workspace) return DIG_ERR_ARG;
-  if (B < 0 || T <= 0 || C <= 0 || ldw <= 0 || ld < C || blank < 0 || blank >= C || W < 0 || max_count < 0) return DIG_ERR_ARG;
-  if (T > 64 || C < 2 || C > 256 || ldw > 63 || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_lexicon_decode(logits, ld, B, T, C, blank, eos, padding, words, word_len, ldw, W, lex_begin, lex_count, max_count,
+                                             best_index, logp, ids, score, n, scores, workspace, workspace_bytes))
+    return rc;
   if (B == 0) return DIG_OK;
-  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
-  if (workspace_bytes < dig_ctc_lexicon_workspace_bytes(B, T, C, max_count)) return DIG_ERR_ARG;
   const float NINF = -std::numeric_limits<float>::infinity();
   std::vector<float> lp((size_t)T * C);
   for (int b = 0; b < B; ++b) {

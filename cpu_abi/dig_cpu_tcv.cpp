@@ -16,14 +16,6 @@ inline float keep(const dig_dropout_t* d, int t, int k, int sh) {
   return drop_hash(d->k0, d->k1, ((unsigned)t << 16) | (unsigned)k, (unsigned)sh) >= d->thr ? d->scale : 0.f;
 }
 
-int check(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, int S, int Lq, int N, int heads,
-          int d, int spm) {
-  if (!film || !u || !vk || !mem || !lnc_g || !lnc_b || S <= 0 || Lq <= 0 || N <= 0 || spm <= 0 || S % spm) return DIG_ERR_ARG;
-  if ((d != 128 && d != 384 && d != 512) || heads != d / 64 || N > 256 || Lq > 32) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(film) || !aligned16(u) || !aligned16(vk) || !aligned16(mem)) return DIG_ERR_ALIGN;
-  return DIG_OK;
-}
-
 struct Row {                                        // one query row: tanh(gamma), tanh(beta)
   std::vector<float> g, b;
   Row(const bf16_t* film, int d) : g(d), b(d) {
@@ -53,10 +45,7 @@ extern "C" {
 int dig_tcv_attn_fwd(const void* film_, const void* u_, const void* vk_, const void* mem_, const float* lnc_g, const float* lnc_b, float eps,
                      void* c_, float* lse, float* wmean, int S, int Lq, int N, int heads, int d, int slots_per_mem, const dig_dropout_t* drop,
                      hipStream_t) {
-  if (!c_ || !lse) return DIG_ERR_ARG;
-  const int rc = check(film_, u_, vk_, mem_, lnc_g, lnc_b, S, Lq, N, heads, d, slots_per_mem);
-  if (rc) return rc;
-  if (!aligned16(c_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::tcv_attn_fwd(film_, u_, vk_, mem_, lnc_g, lnc_b, eps, c_, lse, wmean, S, Lq, N, heads, d, slots_per_mem, drop)) return rc;
   const bf16_t* film = (const bf16_t*)film_; const bf16_t* u = (const bf16_t*)u_; const bf16_t* vk = (const bf16_t*)vk_;
   const bf16_t* mem = (const bf16_t*)mem_;
   bf16_t* c = (bf16_t*)c_;
@@ -101,11 +90,9 @@ int dig_tcv_attn_bwd(const void* film_, const void* u_, const void* vk_, const v
                      const void* c_, const float* lse, const void* dc_, void* du_, void* dfilm_, void* dvk_, void* dmem_, float* dlnc_g,
                      float* dlnc_b, float* workspace, int S, int Lq, int N, int heads, int d, int slots_per_mem, const dig_dropout_t* drop,
                      hipStream_t) {
-  if (!c_ || !lse || !dc_ || !du_ || !dfilm_ || !dvk_ || !dmem_ || !dlnc_g || !dlnc_b || !workspace) return DIG_ERR_ARG;
-  const int rc = check(film_, u_, vk_, mem_, lnc_g, lnc_b, S, Lq, N, heads, d, slots_per_mem);
-  if (rc) return rc;
-  if (slots_per_mem != 1) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(c_) || !aligned16(dc_) || !aligned16(du_) || !aligned16(dfilm_) || !aligned16(dvk_) || !aligned16(dmem_)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::tcv_attn_bwd(film_, u_, vk_, mem_, lnc_g, lnc_b, eps, c_, lse, dc_, du_, dfilm_, dvk_, dmem_, dlnc_g, dlnc_b, workspace, S,
+                                       Lq, N, heads, d, slots_per_mem, drop))
+    return rc;
   const bf16_t* film = (const bf16_t*)film_; const bf16_t* u = (const bf16_t*)u_; const bf16_t* vk = (const bf16_t*)vk_;
   const bf16_t* mem = (const bf16_t*)mem_; const bf16_t* dc = (const bf16_t*)dc_;
   bf16_t* du = (bf16_t*)du_; bf16_t* dfilm = (bf16_t*)dfilm_; bf16_t* dvk = (bf16_t*)dvk_; bf16_t* dmem = (bf16_t*)dmem_;

@@ -179,11 +179,6 @@ __global__ __launch_bounds__(AB_THREADS) void abiaug_tail_kernel(const unsigned 
   }
 }
 
-inline bool run_ok(const dig_abi_run* r) {
-  return r && r->geom_type >= 0 && r->geom_type <= 2 && r->noise_var >= 0 && r->mb_size >= 1 && r->mb_size <= DIG_ABI_MB_MAX &&
-         r->rescale_factor >= 0 && r->rescale_factor <= 4;
-}
-
 inline int slices_for(long long npix) { return (int)std::min<long long>(64, std::max<long long>(1, npix / (4 * AB_THREADS))); }
 
 }  // namespace
@@ -191,22 +186,20 @@ inline int slices_for(long long npix) { return (int)std::min<long long>(64, std:
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_abiaug_sample(dig_abi_params* params, long long* info, const int* heights, const int* widths, int n_img,
                                  const dig_abi_run* run, unsigned long long seed, unsigned step, hipStream_t stream) {
-  if (!params || !info || !heights || !widths || n_img <= 0 || !run_ok(run)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_sample(params, info, heights, widths, n_img, run, seed, step)) return rc;
   hipLaunchKernelGGL(abiaug_sample_kernel, dim3(1), dim3(AB_THREADS), 0, stream, params, info, heights, widths, n_img, *run, seed, step);
   return dig_check_launch();
 }
 
 extern "C" long long dig_abiaug_workspace_bytes(int geom, int det, int wh, int ww, const dig_abi_run* run) {
-  if (!run_ok(run) || wh <= 0 || ww <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_workspace_bytes(geom, det, wh, ww, run)) return rc;
   return dig_abi::image_bytes(geom, det, wh, ww, run->rescale_factor);
 }
 
 extern "C" int dig_abiaug_warp_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                                   const dig_abi_params* params, const dig_abi_run* run, unsigned char* work, long long work_bytes, int max_wh,
                                   int max_ww, hipStream_t stream) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || n_img <= 0 || max_wh <= 0 || max_ww <= 0 ||
-      work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_warp_u8(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, max_wh, max_ww)) return rc;
   if (work_bytes == 0) return DIG_OK;                        // (no image has a workspace: no gate of the geometry fired)
   hipLaunchKernelGGL(abiaug_warp_kernel, dim3(slices_for((long long)max_wh * max_ww), n_img), dim3(AB_THREADS), 0, stream, packed, offsets,
                      heights, widths, params, *run, work, work_bytes);
@@ -216,9 +209,7 @@ extern "C" int dig_abiaug_warp_u8(const unsigned char* packed, const long long* 
 extern "C" int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths,
                                          int n_img, const dig_abi_params* params, const dig_abi_run* run, unsigned char* work,
                                          long long work_bytes, int max_wh, int max_ww, hipStream_t stream) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || n_img <= 0 || max_wh <= 0 || max_ww <= 0 ||
-      work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_deteriorate_u8(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, max_wh, max_ww)) return rc;
   if (work_bytes == 0) return DIG_OK;
   const dig_abi_run R = *run;
   const int s_img = slices_for((long long)max_wh * max_ww), s_rs = slices_for((long long)dig_abi::RS_H * dig_abi::RS_W);
@@ -244,12 +235,11 @@ extern "C" int dig_abiaug_deteriorate_u8(const unsigned char* packed, const long
 extern "C" int dig_abiaug_tail(const unsigned char* packed, const long long* offsets, const int* heights, const int* widths, int n_img,
                                const dig_abi_params* params, const dig_abi_run* run, const unsigned char* work, long long work_bytes, float* out,
                                int out_h, int out_w, float mean, float std_, int max_wh, int max_ww, hipStream_t stream) {
-  if (!packed || !offsets || !heights || !widths || !params || !run_ok(run) || !out || n_img <= 0 || out_h <= 0 || out_w <= 0 ||
-      max_wh <= 0 || max_ww <= 0 || std_ == 0.f || work_bytes < 0 || (work_bytes > 0 && !work))
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::abiaug_tail(packed, offsets, heights, widths, n_img, params, run, work, work_bytes, out, out_h, out_w, mean, std_, max_wh,
+                                      max_ww))
+    return rc;
   const int ksh = dig_pillow::ksize_for(max_ww, out_w), ksv = dig_pillow::ksize_for(max_wh, out_h);
-  const size_t lds = dig_kv::stage_b_lds_bytes(out_h, out_w, ksh, ksv) - 3 * (size_t)out_h * out_w;   // (no pixel planes)
-  if (lds > 160 * 1024) return DIG_ERR_UNSUPPORTED;
+  const size_t lds = dig_rules::abiaug_tail_lds_bytes(out_h, out_w, ksh, ksv);          // (stage B without the pixel planes)
   static size_t attr = 0;
   if (lds > attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(abiaug_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

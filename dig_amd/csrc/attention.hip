@@ -949,11 +949,9 @@ extern "C" int dig_attn_bwd_mode(int single_pass) {
 
 extern "C" int dig_attn_fwd_dropout(const void* qkv, void* ctx, float* lse, int n_img, int heads, int embed_dim,
                                     const dig_dropout_t* drop, int q_rows, hipStream_t stream) {
-  if (!qkv || !ctx || !lse || n_img <= 0 || heads <= 0 || embed_dim != heads * DH || q_rows < 1 || q_rows > N_TOK) return DIG_ERR_ARG;
+  if (int rc = dig_rules::attn_fwd_dropout(qkv, ctx, lse, n_img, heads, embed_dim, drop, q_rows)) return rc;
   const int nqb = (q_rows + 31) / 32;
-  if (!aligned16(qkv) || !aligned16(ctx)) return DIG_ERR_ALIGN;
   const size_t qb = (size_t)n_img * N_TOK * 3 * embed_dim * 2;
-  if (qb >= (1ull << 32)) return DIG_ERR_ARG;
   static bool attr[DIG_MAX_DEVICES] = {};
   const int dev = dig_device();
   if (!attr[dev]) {
@@ -980,13 +978,9 @@ extern "C" int dig_attn_fwd(const void* qkv, void* ctx, float* lse, int n_img, i
 extern "C" int dig_attn_bwd_dropout(const void* qkv, const void* ctx, const void* dctx, const float* lse, void* dqkv, int n_img,
                                     int heads, int embed_dim, float scale, float* q_colsum, float* v_colsum,
                                     const dig_dropout_t* drop, int q_rows, hipStream_t stream) {
-  if (!qkv || !ctx || !dctx || !lse || !dqkv || n_img <= 0 || heads <= 0 || embed_dim != heads * DH || q_rows < 1 || q_rows > N_TOK) return DIG_ERR_ARG;
+  if (int rc = dig_rules::attn_bwd_dropout(qkv, ctx, dctx, lse, dqkv, n_img, heads, embed_dim, scale, q_colsum, v_colsum, drop, q_rows)) return rc;
   const int nqb = (q_rows + 31) / 32;
-  if (nqb < 8 && q_colsum) return DIG_ERR_UNSUPPORTED;                       // the fused dQ column sums assume all eight query blocks
-  if ((q_colsum == nullptr) != (v_colsum == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(qkv) || !aligned16(ctx) || !aligned16(dctx) || !aligned16(dqkv)) return DIG_ERR_ALIGN;
   const size_t qb = (size_t)n_img * N_TOK * 3 * embed_dim * 2;
-  if (qb >= (1ull << 32)) return DIG_ERR_ARG;
   const int dev = dig_device();
   if (g_attn_bwd_single_pass.load(std::memory_order_relaxed) && !(drop && drop->thr) && nqb == 8) {
     static bool sp_attr[DIG_MAX_DEVICES] = {};
@@ -1029,12 +1023,8 @@ extern "C" int dig_attn_bwd_dropout(const void* qkv, const void* ctx, const void
 // rows, projt = Wproj^T [D in][D out] (bf16).  D a multiple of 128, at most 512 (the weight slice of a head fills the two operand tiles).
 extern "C" int dig_attn_bwd_proj(const void* qkv, const void* ctx, const void* dy, const void* projt, const float* lse, void* dqkv, int n_img,
                                  int heads, int embed_dim, float scale, float* q_colsum, float* v_colsum, hipStream_t stream) {
-  if (!qkv || !ctx || !dy || !projt || !lse || !dqkv || n_img <= 0 || heads <= 0) return DIG_ERR_ARG;
-  if ((q_colsum == nullptr) != (v_colsum == nullptr)) return DIG_ERR_ARG;
-  if (embed_dim != heads * DH || (embed_dim & 127) || embed_dim > 512) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(qkv) || !aligned16(ctx) || !aligned16(dy) || !aligned16(projt) || !aligned16(dqkv)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::attn_bwd_proj(qkv, ctx, dy, projt, lse, dqkv, n_img, heads, embed_dim, scale, q_colsum, v_colsum)) return rc;
   const size_t qb = (size_t)n_img * N_TOK * 3 * embed_dim * 2;
-  if (qb >= (1ull << 32)) return DIG_ERR_ARG;
   const int dev = dig_device();
   static bool attr[DIG_MAX_DEVICES] = {};
   if (!attr[dev]) {

@@ -62,8 +62,8 @@
 
 namespace {
 
-constexpr int KD = 384;                   // model width
-constexpr int NH = 6;                     // heads (of DH = 64)
+constexpr int KD = dig_rules::ATTN_BLOCK_DIM;                   // model width
+constexpr int NH = dig_rules::ATTN_BLOCK_HEADS;                     // heads (of DH = 64)
 constexpr int SLOTB = 24576;              // ring slot: [64 rows][128 k] (16 KiB, 16 pieces per row) + [64 rows][64 k] (8 KiB, 8 pieces per row)
 constexpr int RING_OFF = 0;
 constexpr int K_OFF = 3 * SLOTB;          // K fragments [key tile 8][k-step 4][lane 64] x 16 B;  projection phase: residual staging, 4 KiB per wave
@@ -550,19 +550,13 @@ __global__ __launch_bounds__(512) void attn_block_kernel(AbParams p) {
 
 }  // namespace
 
-extern "C" int dig_attn_block_supported(int heads, int embed_dim) { return (heads == NH && embed_dim == KD) ? 1 : 0; }
 
 // x_mid = x + proj(attention(ln1)) for n_img images of 256 tokens; qkv / lse null: nothing is kept for a backward (ctx is always written: scratch)
 extern "C" int dig_attn_block_fwd(const void* ln1, const void* x, const void* qkv_w, const float* qkv_b, const void* proj_w, const float* proj_b,
                                   void* qkv, void* ctx, float* lse, void* x_mid, int n_img, int heads, int embed_dim, float scale,
                                   hipStream_t stream) {
-  if (!ln1 || !x || !qkv_w || !proj_w || !ctx || !x_mid || n_img <= 0) return DIG_ERR_ARG;
-  if ((qkv == nullptr) != (lse == nullptr)) return DIG_ERR_ARG;
-  if (!dig_attn_block_supported(heads, embed_dim)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(ln1) || !aligned16(x) || !aligned16(qkv_w) || !aligned16(proj_w) || !aligned16(ctx) || !aligned16(x_mid) || (qkv && !aligned16(qkv)))
-    return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::attn_block_fwd(ln1, x, qkv_w, qkv_b, proj_w, proj_b, qkv, ctx, lse, x_mid, n_img, heads, embed_dim, scale)) return rc;
   const size_t qb = (size_t)n_img * 256 * 3 * KD * 2;
-  if (qb >= (1ull << 32)) return DIG_ERR_ARG;
   AbParams p;
   p.X = (const bf16_t*)ln1; p.resid = (const bf16_t*)x; p.Wqkv = (const bf16_t*)qkv_w; p.bqkv = qkv_b; p.Wp = (const bf16_t*)proj_w; p.bp = proj_b;
   p.qkv = (bf16_t*)qkv; p.ctx = (bf16_t*)ctx; p.lse = lse; p.out = (bf16_t*)x_mid; p.scale = scale;

@@ -5,8 +5,8 @@
 
 namespace {
 
-constexpr int N_TOK = 256;
-constexpr int DH = 64;
+constexpr int N_TOK = dig_rules::ATTN_TOKENS;
+constexpr int DH = dig_rules::ATTN_HEAD_DIM;
 constexpr int TILE = N_TOK * DH * 2;  // 32 KiB
 
 __device__ __forceinline__ int swz(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include "../../include/dig_hip.h"   // the ABI's types, limits and error codes; every entry point is compiled against its declaration
+#include "abi_rules.h"               // aligned16 / ranges_overlap, the limits and the argument rules of every entry point (shared with cpu_abi/)
 
 typedef unsigned short bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -252,10 +253,4 @@ __device__ __forceinline__ bool dig_grid_sum_last(float* __restrict__ ws, const 
 static inline int dig_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? DIG_OK : DIG_ERR_LAUNCH;
-}
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-// [a, a + bytes) and [b, b + bytes) share a byte
-static inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
 }

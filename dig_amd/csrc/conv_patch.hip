@@ -132,31 +132,28 @@ inline unsigned grid_for(size_t total) { return (unsigned)std::min<size_t>(8192,
 }  // namespace
 
 extern "C" int dig_im2col3x3(const void* x, void* col, int n_img, int H, int W, int C, int ldc, hipStream_t stream) {
-  if (!x || !col || n_img <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || ldc < 9 * C || (ldc & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(col)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::im2col3x3(x, col, n_img, H, W, C, ldc)) return rc;
   const size_t total = (size_t)n_img * H * W * (C / 8);
   hipLaunchKernelGGL(im2col3x3_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)col, n_img, H, W, C, ldc);
   return dig_check_launch();
 }
 
 extern "C" int dig_conv3x3_weight_flip(const void* w, void* wt, int c_out, int c_in, hipStream_t stream) {
-  if (!w || !wt || c_out <= 0 || c_in <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::conv3x3_weight_flip(w, wt, c_out, c_in)) return rc;
   hipLaunchKernelGGL(conv3x3_weight_flip_kernel, dim3(grid_for((size_t)c_out * c_in)), dim3(256), 0, stream, (const bf16_t*)w, (bf16_t*)wt, c_out,
                      c_in);
   return dig_check_launch();
 }
 
 extern "C" int dig_maxpool2x2_fwd(const void* x, void* y, unsigned char* idx, int n_img, int H, int W, int C, hipStream_t stream) {
-  if (!x || !y || !idx || n_img <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(y) || (reinterpret_cast<uintptr_t>(idx) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::maxpool2x2_fwd(x, y, idx, n_img, H, W, C)) return rc;
   const size_t total = (size_t)n_img * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL(maxpool2x2_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, idx, n_img, H, W, C);
   return dig_check_launch();
 }
 
 extern "C" int dig_maxpool2x2_bwd(const void* dy, const unsigned char* idx, void* dx, int n_img, int H, int W, int C, hipStream_t stream) {
-  if (!dy || !dx || !idx || n_img <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(dy) || !aligned16(dx) || (reinterpret_cast<uintptr_t>(idx) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::maxpool2x2_bwd(dy, idx, dx, n_img, H, W, C)) return rc;
   const size_t total = (size_t)n_img * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)dy, idx, (bf16_t*)dx, n_img, H, W, C);
   return dig_check_launch();

@@ -22,7 +22,8 @@
 
 namespace {
 
-constexpr int CTC_MAX_T = 64, CTC_MAX_C = 256, CTC_MAX_LDT = 63;
+using dig_rules::CTC_MAX_T;
+using dig_rules::CTC_MAX_C;
 
 __device__ __forceinline__ float lse2(float a, float b) {
   const float m = fmaxf(a, b);
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(64) void ctc_greedy_kernel(const float* __restrict_
 // 0) is never taken: neither it nor a descendant can become the result.  After the selection every state is re-centred on the best tot,
 // whose sum is kept in double, as the alpha recursion above does.  The next frame's logits are loaded before the search of the current
 // one.  LDS at W = 32, C = 256: 32 KB table + 1 KB log-softmax + 4.3 KB prefixes.
-constexpr int CTC_MAX_W = 32, CTC_PFX_WORDS = 17;                          // 64 prefix bytes and a pad word: row j starts on bank 17 j
+constexpr int CTC_MAX_W = dig_rules::CTC_MAX_W, CTC_PFX_WORDS = 17;                          // 64 prefix bytes and a pad word: row j starts on bank 17 j
 
 // The value of lane l (wave-uniform l) as a scalar: v_readlane, where __shfl would go through the LDS crossbar.
 __device__ __forceinline__ int lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
@@ -627,19 +628,12 @@ __global__ __launch_bounds__(64) void ctc_lex_fold_kernel(const unsigned long lo
   if (lane == 0) { best_index[b] = w; logp[b] = lpb; n_out[b] = n; }
 }
 
-int ctc_check(const void* logits, int ld, const void* target, int ldt, const void* target_len, int B, int T, int C, int blank) {
-  if (!logits || !target || !target_len || B < 0 || T <= 0 || C <= 0 || ldt <= 0 || ld < C || blank < 0 || blank >= C) return DIG_ERR_ARG;
-  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || ldt > CTC_MAX_LDT) return DIG_ERR_UNSUPPORTED;
-  return DIG_OK;
-}
-
 }  // namespace
 
 extern "C" int dig_ctc_loss(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B,
                             int T, int C, int blank, float* nll, float* loss, hipStream_t stream) {
-  if (!nll || !loss) return DIG_ERR_ARG;
-  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
-  if (rc != DIG_OK || B == 0) return rc;
+  if (int rc = dig_rules::ctc_loss(logits, ld, target, ldt, target_len, len_offset, B, T, C, blank, nll, loss)) return rc;
+  if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_kernel<false>, dim3(B), dim3(64), (size_t)T * 64 * sizeof(float), stream, logits, ld, target, ldt, target_len, len_offset,
                      (const float*)nullptr, B, T, C, blank, nll, (void*)nullptr, 0, 0);
   hipLaunchKernelGGL(ctc_mean_kernel, dim3(1), dim3(64), 0, stream, nll, B, loss);
@@ -649,9 +643,9 @@ extern "C" int dig_ctc_loss(const float* logits, int ld, const long long* target
 extern "C" int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset,
                                 const float* gscalar, int B, int T, int C, int blank, void* dlogits, int ldd, int dlogits_is_f32,
                                 hipStream_t stream) {
-  if (!dlogits || ldd < C) return DIG_ERR_ARG;
-  const int rc = ctc_check(logits, ld, target, ldt, target_len, B, T, C, blank);
-  if (rc != DIG_OK || B == 0) return rc;
+  if (int rc = dig_rules::ctc_loss_bwd(logits, ld, target, ldt, target_len, len_offset, gscalar, B, T, C, blank, dlogits, ldd, dlogits_is_f32))
+    return rc;
+  if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_kernel<true>, dim3(B), dim3(64), (size_t)T * 192 * sizeof(float), stream, logits, ld, target, ldt, target_len, len_offset,
                      gscalar, B, T, C, blank, (float*)nullptr, dlogits, ldd, dlogits_is_f32 ? 1 : 0);
   return dig_check_launch();
@@ -659,8 +653,7 @@ extern "C" int dig_ctc_loss_bwd(const float* logits, int ld, const long long* ta
 
 extern "C" int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids,
                                      float* score, int* n, hipStream_t stream) {
-  if (!logits || !ids || !score || !n || B < 0 || T <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_greedy_decode(logits, ld, B, T, C, blank, eos, padding, ids, score, n)) return rc;
   if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(64), 0, stream, logits, ld, T, C, blank, eos, padding, ids, score, n);
   return dig_check_launch();
@@ -668,33 +661,22 @@ extern "C" int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, 
 
 extern "C" int dig_ctc_beam_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, int beam_width,
                                    long long* ids, float* score, float* logp, int* n, hipStream_t stream) {
-  if (!logits || !ids || !score || !logp || !n || B < 0 || T <= 0 || C <= 0 || ld < C || blank < 0 || blank >= C || beam_width <= 0) return DIG_ERR_ARG;
-  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || beam_width > CTC_MAX_W) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_beam_decode(logits, ld, B, T, C, blank, eos, padding, beam_width, ids, score, logp, n)) return rc;
   if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_beam_kernel, dim3(B), dim3(64), (size_t)((beam_width * ((C + 63) / 64 * 64) + 255) & ~255) * sizeof(float), stream, logits, ld, T, C, blank, eos, padding,
                      beam_width, ids, score, logp, n);
   return dig_check_launch();
 }
 
-static inline long long ctc_lex_chunks(int max_count) { return ((long long)max_count + CTC_LEX_CHUNK - 1) / CTC_LEX_CHUNK; }
-
-extern "C" long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count) {
-  if (B <= 0 || T <= 0 || C <= 0 || max_count < 0) return 0;
-  const long long keys = (long long)B * std::max(1LL, ctc_lex_chunks(max_count)) * (long long)sizeof(unsigned long long);
-  return keys + (long long)B * T * C * (long long)sizeof(float);
-}
-
 extern "C" int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, const int* words,
                                       const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count,
                                       int* best_index, float* logp, long long* ids, float* score, int* n, float* scores, void* workspace,
                                       long long workspace_bytes, hipStream_t stream) {
-  if (!logits || !words || !word_len || !lex_begin || !lex_count || !best_index || !logp || !ids || !score || !n || !workspace) return DIG_ERR_ARG;
-  if (B < 0 || T <= 0 || C <= 0 || ldw <= 0 || ld < C || blank < 0 || blank >= C || W < 0 || max_count < 0) return DIG_ERR_ARG;
-  if (T > CTC_MAX_T || C < 2 || C > CTC_MAX_C || ldw > CTC_MAX_LDT || B > 65535) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::ctc_lexicon_decode(logits, ld, B, T, C, blank, eos, padding, words, word_len, ldw, W, lex_begin, lex_count, max_count,
+                                             best_index, logp, ids, score, n, scores, workspace, workspace_bytes))
+    return rc;
   if (B == 0) return DIG_OK;
-  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
-  if (workspace_bytes < dig_ctc_lexicon_workspace_bytes(B, T, C, max_count)) return DIG_ERR_ARG;
-  const int n_chunks = (int)ctc_lex_chunks(max_count);                     // 0 with max_count == 0: nothing to score
+  const int n_chunks = (int)dig_rules::ctc_lex_chunks(max_count);                     // 0 with max_count == 0: nothing to score
   unsigned long long* partial = (unsigned long long*)workspace;
   float* lp = (float*)(partial + (size_t)B * std::max(1, n_chunks));
   if (n_chunks > 0) {

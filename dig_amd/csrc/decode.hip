@@ -242,28 +242,26 @@ __global__ __launch_bounds__(256) void attn_beam_advance_kernel(const float* __r
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_decode_embed(const long long* tokens, const float* emb, const float* pe_row, void* x, int B, int d, int vocab,
                                 hipStream_t stream) {
-  if (!tokens || !emb || !pe_row || !x || B <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::decode_embed(tokens, emb, pe_row, x, B, d, vocab)) return rc;
   hipLaunchKernelGGL(embed_kernel, dim3((B * d + 255) / 256), dim3(256), 0, stream, tokens, emb, pe_row, (bf16_t*)x, B, d, vocab);
   return dig_check_launch();
 }
 
 extern "C" int dig_decode_self_attn(const void* qkv_cache, void* out, int B, int T, int heads, int head_dim, int t, float scale,
                                     hipStream_t stream) {
-  if (!qkv_cache || !out || B <= 0 || heads <= 0 || t < 0 || t >= T) return DIG_ERR_ARG;
+  if (int rc = dig_rules::decode_self_attn(qkv_cache, out, B, T, heads, head_dim, t, scale)) return rc;
   const bf16_t* in = (const bf16_t*)qkv_cache;
   const int hk = heads * head_dim;
   if (head_dim == 64) hipLaunchKernelGGL(self_attn_kernel<64>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
   else if (head_dim == 48) hipLaunchKernelGGL(self_attn_kernel<48>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
   else if (head_dim == 24) hipLaunchKernelGGL(self_attn_kernel<24>, dim3(B, heads), dim3(64), 0, stream, in, (bf16_t*)out, T, hk, t, scale);
-  else return DIG_ERR_UNSUPPORTED;
+  else return DIG_ERR_UNSUPPORTED;   // unreachable: abi_rules.h
   return dig_check_launch();
 }
 
 extern "C" int dig_decode_cross_attn(const void* q, const void* kv_mem, void* out, float* weights, int B, int n_mem, int heads,
                                      int head_dim, float scale, int slots_per_mem, hipStream_t stream) {
-  if (!q || !kv_mem || !out || B <= 0 || n_mem <= 0 || heads <= 0 || slots_per_mem < 1 || B % slots_per_mem) return DIG_ERR_ARG;
-  if ((head_dim != 24 && head_dim != 48 && head_dim != 64) || n_mem > 8192) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(kv_mem) || !aligned16(q)) return DIG_ERR_ALIGN;           // 16-byte reads of both
+  if (int rc = dig_rules::decode_cross_attn(q, kv_mem, out, weights, B, n_mem, heads, head_dim, scale, slots_per_mem)) return rc;
   const size_t lds = (size_t)std::max(n_mem, 4 * head_dim) * sizeof(float);
   const bf16_t* qp = (const bf16_t*)q;
   const bf16_t* kv = (const bf16_t*)kv_mem;
@@ -275,23 +273,14 @@ extern "C" int dig_decode_cross_attn(const void* q, const void* kv_mem, void* ou
 }
 
 extern "C" int dig_softmax_argmax(const float* logits, int ld, float* probs, long long* tokens, int B, int C, hipStream_t stream) {
-  if (!logits || !probs || !tokens || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::softmax_argmax(logits, ld, probs, tokens, B, C)) return rc;
   hipLaunchKernelGGL(softmax_argmax_kernel, dim3(B), dim3(64), 0, stream, logits, ld, probs, tokens, C);
   return dig_check_launch();
 }
 
-// the arguments of the ranking, as both beam entry points check them
-static int beam_check(const float* logits, int ld, const float* seq_scores, int B, int beam_width, int max_width, int C, const long long* symbols,
-                      const long long* predecessors, const float* stored_scores) {
-  if (!logits || !seq_scores || !symbols || !predecessors || !stored_scores || B <= 0 || C <= 0 || ld < C) return DIG_ERR_ARG;
-  if (beam_width < 1 || beam_width > max_width || (size_t)beam_width * C * sizeof(float) > 60000) return DIG_ERR_UNSUPPORTED;
-  return DIG_OK;
-}
-
 extern "C" int dig_beam_step(const float* logits, int ld, float* seq_scores, int B, int beam_width, int C, int eos, long long* symbols,
                              long long* predecessors, float* stored_scores, hipStream_t stream) {
-  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 16, C, symbols, predecessors, stored_scores);
-  if (rc != DIG_OK) return rc;
+  if (int rc = dig_rules::beam_step(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores)) return rc;
   hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
                      eos, symbols, predecessors, stored_scores);
   return dig_check_launch();
@@ -301,11 +290,9 @@ extern "C" int dig_attn_beam_advance(const float* logits, int ld, float* seq_sco
                                      long long* predecessors, float* stored_scores, const long long* force_candidates, const float* s_in,
                                      const void* sbf_in, float* s_out, void* sbf_out, int S, const float* table, int E, void* inp, int ld_inp,
                                      hipStream_t stream) {
-  if (!s_in || !sbf_in || !s_out || !sbf_out || !table || !inp || S <= 0 || E <= 0 || ld_inp < E) return DIG_ERR_ARG;
-  const int rc = beam_check(logits, ld, seq_scores, B, beam_width, 8, C, symbols, predecessors, stored_scores);
-  if (rc != DIG_OK) return rc;
-  const size_t rows = (size_t)B * beam_width * S;
-  if (ranges_overlap(s_in, s_out, rows * sizeof(float)) || ranges_overlap(sbf_in, sbf_out, rows * sizeof(bf16_t))) return DIG_ERR_ARG;
+  if (int rc = dig_rules::attn_beam_advance(logits, ld, seq_scores, B, beam_width, C, eos, symbols, predecessors, stored_scores, force_candidates,
+                                            s_in, sbf_in, s_out, sbf_out, S, table, E, inp, ld_inp))
+    return rc;
   hipLaunchKernelGGL(attn_beam_advance_kernel, dim3(B), dim3(256), (size_t)beam_width * C * sizeof(float), stream, logits, ld, seq_scores, beam_width, C,
                      eos, symbols, predecessors, stored_scores, force_candidates, s_in, (const bf16_t*)sbf_in, s_out, (bf16_t*)sbf_out, S, table, E,
                      (bf16_t*)inp, ld_inp);

@@ -690,7 +690,7 @@ __global__ __launch_bounds__(256) void dropout_apply_kernel(const bf16_t* __rest
 extern "C" int dig_patch_embed_fwd(const float* img, const float* W, const float* bias, const unsigned char* mask,
                                    const float* mask_token, const float* pos, void* out, int n_img, int gh, int gw, int D,
                                    hipStream_t stream) {
-  if (!img || !W || !bias || !mask_token || !pos || !out || n_img <= 0 || D <= 0 || D > 1024 || (D & 63)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::patch_embed_fwd(img, W, bias, mask, mask_token, pos, out, n_img, gh, gw, D)) return rc;
   const int n_tok = n_img * gh * gw;
   if ((D & 31) == 0 && 48 * D * 4 <= 96 * 1024 && aligned16(img) && aligned16(bias) && aligned16(mask_token) && aligned16(pos) && aligned16(out)) {
     // fp32 MFMA form (exact f32 arithmetic, another summation order than the thread-per-channel kernel: both add k in a fixed order)
@@ -713,7 +713,7 @@ extern "C" int dig_patch_embed_fwd(const float* img, const float* W, const float
 
 extern "C" int dig_patch_embed_bwd(const void* dy, const float* img, const unsigned char* mask, float* dW, float* dbias,
                                    float* dmask_token, int n_img, int gh, int gw, int D, hipStream_t stream) {
-  if (!dy || !img || !dW || !dbias || !dmask_token || n_img <= 0 || D <= 0 || D > 1024 || (D & 63)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::patch_embed_bwd(dy, img, mask, dW, dbias, dmask_token, n_img, gh, gw, D)) return rc;
   const int n_tok = n_img * gh * gw;
   int tpb = 512;
   while ((n_tok + tpb - 1) / tpb > 256) tpb *= 2;
@@ -724,7 +724,7 @@ extern "C" int dig_patch_embed_bwd(const void* dy, const float* img, const unsig
 
 extern "C" int dig_window_pool_fwd(const void* x, void* out, int out_is_f32, int n_img, int gh, int gw, int nwin, int D,
                                    hipStream_t stream) {
-  if (!x || !out || n_img <= 0 || nwin <= 0 || gh <= 0 || gw <= 0 || (D & 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::window_pool_fwd(x, out, out_is_f32, n_img, gh, gw, nwin, D)) return rc;
   if ((D & 7) == 0 && D / 8 <= 256 && aligned16(x) && aligned16(out)) {
     if (out_is_f32)
       hipLaunchKernelGGL(window_pool_fwd16_kernel<float>, dim3(n_img * nwin), dim3(256), 0, stream, (const bf16_t*)x, (float*)out, n_img, gh, gw, nwin, D);
@@ -743,7 +743,7 @@ extern "C" int dig_window_pool_fwd(const void* x, void* out, int out_is_f32, int
 
 extern "C" int dig_window_pool_bwd(const void* dpool, void* dx, int n_img, int gh, int gw, int nwin, int D, int accumulate,
                                    hipStream_t stream) {
-  if (!dpool || !dx || n_img <= 0 || nwin <= 0 || gh <= 0 || gw <= 0 || (D & 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::window_pool_bwd(dpool, dx, n_img, gh, gw, nwin, D, accumulate)) return rc;
   if ((D & 7) == 0 && aligned16(dpool) && aligned16(dx)) {
     const size_t total = (size_t)n_img * gh * gw * (D / 8);
     hipLaunchKernelGGL(window_pool_bwd16_kernel, dim3((unsigned)std::min<size_t>(2048, (total + 255) / 256)), dim3(256), 0, stream,
@@ -770,7 +770,7 @@ __global__ void mask_views_u8_kernel(const T* __restrict__ mask, unsigned char* 
 }
 
 extern "C" int dig_mask_views_u8(const void* mask, int elem_kind, int B, int V, int N, int keep_views, unsigned char* out, hipStream_t stream) {
-  if (!mask || !out || B <= 0 || V <= 0 || N <= 0 || keep_views < 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mask_views_u8(mask, elem_kind, B, V, N, keep_views, out)) return rc;
   const size_t total = (size_t)B * V * N;
   const int grid = (int)std::min<size_t>(1024, (total + 255) / 256);
   switch (elem_kind) {                                                 // 0: 1-byte (bool / uint8), 1: fp32, 2: fp64, 3: int32, 4: int64
@@ -779,34 +779,32 @@ extern "C" int dig_mask_views_u8(const void* mask, int elem_kind, int B, int V, 
     case 2: hipLaunchKernelGGL(mask_views_u8_kernel<double>, dim3(grid), dim3(256), 0, stream, (const double*)mask, out, B, V, N, keep_views); break;
     case 3: hipLaunchKernelGGL(mask_views_u8_kernel<int>, dim3(grid), dim3(256), 0, stream, (const int*)mask, out, B, V, N, keep_views); break;
     case 4: hipLaunchKernelGGL(mask_views_u8_kernel<long long>, dim3(grid), dim3(256), 0, stream, (const long long*)mask, out, B, V, N, keep_views); break;
-    default: return DIG_ERR_UNSUPPORTED;
+    default: return DIG_ERR_UNSUPPORTED;   // unreachable: abi_rules.h
   }
   return dig_check_launch();
 }
 
 extern "C" int dig_mask_to_index(const unsigned char* mask, int* idx, int* count, int B, int N, int max_per_sample,
                                  hipStream_t stream) {
-  if (!mask || !idx || !count || B <= 0 || N <= 0 || max_per_sample <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mask_to_index(mask, idx, count, B, N, max_per_sample)) return rc;
   hipLaunchKernelGGL(mask_to_index_kernel, dim3(B), dim3(64), 0, stream, mask, idx, count, B, N, max_per_sample);
   return dig_check_launch();
 }
 
 extern "C" int dig_gather_rows(const void* src, const int* idx, void* dst, int M, int M_pad, int D, hipStream_t stream) {
-  if (!src || !idx || !dst || M <= 0 || M_pad < M || (D & 7)) return DIG_ERR_ARG;
-  if (!aligned16(src) || !aligned16(dst)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::gather_rows(src, idx, dst, M, M_pad, D)) return rc;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(M_pad), dim3(64), 0, stream, (const bf16_t*)src, idx, (bf16_t*)dst, M, D / 8);
   return dig_check_launch();
 }
 
 extern "C" int dig_scatter_rows_add(const void* src, const int* idx, void* dst, int M, int D, hipStream_t stream) {
-  if (!src || !idx || !dst || M <= 0 || (D & 7)) return DIG_ERR_ARG;
-  if (!aligned16(src) || !aligned16(dst)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::scatter_rows_add(src, idx, dst, M, D)) return rc;
   hipLaunchKernelGGL(scatter_rows_add_kernel, dim3(M), dim3(64), 0, stream, (const bf16_t*)src, idx, (bf16_t*)dst, M, D / 8);
   return dig_check_launch();
 }
 
 extern "C" int dig_mim_target(const float* img, const int* idx, float* target, int M, int gh, int gw, int normalize, hipStream_t stream) {
-  if (!img || !idx || !target || M <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mim_target(img, idx, target, M, gh, gw, normalize)) return rc;
   hipLaunchKernelGGL(mim_target_kernel, dim3((M * 48 + 255) / 256), dim3(256), 0, stream, img, idx, target, M, gh, gw, gh * 4,
                      gw * 4, normalize);
   return dig_check_launch();
@@ -814,7 +812,7 @@ extern "C" int dig_mim_target(const float* img, const int* idx, float* target, i
 
 extern "C" int dig_mse_fwd_bwd_ws(const float* pred, int ld_pred, const float* target, int M, int C, float gscale, float* loss,
                                   void* dpred, int ld_dpred, float* workspace, hipStream_t stream) {
-  if (!pred || !target || M <= 0 || C <= 0 || ld_pred < C || (dpred && ld_dpred < C)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::mse_fwd_bwd_ws(pred, ld_pred, target, M, C, gscale, loss, dpred, ld_dpred, workspace)) return rc;
   const int ldd = dpred ? ld_dpred : C;
   const int total = M * ldd;
   hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(std::min(256, (total + 255) / 256)), dim3(256), 0, stream, pred, ld_pred, target, M, C,
@@ -827,8 +825,7 @@ extern "C" int dig_mse_fwd_bwd(const float* pred, int ld_pred, const float* targ
 }
 
 extern "C" int dig_add_bf16(const void* a, const void* b, void* out, long long n, hipStream_t stream) {
-  if (!a || !b || !out || n <= 0 || (n & 7)) return DIG_ERR_ARG;
-  if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::add_bf16(a, b, out, n)) return rc;
   const size_t n8 = (size_t)n / 8;
   hipLaunchKernelGGL(add_bf16_kernel, dim3((unsigned)std::min<size_t>(4096, (n8 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a,
                      (const bf16_t*)b, (bf16_t*)out, n8);
@@ -836,8 +833,7 @@ extern "C" int dig_add_bf16(const void* a, const void* b, void* out, long long n
 }
 
 extern "C" int dig_gelu_bwd(const void* dact, const void* pre, void* dpre, long long n, hipStream_t stream) {
-  if (!dact || !pre || !dpre || n <= 0 || (n & 7)) return DIG_ERR_ARG;
-  if (!aligned16(dact) || !aligned16(pre) || !aligned16(dpre)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::gelu_bwd(dact, pre, dpre, n)) return rc;
   const size_t n8 = (size_t)n / 8;
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)std::min<size_t>(8192, (n8 + 255) / 256)), dim3(256), 0, stream,
                      (const bf16_t*)dact, (const bf16_t*)pre, (bf16_t*)dpre, n8);
@@ -857,8 +853,7 @@ extern "C" long long dig_colsum_workspace_bytes(int rows, int C) {
 }
 
 extern "C" int dig_colsum(const void* x, float* out, float* workspace, int rows, int C, int ld, hipStream_t stream) {
-  if (!x || !out || !workspace || rows <= 0 || C <= 0 || (C & 7) || (ld & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum(x, out, workspace, rows, C, ld)) return rc;
   const int cb = (C + 511) / 512;
   const int rpb = colsum_rows_per_block(rows, C);
   const int nb = (rows + rpb - 1) / rpb;
@@ -869,14 +864,13 @@ extern "C" int dig_colsum(const void* x, float* out, float* workspace, int rows,
 
 // out[c] += sum_b partials[b][c]  (the per-64-row column sums dig_gemm_bf16 writes with colsum_partials)
 extern "C" int dig_colsum_partials(const float* partials, int n_parts, int C, float* out, hipStream_t stream) {
-  if (!partials || !out || n_parts <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(partials)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum_partials(partials, n_parts, C, out)) return rc;
   hipLaunchKernelGGL(colsum_finalize_kernel, dim3(C / 8), dim3(256), 0, stream, partials, n_parts, C, out);
   return dig_check_launch();
 }
 
 extern "C" int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_segs, hipStream_t stream) {
-  if (!segs || n_segs < 1 || n_segs > DIG_COLSUM_MAX_SEGS) return DIG_ERR_ARG;
+  if (int rc = dig_rules::colsum_partials_multi(segs, n_segs)) return rc;
   ColsumSegs a;
   a.n_segs = n_segs;
   // more than one block's worth of segments with every width a multiple of 32: the full-line form (32 columns per workgroup)
@@ -886,8 +880,6 @@ extern "C" int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_seg
   int blocks = 0;
   for (int k = 0; k < n_segs; ++k) {
     const dig_colsum_seg_t& g = segs[k];
-    if (!g.partials || !g.out || g.n_parts <= 0 || g.C <= 0 || (g.C & 7) || g.stride < g.C || (g.stride & 3)) return DIG_ERR_ARG;
-    if (!aligned16(g.partials)) return DIG_ERR_ALIGN;
     a.part[k] = g.partials; a.out[k] = g.out; a.stride[k] = g.stride; a.n_parts[k] = g.n_parts;
     a.first[k] = blocks;
     blocks += g.C / cols;
@@ -899,8 +891,7 @@ extern "C" int dig_colsum_partials_multi(const dig_colsum_seg_t* segs, int n_seg
 }
 
 extern "C" int dig_patchify_bf16(const float* img, const unsigned char* mask, void* out, int n_img, int gh, int gw, hipStream_t stream) {
-  if (!img || !out || n_img <= 0) return DIG_ERR_ARG;
-  if (!aligned16(img) || !aligned16(out)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::patchify_bf16(img, mask, out, n_img, gh, gw)) return rc;
   const int n_tok = n_img * gh * gw;
   hipLaunchKernelGGL(patchify_bf16_kernel, dim3((n_tok * 16 + 255) / 256), dim3(256), 0, stream, img, mask, (bf16_t*)out, n_tok, gh, gw,
                      gh * 4, gw * 4);
@@ -909,8 +900,7 @@ extern "C" int dig_patchify_bf16(const float* img, const unsigned char* mask, vo
 
 extern "C" int dig_colsum_masked(const void* x, const unsigned char* mask, float* out_unmasked, float* out_masked,
                                  float* workspace /* 2 x dig_colsum_workspace_bytes(rows, C) */, int rows, int C, hipStream_t stream) {
-  if (!x || !mask || !out_unmasked || !out_masked || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::colsum_masked(x, mask, out_unmasked, out_masked, workspace, rows, C)) return rc;
   const int cb = (C + 511) / 512;
   const int rpb = colsum_rows_per_block(rows, C);
   const int nb = (rows + rpb - 1) / rpb;
@@ -923,9 +913,7 @@ extern "C" int dig_colsum_masked(const void* x, const unsigned char* mask, float
 }
 
 extern "C" int dig_dropout_apply(const void* in, void* out, long long rows, int cols, const dig_dropout_t* drop, hipStream_t stream) {
-  if (!in || !out || !drop || rows <= 0 || cols <= 0 || (cols & 7) || rows * cols >= (1ll << 32)) return DIG_ERR_ARG;
-  if (drop->pthr && drop->rows_per_sample <= 0) return DIG_ERR_ARG;
-  if (!aligned16(in) || !aligned16(out)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::dropout_apply(in, out, rows, cols, drop)) return rc;
   const long long n8 = rows * cols / 8;
   hipLaunchKernelGGL(dropout_apply_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, n8, cols, *drop);
   return dig_check_launch();

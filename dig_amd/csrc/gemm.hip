@@ -70,7 +70,7 @@ __device__ __forceinline__ void epilogue_drop(float (&v)[8], const DropArg<true>
 __device__ __forceinline__ void epilogue_drop(float (&)[8], const DropArg<false>&, int, int, int) {}
 
 constexpr int BI = 128, BJ = 128;
-constexpr int BR = 64;                   // granule of the reduction dim (R % 64 rule for direct operands, split slabs)
+constexpr int BR = dig_rules::GEMM_BR;                   // granule of the reduction dim (R % 64 rule for direct operands, split slabs)
 
 // chunk swizzle of the direct layout: rows are BK*2 bytes; 16 consecutive rows must hit 16 distinct 16-B slots of a
 // 256-B bank row for ds_read_b128
@@ -961,27 +961,11 @@ extern "C" int dig_gemm_bf16_dropout(const void* A, const void* B, void* C, int 
                                      void* pre_act, int ldp, float alpha, int alpha_cols, int act, int splits, int a_rows,
                                      int b_rows, int bk, float* colsum_partials, const dig_dropout_t* drop,
                                      hipStream_t stream) {
-  if (!A || !B || !C || I <= 0 || J <= 0 || R <= 0 || splits < 1) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gemm_bf16_dropout(A, B, C, I, J, R, lda, ldb, ldc, trans_a, trans_b, out_kind, bias, resid, ldr, pre_act, ldp, alpha,
+                                            alpha_cols, act, splits, a_rows, b_rows, bk, colsum_partials, drop))
+    return rc;
   const bool dropping = drop && (drop->thr || drop->pthr);
-  if (dropping) {
-    // instantiated for the tiles the fine-tune step uses: 128x128 (bk 0 / 64 / 32) forward and dgrad, 256x256 / 256x192 (bk 244 / 264) forward
-    if (out_kind != 0 || trans_a || !(bk == 0 || bk == 32 || bk == 64 || ((bk == 244 || bk == 264) && !trans_b))) return DIG_ERR_UNSUPPORTED;
-    if ((size_t)I * (size_t)J >= (1ull << 32) || (drop->pthr && drop->rows_per_sample <= 0)) return DIG_ERR_ARG;
-  }
-  if (bias && !aligned16(bias)) return DIG_ERR_ALIGN;
-  if (out_kind < 0 || out_kind > 2 || act < 0 || act > 2 || (bk != 0 && bk != 32 && bk != 64 && bk != 244 && bk != 264 && bk != 212 && bk != 221 && bk != 544 && bk != 564)) return DIG_ERR_ARG;
-  if (act == 2 && !resid) return DIG_ERR_ARG;                   // act 2: resid carries the saved pre-activation
   if (bk == 0) bk = 64;
-  if (!aligned16(A) || !aligned16(B) || !aligned16(C) || (lda & 7) || (ldb & 7)) return DIG_ERR_ALIGN;
-  if ((J & 7) || (ldc & 7) || (resid && ((ldr & 7) || !aligned16(resid))) || (pre_act && ((ldp & 7) || !aligned16(pre_act)))) return DIG_ERR_ALIGN;
-  if (!trans_a && (R % BR)) return DIG_ERR_ARG;   // direct operands need R % 64 == 0 (row-wrap would pollute)
-  if (!trans_b && (R % BR)) return DIG_ERR_ARG;
-  if (out_kind == 2 && (bias || resid || act)) return DIG_ERR_ARG;
-  if (out_kind != 2 && splits != 1) return DIG_ERR_ARG;
-  if (out_kind == 2 && ldc != J) return DIG_ERR_ARG;            // partial slabs are dense [splits][I][J]
-  if (colsum_partials && !(act == 2 && out_kind == 0 && trans_b && !trans_a && (bk < 100 || bk == 244)))
-    return DIG_ERR_UNSUPPORTED;                                  // 128x128 kernel and the 64x64-per-wave wide tiles
-  if (colsum_partials && !aligned16(colsum_partials)) return DIG_ERR_ALIGN;
   GemmParams p;
   p.splits_x = 0;
   p.colsum = colsum_partials;
@@ -991,13 +975,10 @@ extern "C" int dig_gemm_bf16_dropout(const void* A, const void* B, void* C, int 
   // a_rows / b_rows (0 = default) bound the rows that really exist in memory; rows past them read as zero.
   const size_t ab = (size_t)(a_rows > 0 ? a_rows : (trans_a ? R : I)) * lda * 2;
   const size_t bb = (size_t)(b_rows > 0 ? b_rows : (trans_b ? R : J)) * ldb * 2;
-  if (ab >= (1ull << 32) || bb >= (1ull << 32)) return DIG_ERR_ARG;
   p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
   p.bias = bias; p.resid = (const bf16_t*)resid; p.ldr = ldr; p.pre = (bf16_t*)pre_act; p.ldp = ldp;
   p.alpha = alpha; p.alpha_cols = alpha_cols; p.act = act;
-  const int rtiles = (R + BR - 1) / BR;
-  p.r_per_split = ((rtiles + splits - 1) / splits) * BR;
-  if ((R + p.r_per_split - 1) / p.r_per_split != splits) return DIG_ERR_ARG;   // use dig_gemm_effective_splits()
+  p.r_per_split = (int)dig_rules::gemm_rows_per_split(R, splits);
   p.tiles_i = (I + BI - 1) / BI; p.tiles_j = (J + BJ - 1) / BJ;
   if (dropping) {
     const DropArg<true> da{*drop};
@@ -1049,7 +1030,7 @@ extern "C" int dig_gemm_bf16_dropout(const void* A, const void* B, void* C, int 
   DIG_GEMM_CASE(false, true, 1)
   DIG_GEMM_CASE(true, true, 2)
 #undef DIG_GEMM_CASE
-  return DIG_ERR_UNSUPPORTED;
+  return DIG_ERR_UNSUPPORTED;   // unreachable: abi_rules.h (gemm_form_ok lists the forms instantiated above)
 }
 
 extern "C" int dig_gemm_bf16(const void* A, const void* B, void* C, int I, int J, int R, int lda, int ldb, int ldc,
@@ -1060,23 +1041,13 @@ extern "C" int dig_gemm_bf16(const void* A, const void* B, void* C, int I, int J
                                alpha_cols, act, splits, a_rows, b_rows, bk, colsum_partials, nullptr, stream);
 }
 
-// Number of R-splits dig_gemm_bf16 will really use for a requested split count (slabs are whole 64-row K-tiles).
-extern "C" int dig_gemm_effective_splits(int R, int splits) {
-  if (R <= 0 || splits < 1) return 0;
-  const int rtiles = (R + BR - 1) / BR;
-  const int per = ((rtiles + splits - 1) / splits) * BR;
-  return (R + per - 1) / per;
-}
-
 extern "C" int dig_reduce_partials_multi(const dig_reduce_seg_t* segs, int n_segs, hipStream_t stream) {
-  if (!segs || n_segs < 1 || n_segs > DIG_REDUCE_MAX_SEGS) return DIG_ERR_ARG;
+  if (int rc = dig_rules::reduce_partials_multi(segs, n_segs)) return rc;
   ReduceSegs a;
   a.n_segs = n_segs;
   int blocks = 0;
   for (int k = 0; k < n_segs; ++k) {
     const dig_reduce_seg_t& g = segs[k];
-    if (!g.partials || !g.out || g.splits < 1 || g.n <= 0 || (g.n & 3)) return DIG_ERR_ARG;
-    if (!aligned16(g.partials) || !aligned16(g.out)) return DIG_ERR_ALIGN;
     a.part[k] = g.partials; a.out[k] = g.out; a.n4[k] = g.n / 4; a.splits[k] = g.splits;
     a.first[k] = blocks;
     blocks += (int)std::min<long long>(1024, (g.n / 4 + 255) / 256);
@@ -1087,8 +1058,7 @@ extern "C" int dig_reduce_partials_multi(const dig_reduce_seg_t* segs, int n_seg
 }
 
 extern "C" int dig_reduce_partials_bf16(const float* partials, int splits, long long n, void* out, hipStream_t stream) {
-  if (!partials || !out || splits < 1 || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(partials) || (((uintptr_t)out) & 7u)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::reduce_partials_bf16(partials, splits, n, out)) return rc;
   const long long n4 = n / 4;
   hipLaunchKernelGGL(reduce_partials_bf16_kernel, dim3((unsigned)std::min<long long>(2048, (n4 + 255) / 256)), dim3(256), 0, stream, partials,
                      splits, n4, (bf16_t*)out);
@@ -1097,8 +1067,7 @@ extern "C" int dig_reduce_partials_bf16(const float* partials, int splits, long 
 
 extern "C" int dig_reduce_partials(const float* partials, int splits, long long n, float* out, int accumulate,
                                    hipStream_t stream) {
-  if (!partials || !out || splits < 1 || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(partials) || !aligned16(out)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::reduce_partials(partials, splits, n, out, accumulate)) return rc;
   const long long n4 = n / 4;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)std::min<long long>(2048, (n4 + 255) / 256)), dim3(256), 0, stream,
                      partials, splits, n4, out, accumulate);

@@ -25,8 +25,8 @@ __device__ __forceinline__ void load8f(const bf16_t* __restrict__ src, float (&r
   for (int e = 0; e < 4; ++e) { r[2 * e] = bf2f((bf16_t)(w[e] & 0xffff)); r[2 * e + 1] = bf2f((bf16_t)(w[e] >> 16)); }
 }
 
-constexpr int MAXA = 1024;     // attention width (attDim): <= 1024, multiple of 8
-constexpr int MAXN = 512;      // encoder tokens per sample
+constexpr int MAXA = dig_rules::ADDATTN_MAX_A;     // attention width (attDim): <= 1024, multiple of 8
+constexpr int MAXN = dig_rules::ADDATTN_MAX_N;      // encoder tokens per sample
 
 // scores of one sample: a wave per token (lanes over the A channels, 8 per lane and pass), wave reduction.
 // sp: sProj row staged in LDS (fp32), w in LDS.  v[n] = sum_a w[a] * tanh(sp[a] + xproj[n, a])
@@ -404,9 +404,7 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const long long* __rest
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_addattn_fwd(const void* xproj, const void* sproj, const float* w, const void* x, float* alpha, void* ctx, int ldc, int B, int N,
                                int A, int X, hipStream_t stream) {
-  if (!xproj || !sproj || !w || !x || !alpha || !ctx || B <= 0 || N <= 0 || N > MAXN || A <= 0 || A > MAXA || (A & 7) || X <= 0 || (X & 1) || (ldc & 1))
-    return DIG_ERR_ARG;
-  if (!aligned16(xproj)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_fwd(xproj, sproj, w, x, alpha, ctx, ldc, B, N, A, X)) return rc;
   hipLaunchKernelGGL(addattn_fwd_kernel, dim3(B), dim3(NT), 0, stream, (const bf16_t*)xproj, (const bf16_t*)sproj, w, (const bf16_t*)x, alpha,
                      (bf16_t*)ctx, ldc, N, A, X);
   return dig_check_launch();
@@ -414,9 +412,7 @@ extern "C" int dig_addattn_fwd(const void* xproj, const void* sproj, const float
 
 extern "C" int dig_addattn_fwd_slots(const void* xproj, const void* sproj, const float* w, const void* x, float* alpha, void* ctx, int ldc, int B, int N,
                                      int A, int X, int slots, hipStream_t stream) {
-  if (!xproj || !sproj || !w || !x || !ctx || B <= 0 || N <= 0 || A <= 0 || X <= 0 || (X & 1) || (ldc & 1)) return DIG_ERR_ARG;
-  if (N > MAXN || A > MAXA || (A & 7) || slots < 1 || slots > 8) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(xproj)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_fwd_slots(xproj, sproj, w, x, alpha, ctx, ldc, B, N, A, X, slots)) return rc;
   // sp [K][A] | ws [A], re-used by part [K][X] on the split-token path (X <= NT), then v [K][N]: at most 8 * (1024 + 512) * 4 + 4096 B
   const int K = slots, v_off = std::max(K * A + A, X / 2 <= NT / 2 ? K * X : 0);
   const size_t lds = (size_t)(v_off + K * N) * sizeof(float);                     // <= 53,248 B: below the 64 KB a launch gets by default
@@ -434,10 +430,7 @@ extern "C" int dig_addattn_fwd_slots(const void* xproj, const void* sproj, const
 
 extern "C" int dig_addattn_bwd(const void* xproj, const void* sproj, const float* w, const void* x, const float* alpha, const void* dctx, int ldd,
                                float* dv, void* dsproj, float* dw_acc, int B, int N, int A, int X, hipStream_t stream) {
-  if (!xproj || !sproj || !w || !x || !alpha || !dctx || !dv || !dsproj || !dw_acc || B <= 0 || N <= 0 || N > MAXN || A <= 0 || A > MAXA || (A & 7) ||
-      X <= 0 || X > MAXA || (X & 7))
-    return DIG_ERR_ARG;
-  if (!aligned16(xproj) || !aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::addattn_bwd(xproj, sproj, w, x, alpha, dctx, ldd, dv, dsproj, dw_acc, B, N, A, X)) return rc;
   hipLaunchKernelGGL(addattn_bwd_kernel, dim3(B), dim3(NT), 0, stream, (const bf16_t*)xproj, (const bf16_t*)sproj, w, (const bf16_t*)x, alpha,
                      (const bf16_t*)dctx, ldd, dv, (bf16_t*)dsproj, dw_acc, N, A, X);
   return dig_check_launch();
@@ -446,11 +439,8 @@ extern "C" int dig_addattn_bwd(const void* xproj, const void* sproj, const float
 extern "C" int dig_addattn_bwd_tokens(const void* xproj, const void* sproj_all, const float* w, const float* dv_all, const float* alpha_all,
                                       const void* dctx_all, int ldd, void* dxproj, void* dx, int T, int B, int N, int A, int X,
                                       hipStream_t stream) {
-  if (!xproj || !sproj_all || !w || !dv_all || !alpha_all || !dctx_all || !dxproj || !dx || T <= 0 || B <= 0 || N <= 0 || A <= 0 || (A & 1) || X <= 0 ||
-      (X & 1))
-    return DIG_ERR_ARG;
-  const size_t l1 = ((size_t)T * A + (size_t)T * 64) * 4, l2 = ((size_t)T * X + (size_t)T * 64) * 4;
-  if (l1 > 150 * 1024 || l2 > 150 * 1024) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::addattn_bwd_tokens(xproj, sproj_all, w, dv_all, alpha_all, dctx_all, ldd, dxproj, dx, T, B, N, A, X)) return rc;
+  const size_t l1 = dig_rules::addattn_bwd_tokens_lds_bytes(T, A), l2 = dig_rules::addattn_bwd_tokens_lds_bytes(T, X);
   static size_t a1 = 0, a2 = 0;
   if (l1 > a1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(addattn_dxproj_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1); a1 = l1; }
   if (l2 > a2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(addattn_dx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2); a2 = l2; }
@@ -463,7 +453,7 @@ extern "C" int dig_addattn_bwd_tokens(const void* xproj, const void* sproj_all, 
 
 extern "C" int dig_gru_cell_fwd(const void* gi, const void* gh, const float* s_prev, float* s, void* s_bf16, float* gates, int B, int S,
                                 hipStream_t stream) {
-  if (!gi || !gh || !s || !s_bf16 || !gates || B <= 0 || S <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gru_cell_fwd(gi, gh, s_prev, s, s_bf16, gates, B, S)) return rc;
   hipLaunchKernelGGL(gru_cell_fwd_kernel, dim3((B * S + 255) / 256), dim3(256), 0, stream, (const bf16_t*)gi, (const bf16_t*)gh, s_prev, s, (bf16_t*)s_bf16,
                      gates, B, S);
   return dig_check_launch();
@@ -471,14 +461,14 @@ extern "C" int dig_gru_cell_fwd(const void* gi, const void* gh, const float* s_p
 
 extern "C" int dig_gru_cell_bwd(const float* ds_a, const float* ds_b, const float* ds_c, const float* ds_d, const float* gates, const float* s_prev,
                                 void* dgi, void* dgh, float* ds_prev, int B, int S, hipStream_t stream) {
-  if (!ds_a || !gates || !dgi || !dgh || !ds_prev || B <= 0 || S <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::gru_cell_bwd(ds_a, ds_b, ds_c, ds_d, gates, s_prev, dgi, dgh, ds_prev, B, S)) return rc;
   hipLaunchKernelGGL(gru_cell_bwd_kernel, dim3((B * S + 255) / 256), dim3(256), 0, stream, ds_a, ds_b, ds_c, ds_d, gates, s_prev, (bf16_t*)dgi, (bf16_t*)dgh,
                      ds_prev, B, S);
   return dig_check_launch();
 }
 
 extern "C" int dig_embed_rows(const long long* tokens, const float* table, void* out, int ld, int rows, int cols, int vocab, hipStream_t stream) {
-  if (!tokens || !table || !out || rows <= 0 || cols <= 0 || ld < cols || vocab <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::embed_rows(tokens, table, out, ld, rows, cols, vocab)) return rc;
   const size_t n = (size_t)rows * cols;
   hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tokens, table, (bf16_t*)out, ld, rows, cols, vocab);
   return dig_check_launch();

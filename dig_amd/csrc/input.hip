@@ -83,11 +83,10 @@ __global__ __launch_bounds__(64) void random_masks_kernel(unsigned char* __restr
 extern "C" int dig_resize_bicubic_normalize_u8(const unsigned char* packed, const long long* offsets, const int* heights,
                                                const int* widths, int n_img, float* out, int out_h, int out_w, float mean,
                                                float std_, int max_h, int max_w, hipStream_t stream) {
-  if (!packed || !offsets || !heights || !widths || !out || n_img <= 0 || out_h <= 0 || out_w <= 0 || max_h <= 0 || max_w <= 0 || std_ == 0.f)
-    return DIG_ERR_ARG;
+  if (int rc = dig_rules::resize_bicubic_normalize_u8(packed, offsets, heights, widths, n_img, out, out_h, out_w, mean, std_, max_h, max_w))
+    return rc;
   const int ksh = ksize_for(max_w, out_w), ksv = ksize_for(max_h, out_h);
-  const size_t lds = ((size_t)out_w * (ksh + 2) + (size_t)out_h * (ksv + 2)) * sizeof(int);
-  if (lds > 160 * 1024) return DIG_ERR_UNSUPPORTED;                    // crops beyond ~ (64 x out) per axis: shrink on the host first
+  const size_t lds = dig_rules::resize_lds_bytes(out_h, out_w, ksh, ksv);
   static size_t attr = 0;
   if (lds > attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resize_normalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -100,7 +99,7 @@ extern "C" int dig_resize_bicubic_normalize_u8(const unsigned char* packed, cons
 
 extern "C" int dig_random_masks(unsigned char* mask, int n_rows, int n_patches, int num_mask, unsigned long long seed,
                                 unsigned step, hipStream_t stream) {
-  if (!mask || n_rows <= 0 || n_patches <= 0 || n_patches > 16384 || num_mask < 0 || num_mask > n_patches) return DIG_ERR_ARG;
+  if (int rc = dig_rules::random_masks(mask, n_rows, n_patches, num_mask, seed, step)) return rc;
   hipLaunchKernelGGL(random_masks_kernel, dim3(n_rows), dim3(64), n_patches * sizeof(unsigned), stream, mask, n_patches, num_mask,
                      (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), step);
   return dig_check_launch();

@@ -463,12 +463,7 @@ DIG_HD inline void jitter_pixel(int op, const dig_kv_params& P, int contrast_mea
   jitter_apply(op, P.jit_factor, P.hue_shift, contrast_mean, c);
 }
 
-// dynamic LDS bytes of stage B: the resize coefficient tables, four 8-byte contrast sums, the out_h x out_w x 3 image
-inline size_t stage_b_lds_bytes(int out_h, int out_w, int ksh, int ksv) {
-  size_t ints = (size_t)out_w * (ksh + 2) + (size_t)out_h * (ksv + 2);
-  ints += ints & 1;                                                                    // the sums start 8-byte aligned
-  return ints * sizeof(int) + 4 * sizeof(unsigned long long) + 3 * (size_t)out_h * out_w;
-}
+using dig_rules::stage_b_lds_bytes;   // dynamic LDS bytes of stage B (abi_rules.h: the rule and the launcher share it)
 
 // Pillow's ImageStat mean of L over n pixels (sum in a double), + 0.5, truncated
 DIG_HD inline int contrast_mean(long long sum_l, int n) { return (int)((double)sum_l / (double)n + 0.5); }

@@ -32,9 +32,8 @@ __global__ __launch_bounds__(256) void encode_labels_kernel(const int* __restric
 
 extern "C" int dig_encode_labels(const int* chars, const int* offsets, const int* class_of, int eos, int padding, int unknown, int max_len, int B,
                                  long long* labels, long long* lens, hipStream_t stream) {
-  if (!chars || !offsets || !class_of || !labels || !lens || max_len < 1 || B < 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::encode_labels(chars, offsets, class_of, eos, padding, unknown, max_len, B, labels, lens)) return rc;
   if (B == 0) return DIG_OK;
-  if ((long long)B * max_len > 0x7fffffffLL) return DIG_ERR_UNSUPPORTED;
   const int cells = B * max_len;
   hipLaunchKernelGGL(encode_labels_kernel, dim3((cells + 255) / 256), dim3(256), 0, stream, chars, offsets, class_of, eos, padding, unknown,
                      max_len, cells, labels, lens);

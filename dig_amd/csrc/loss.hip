@@ -152,35 +152,34 @@ __global__ __launch_bounds__(64) void step_meters_kernel(const float* __restrict
 }  // namespace
 
 extern "C" int dig_infonce_finish(const float* stats6, float loss_scale, float acc_scale, float* contra, float* accs4, hipStream_t stream) {
-  if (!stats6 || !contra || !accs4) return DIG_ERR_ARG;
+  if (int rc = dig_rules::infonce_finish(stats6, loss_scale, acc_scale, contra, accs4)) return rc;
   hipLaunchKernelGGL(infonce_finish_kernel, dim3(1), dim3(64), 0, stream, stats6, loss_scale, acc_scale, contra, accs4);
   return dig_check_launch();
 }
 
 extern "C" int dig_step_meters(const float* loss, const float* contra, const float* pixel, const float* accs4, const int* counts, int n_counts,
                                const float* grad_norm, float* out10, hipStream_t stream) {
-  if (!loss || !contra || !pixel || !accs4 || !counts || n_counts <= 0 || !out10) return DIG_ERR_ARG;
+  if (int rc = dig_rules::step_meters(loss, contra, pixel, accs4, counts, n_counts, grad_norm, out10)) return rc;
   hipLaunchKernelGGL(step_meters_kernel, dim3(1), dim3(64), 0, stream, loss, contra, pixel, accs4, counts, n_counts, grad_norm, out10);
   return dig_check_launch();
 }
 
 extern "C" int dig_l2norm_fwd(const float* x, float* y, float* inv_norm, int n, int C, float eps, hipStream_t stream) {
-  if (!x || !y || !inv_norm || n <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::l2norm_fwd(x, y, inv_norm, n, C, eps)) return rc;
   hipLaunchKernelGGL(l2norm_fwd_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, x, y, inv_norm, n, C, eps);
   return dig_check_launch();
 }
 
 extern "C" int dig_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, float* dx, int n, int C, hipStream_t stream) {
-  if (!dy || !y || !inv_norm || !dx || n <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::l2norm_bwd(dy, y, inv_norm, dx, n, C)) return rc;
   hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, dy, y, inv_norm, dx, n, C);
   return dig_check_launch();
 }
 
 extern "C" int dig_sgemm(const float* A, const float* B, float* C, int I, int J, int R, int lda, int ldb, int ldc, int trans_b,
                          float alpha, int r_splits, hipStream_t stream) {
-  if (!A || !B || !C || I <= 0 || J <= 0 || R <= 0 || r_splits < 1) return DIG_ERR_ARG;
-  const int per = ((R + r_splits - 1) / r_splits + 63) / 64 * 64;      // whole 64-deep K steps per split
-  if ((R + per - 1) / per != r_splits) return DIG_ERR_ARG;             // (callers pick r_splits with R % (64 * r_splits) == 0)
+  if (int rc = dig_rules::sgemm(A, B, C, I, J, R, lda, ldb, ldc, trans_b, alpha, r_splits)) return rc;
+  const int per = (int)dig_rules::sgemm_rows_per_split(R, r_splits);        // whole 64-deep K steps per split
   dim3 grid((J + 31) / 32, (I + 31) / 32, r_splits);
   if (trans_b)
     hipLaunchKernelGGL(sgemm_kernel<true>, grid, dim3(256), 0, stream, A, B, C, I, J, R, lda, ldb, ldc, alpha, per);
@@ -190,7 +189,7 @@ extern "C" int dig_sgemm(const float* A, const float* B, float* C, int I, int J,
 }
 
 extern "C" int dig_ce_rows_ws(float* logits, int n, int m, int label_offset, float gscale, float* out3, float* workspace, hipStream_t stream) {
-  if (!logits || !out3 || n <= 0 || m <= 0 || label_offset < 0 || label_offset + n > m) return DIG_ERR_ARG;
+  if (int rc = dig_rules::ce_rows_ws(logits, n, m, label_offset, gscale, out3, workspace)) return rc;
   hipLaunchKernelGGL(ce_rows_kernel, dim3(n), dim3(256), 0, stream, logits, n, m, label_offset, gscale, out3, workspace);
   return dig_check_launch();
 }

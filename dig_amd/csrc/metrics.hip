@@ -197,49 +197,40 @@ inline size_t lev_lds_bytes(int cap) { return (size_t)((cap + 1) / 2) * 64 * siz
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_string_match(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
                                 int B, int T, unsigned char* match, hipStream_t stream) {
-  if (!pred || !target || !canon || !match || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::string_match(pred, target, canon, n_classes, eos, B, T, match)) return rc;
   hipLaunchKernelGGL(string_match_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, match);
   return dig_check_launch();
 }
 
 extern "C" int dig_char_fmeasure(const long long* pred, const long long* target, const unsigned char* canon, int n_classes, int eos,
                                  int B, int T, double* f_per_sample, hipStream_t stream) {
-  if (!pred || !target || !canon || !f_per_sample || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::char_fmeasure(pred, target, canon, n_classes, eos, B, T, f_per_sample)) return rc;
   hipLaunchKernelGGL(char_fmeasure_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, pred, target, canon, n_classes, eos, B, T, f_per_sample);
   return dig_check_launch();
 }
 
 extern "C" int dig_tokens_to_text(const long long* tokens, const unsigned char* canon, int n_classes, int eos, int B, int T, int* text,
                                   int* len, hipStream_t stream) {
-  if (!tokens || !canon || !text || !len || n_classes <= 0 || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::tokens_to_text(tokens, canon, n_classes, eos, B, T, text, len)) return rc;
   hipLaunchKernelGGL(tokens_to_text_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, tokens, canon, n_classes, eos, B, T, text, len);
   return dig_check_launch();
 }
 
 extern "C" int dig_edit_distance(const int* a, const int* a_len, int lda, int a_rows, const int* a_index, const int* b, const int* b_len,
                                  int ldb, int n, int* dist, hipStream_t stream) {
-  if (!a || !a_len || !b || !b_len || !dist || lda <= 0 || ldb <= 0 || n <= 0 || a_rows <= 0) return DIG_ERR_ARG;
-  if (!a_index && a_rows < n) return DIG_ERR_ARG;
-  if (lda > LEV_MAX || ldb > LEV_MAX) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::edit_distance(a, a_len, lda, a_rows, a_index, b, b_len, ldb, n, dist)) return rc;
   hipLaunchKernelGGL(edit_distance_kernel, dim3((n + 63) / 64), dim3(64), lev_lds_bytes(ldb), stream, a, a_len, lda, a_rows, a_index, b, b_len,
                      ldb, n, dist);
   return dig_check_launch();
 }
 
-extern "C" long long dig_lexicon_search_workspace_bytes(int B, int max_count) {
-  if (B <= 0 || max_count < 0) return 0;
-  const long long n_chunks = max_count == 0 ? 1 : ((long long)max_count + LEX_CHUNK - 1) / LEX_CHUNK;
-  return (long long)B * n_chunks * (long long)sizeof(unsigned long long);
-}
 
 extern "C" int dig_lexicon_search(const int* query, const int* query_len, int ldq, int B, const int* words, const int* word_len, int ldw,
                                   int W, const int* lex_begin, const int* lex_count, int max_count, int* best_index, int* best_dist,
                                   void* workspace, long long workspace_bytes, hipStream_t stream) {
-  if (!query || !query_len || !words || !word_len || !lex_begin || !lex_count || !best_index || !best_dist || !workspace) return DIG_ERR_ARG;
-  if (ldq <= 0 || ldw <= 0 || B <= 0 || W <= 0 || max_count < 0) return DIG_ERR_ARG;
-  if (ldq > LEV_MAX || ldw > LEV_MAX || B > 65535) return DIG_ERR_UNSUPPORTED;
-  if ((((uintptr_t)workspace) & 7u) != 0) return DIG_ERR_ALIGN;
-  if (workspace_bytes < dig_lexicon_search_workspace_bytes(B, max_count)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::lexicon_search(query, query_len, ldq, B, words, word_len, ldw, W, lex_begin, lex_count, max_count, best_index, best_dist,
+                                         workspace, workspace_bytes))
+    return rc;
   const int n_chunks = max_count == 0 ? 1 : (int)(((long long)max_count + LEX_CHUNK - 1) / LEX_CHUNK);
   unsigned long long* partial = (unsigned long long*)workspace;
   hipLaunchKernelGGL(lexicon_search_kernel, dim3(n_chunks, B), dim3(64), lev_lds_bytes(ldq), stream, query, query_len, ldq, words, word_len,
@@ -249,7 +240,7 @@ extern "C" int dig_lexicon_search(const int* query, const int* query_len, int ld
 }
 
 extern "C" int dig_seq_confidence(const float* score, const int* text_len, int B, int T, double* conf, hipStream_t stream) {
-  if (!score || !text_len || !conf || B <= 0 || T <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_confidence(score, text_len, B, T, conf)) return rc;
   hipLaunchKernelGGL(seq_confidence_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, score, text_len, B, T, conf);
   return dig_check_launch();
 }

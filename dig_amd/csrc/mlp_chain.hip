@@ -67,11 +67,11 @@
 
 namespace {
 
-constexpr int KD = 384;                 // model width: reduction dim of stage 1, output width of stage 2
-constexpr int FC = 64;                  // hidden units per chunk
-constexpr int BM = 128;                 // token rows per workgroup
+constexpr int KD = dig_rules::CHAIN_DIM;                 // model width: reduction dim of stage 1, output width of stage 2
+constexpr int FC = dig_rules::CHAIN_FC;                  // hidden units per chunk
+constexpr int BM = dig_rules::CHAIN_ROWS;                 // token rows per workgroup
 constexpr int NJB = KD / 32;            // 12 output column blocks per token block
-constexpr int SLOT = 16384;
+constexpr int SLOT = dig_rules::CHAIN_SLOT;
 constexpr int W1_RING = 0;
 constexpr int W2_RING = 3 * SLOT;
 constexpr int P_OFF = 6 * SLOT;         // 4 pairs x [32 tokens][64 f] bf16
@@ -1071,13 +1071,13 @@ __global__ __launch_bounds__(512) void mlp_chain_kernel(ChainParams p) {
 
 template <int MODE, bool LN = false, bool DROP = false>
 int launch_chain(const ChainParams& p, hipStream_t stream) {
-  const int lds = X_OFF + (MODE == 0 ? (p.F + KD) * 4 : (MODE == 1 ? SLOT + (p.F + KD) * 4 : 2 * SLOT)) + (LN ? 4 * KD * 4 : 0);
+  const int lds = (int)dig_rules::mlp_chain_lds_bytes(MODE, LN, p.F);
 #ifdef DIG_CHAIN_LDS_ALL
   const int lds_launch = 160 * 1024;                                   // (lab build: stamps live in the spare LDS)
 #else
   const int lds_launch = lds;
 #endif
-  if (lds > 160 * 1024) return DIG_ERR_UNSUPPORTED;
+  if (lds > dig_rules::LDS_LIMIT) return DIG_ERR_UNSUPPORTED;   // unreachable: abi_rules.h
   static int attr_lds[DIG_MAX_DEVICES] = {};
   const int dev = dig_device();
   if (lds_launch > attr_lds[dev]) {
@@ -1100,27 +1100,12 @@ void no_layernorm(ChainParams& p) {
   p.drop = dig_dropout_t{};
 }
 
-int check_common(const void* x, const void* b1, const void* b2, const void* out, int R, int D, int F) {
-  if (!x || !b1 || !b2 || !out || R <= 0) return DIG_ERR_ARG;
-  if (D != KD || F < 2 * FC || (F % (2 * FC))) return DIG_ERR_UNSUPPORTED;       // an even number of 64-wide chunks
-  if (!aligned16(x) || !aligned16(b1) || !aligned16(b2) || !aligned16(out)) return DIG_ERR_ALIGN;
-  if ((size_t)R * F * 2 >= (1ull << 32) || (size_t)F * D * 2 >= (1ull << 31)) return DIG_ERR_UNSUPPORTED;
-  return DIG_OK;
-}
-
 }  // namespace
 
 // C-ABI: see include/dig_hip.h
-extern "C" int dig_mlp_chain_supported(int D, int F) { return D == KD && F >= 2 * FC && F % (2 * FC) == 0 && F <= 6144; }
-
 extern "C" int dig_mlp_chain_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, const void* resid,
                                  void* out, void* pre_out, void* act_out, int R, int D, int F, hipStream_t stream) {
-  const int rc = check_common(x, w1, w2, out, R, D, F);
-  if (rc != DIG_OK) return rc;
-  if ((b1 && !aligned16(b1)) || (b2 && !aligned16(b2)) || (resid && !aligned16(resid)) || (pre_out && !aligned16(pre_out)) ||
-      (act_out && !aligned16(act_out)))
-    return DIG_ERR_ALIGN;
-  if ((pre_out == nullptr) != (act_out == nullptr)) return DIG_ERR_ARG;             // both side outputs or none
+  if (int rc = dig_rules::mlp_chain_fwd(x, w1, b1, w2, b2, resid, out, pre_out, act_out, R, D, F)) return rc;
   ChainParams p;
   p.X = (const bf16_t*)x; p.B1 = (const bf16_t*)w1; p.B2 = (const bf16_t*)w2; p.bias1 = b1; p.bias2 = b2;
   p.resid = (const bf16_t*)resid; p.out = (bf16_t*)out; p.side0 = (bf16_t*)act_out; p.side1 = (bf16_t*)pre_out; p.colsum = nullptr;
@@ -1140,17 +1125,9 @@ extern "C" int dig_mlp_chain_fwd_ln_dropout(const void* x, const void* resid, co
                                             void* out, void* pre_out, void* act_out, const float* nln_g, const float* nln_b, void* nln_out,
                                             float* nln_mean, float* nln_rstd, int R, int D, int F, const dig_dropout_t* drop,
                                             hipStream_t stream) {
-  const int rc = check_common(x, w1, w2, out, R, D, F);
-  if (rc != DIG_OK) return rc;
-  if ((ln_g == nullptr) != (ln_b == nullptr) || (nln_g == nullptr) != (nln_b == nullptr) || (nln_g == nullptr) != (nln_out == nullptr)) return DIG_ERR_ARG;
-  if ((ln_mean == nullptr) != (ln_rstd == nullptr) || (nln_mean == nullptr) != (nln_rstd == nullptr)) return DIG_ERR_ARG;
-  if (!ln_g && (ln_out || ln_mean)) return DIG_ERR_ARG;                              // x is normalised already: nothing to report about it
-  if (resid && !aligned16(resid)) return DIG_ERR_ALIGN;
-  if ((pre_out == nullptr) != (act_out == nullptr)) return DIG_ERR_ARG;
-  if (F > 2048) return DIG_ERR_UNSUPPORTED;                                         // (LDS: the LayerNorm vectors sit behind b1 / b2)
-  if ((b1 && !aligned16(b1)) || (b2 && !aligned16(b2)) || (pre_out && !aligned16(pre_out)) || (act_out && !aligned16(act_out)) ||
-      (ln_out && !aligned16(ln_out)) || (nln_out && !aligned16(nln_out)))
-    return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::mlp_chain_fwd_ln_dropout(x, resid, ln_g, ln_b, eps, ln_out, ln_mean, ln_rstd, w1, b1, w2, b2, out, pre_out, act_out, nln_g,
+                                                   nln_b, nln_out, nln_mean, nln_rstd, R, D, F, drop))
+    return rc;
   ChainParams p;
   p.X = (const bf16_t*)x; p.B1 = (const bf16_t*)w1; p.B2 = (const bf16_t*)w2; p.bias1 = b1; p.bias2 = b2;
   p.resid = (const bf16_t*)resid; p.out = (bf16_t*)out; p.side0 = (bf16_t*)act_out; p.side1 = (bf16_t*)pre_out; p.colsum = nullptr;
@@ -1160,8 +1137,6 @@ extern "C" int dig_mlp_chain_fwd_ln_dropout(const void* x, const void* resid, co
   p.ln_g = ln_g; p.ln_b = ln_b; p.ln_out = (bf16_t*)ln_out; p.ln_mean = ln_mean; p.ln_rstd = ln_rstd;
   p.nln_g = nln_g; p.nln_b = nln_b; p.nln_out = (bf16_t*)nln_out; p.nln_mean = nln_mean; p.nln_rstd = nln_rstd; p.ln_eps = eps;
   if (drop && (drop->thr || drop->pthr)) {
-    if (drop->pthr && drop->rows_per_sample <= 0) return DIG_ERR_ARG;
-    if ((size_t)R * D >= (1ull << 32)) return DIG_ERR_UNSUPPORTED;                  // (element index of the mask hash: 32 bits)
     p.drop = *drop;
     return pre_out ? launch_chain<1, true, true>(p, stream) : launch_chain<0, true, true>(p, stream);
   }
@@ -1182,13 +1157,9 @@ extern "C" int dig_mlp_chain_fwd_ln(const void* x, const void* resid, const floa
 extern "C" int dig_mlp_chain_bwd_ln_proj(const void* dy, const void* w2t, const void* pre, const void* w1t, void* dpre_out, const void* x_mid,
                                          const float* ln_g, const float* ln_mean, const float* ln_rstd, void* dx_mid_out, float* colsum_partials,
                                          float* ln_partials, const void* projt, void* dctx_out, int R, int D, int F, hipStream_t stream) {
-  const int rc = check_common(dy, w2t, w1t, dx_mid_out, R, D, F);
-  if (rc != DIG_OK) return rc;
-  if (!pre || !dpre_out || !x_mid || !ln_g || !ln_mean || !ln_rstd || !ln_partials || ((projt == nullptr) != (dctx_out == nullptr))) return DIG_ERR_ARG;
-  if ((size_t)(R + BM) * D * 2 >= (1ull << 32)) return DIG_ERR_UNSUPPORTED;       // (row offsets of the LayerNorm phase are 32-bit)
-  if (!aligned16(pre) || !aligned16(dpre_out) || !aligned16(x_mid) || (colsum_partials && !aligned16(colsum_partials)) ||
-      (projt && (!aligned16(projt) || !aligned16(dctx_out))))
-    return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::mlp_chain_bwd_ln_proj(dy, w2t, pre, w1t, dpre_out, x_mid, ln_g, ln_mean, ln_rstd, dx_mid_out, colsum_partials, ln_partials,
+                                                projt, dctx_out, R, D, F))
+    return rc;
   ChainParams p;
   p.X = (const bf16_t*)dy; p.B1 = (const bf16_t*)w2t; p.B2 = (const bf16_t*)w1t; p.bias1 = nullptr; p.bias2 = nullptr;
   p.resid = (const bf16_t*)x_mid; p.out = (bf16_t*)dx_mid_out; p.side0 = (bf16_t*)dpre_out; p.side1 = (bf16_t*)pre; p.colsum = colsum_partials;
@@ -1209,10 +1180,7 @@ extern "C" int dig_mlp_chain_bwd_ln(const void* dy, const void* w2t, const void*
 
 extern "C" int dig_mlp_chain_bwd(const void* dy, const void* w2t, const void* pre, const void* w1t, void* dpre_out, void* dx_out,
                                  float* colsum_partials, int R, int D, int F, hipStream_t stream) {
-  const int rc = check_common(dy, w2t, w1t, dx_out, R, D, F);
-  if (rc != DIG_OK) return rc;
-  if (!pre || !dpre_out) return DIG_ERR_ARG;
-  if (!aligned16(pre) || !aligned16(dpre_out) || (colsum_partials && !aligned16(colsum_partials))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::mlp_chain_bwd(dy, w2t, pre, w1t, dpre_out, dx_out, colsum_partials, R, D, F)) return rc;
   ChainParams p;
   p.X = (const bf16_t*)dy; p.B1 = (const bf16_t*)w2t; p.B2 = (const bf16_t*)w1t; p.bias1 = nullptr; p.bias2 = nullptr;
   p.resid = nullptr; p.out = (bf16_t*)dx_out; p.side0 = (bf16_t*)dpre_out; p.side1 = (bf16_t*)pre; p.colsum = colsum_partials;
@@ -1221,12 +1189,6 @@ extern "C" int dig_mlp_chain_bwd(const void* dy, const void* w2t, const void* pr
   no_layernorm(p);
   return launch_chain<2>(p, stream);
 }
-
-// number of partial rows dig_mlp_chain_bwd_ln writes into ln_partials ([rows][3][D] fp32): one per workgroup of 128 tokens
-extern "C" int dig_mlp_chain_ln_parts(int R) { return (R + BM - 1) / BM; }
-
-// number of partial rows dig_mlp_chain_bwd writes into colsum_partials ([rows][F] fp32)
-extern "C" int dig_mlp_chain_colsum_rows(int R) { return ((R + BM - 1) / BM) * 4; }
 
 // dst[cols, rows] = src[rows, cols]^T (bf16): the K-contiguous copies of W2 / W1 the backward chain reads (1.2 MB each, once per step)
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int rows, int cols) {
@@ -1243,7 +1205,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __res
   }
 }
 // the same for a list of equally shaped matrices in ONE launch (all MLP weights of an encoder: 24 launches of ~10 us -> 1)
-#define DIG_TRANSPOSE_MAX 32
+constexpr int DIG_TRANSPOSE_MAX = dig_rules::TRANSPOSE_MAX;
 struct TransposeList { const bf16_t* src[DIG_TRANSPOSE_MAX]; bf16_t* dst[DIG_TRANSPOSE_MAX]; };
 __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(TransposeList l, int rows, int cols) {
   __shared__ bf16_t tile[64][66];
@@ -1261,17 +1223,16 @@ __global__ __launch_bounds__(256) void transpose_bf16_multi_kernel(TransposeList
   }
 }
 extern "C" int dig_transpose_bf16_multi(const void* const* srcs, void* const* dsts, int count, int rows, int cols, hipStream_t stream) {
-  if (!srcs || !dsts || count < 1 || count > DIG_TRANSPOSE_MAX || rows <= 0 || cols <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::transpose_bf16_multi(srcs, dsts, count, rows, cols)) return rc;
   TransposeList l;
   for (int k = 0; k < count; ++k) {
-    if (!srcs[k] || !dsts[k]) return DIG_ERR_ARG;
     l.src[k] = (const bf16_t*)srcs[k]; l.dst[k] = (bf16_t*)dsts[k];
   }
   hipLaunchKernelGGL(transpose_bf16_multi_kernel, dim3((cols + 63) / 64, (rows + 63) / 64, count), dim3(256), 0, stream, l, rows, cols);
   return dig_check_launch();
 }
 extern "C" int dig_transpose_bf16(const void* src, void* dst, int rows, int cols, hipStream_t stream) {
-  if (!src || !dst || rows <= 0 || cols <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::transpose_bf16(src, dst, rows, cols)) return rc;
   hipLaunchKernelGGL(transpose_bf16_kernel, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, stream, (const bf16_t*)src,
                      (bf16_t*)dst, rows, cols);
   return dig_check_launch();

@@ -392,7 +392,7 @@ __global__ void bn_running_kernel(const float* __restrict__ sums, float n, float
 // lanes x 4 column groups of 8 walks rows rl, rl + 64, ... twice -- sums (folded over the row lanes through LDS in lane order: fixed order,
 // bit-reproducible), then the apply on the second, L2-hot read of its 64 KiB slab.  Same expressions as the three-launch path; the
 // summation ORDER over rows differs (row lanes instead of strips), so the two paths agree to fp32 round-off, not bit for bit.
-constexpr int BNF_COLS = 32, BNF_LANES = 64;
+constexpr int BNF_COLS = dig_rules::BN_FUSED_COLS, BNF_LANES = 64;
 
 // MODE 0 forward: y = [relu](gamma xhat + beta), mean / rstd out, running statistics;  MODE 1 backward: dx, += dbeta / dgamma
 template <int MODE>
@@ -508,36 +508,26 @@ inline int ln_fwd_grid(int rows, bool gelu) { const int per = 4 * (gelu ? 2 : 4)
     case 256: hipLaunchKernelGGL((KERNEL<4, GELU>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); break; \
     case 384: hipLaunchKernelGGL((KERNEL<6, GELU>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); break; \
     case 512: hipLaunchKernelGGL((KERNEL<8, GELU>), dim3(grid), dim3(256), 0, stream, __VA_ARGS__); break; \
-    default: return DIG_ERR_UNSUPPORTED;                                                           \
+    default: return DIG_ERR_UNSUPPORTED; /* unreachable: abi_rules.h */                            \
   }
 
 extern "C" int dig_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                  int rows, int D, float eps, int fuse_gelu, hipStream_t stream) {
-  if (!x || !gamma || !beta || !y || !mean || !rstd || rows <= 0) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(y)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, D, eps, fuse_gelu)) return rc;
   const int grid = ln_fwd_grid(rows, fuse_gelu != 0);
   if (fuse_gelu) { LN_DISPATCH(D, true, ln_fwd_kernel, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, rows, eps) }
   else { LN_DISPATCH(D, false, ln_fwd_kernel, (const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, rows, eps) }
   return dig_check_launch();
 }
 
-extern "C" long long dig_layernorm_bwd_workspace_bytes(int rows, int D) {
-  return (long long)std::max(1, std::min(1024, (rows + 15) / 16)) * 3 * D * sizeof(float);
-}
-
 // dcolsum (nullable): receives += column sums of dres (the bias gradient of the layer that produced the skip-path sum)
-// number of partial rows ([parts][3][D] fp32) the LayerNorm backward leaves in its workspace
-extern "C" int dig_layernorm_bwd_parts(int rows) { return std::max(1, std::min(1024, (rows + 15) / 16)); }
-
 // dx only; dgamma / dbeta / dres column-sum partials stay in `workspace` for dig_layernorm_bwd_finalize (which a caller may
 // run on another stream: nothing on the data-gradient chain depends on it)
 extern "C" int dig_layernorm_bwd_partials(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
                                           const float* rstd, const void* dres, void* dx, float* workspace, int rows, int D,
                                           int fuse_gelu, hipStream_t stream) {
-  if (!dy || !x || !gamma || !mean || !rstd || !dx || !workspace || rows <= 0) return DIG_ERR_ARG;
-  if (fuse_gelu && !beta) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || (dres && !aligned16(dres))) return DIG_ERR_ALIGN;
-  const int grid = dig_layernorm_bwd_parts(rows);
+  if (int rc = dig_rules::layernorm_bwd_partials(dy, x, gamma, beta, mean, rstd, dres, dx, workspace, rows, D, fuse_gelu)) return rc;
+  const int grid = dig_rules::layernorm_bwd_parts(rows);
   if (fuse_gelu) { LN_DISPATCH(D, true, ln_bwd_kernel, (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, workspace, rows) }
   else { LN_DISPATCH(D, false, ln_bwd_kernel, (const bf16_t*)dy, (const bf16_t*)x, gamma, beta, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, workspace, rows) }
   return dig_check_launch();
@@ -545,8 +535,8 @@ extern "C" int dig_layernorm_bwd_partials(const void* dy, const void* x, const f
 
 extern "C" int dig_layernorm_bwd_finalize(const float* workspace, int rows, int D, float* dgamma, float* dbeta, float* dcolsum,
                                           hipStream_t stream) {
-  if (!workspace || !dgamma || !dbeta || rows <= 0 || D <= 0 || (D & 15)) return DIG_ERR_ARG;
-  hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((3 * D) / 16), dim3(256), 0, stream, workspace, dig_layernorm_bwd_parts(rows), D, dgamma,
+  if (int rc = dig_rules::layernorm_bwd_finalize(workspace, rows, D, dgamma, dbeta, dcolsum)) return rc;
+  hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((3 * D) / 16), dim3(256), 0, stream, workspace, dig_rules::layernorm_bwd_parts(rows), D, dgamma,
                      dbeta, dcolsum);
   return dig_check_launch();
 }
@@ -554,7 +544,7 @@ extern "C" int dig_layernorm_bwd_finalize(const float* workspace, int rows, int 
 // the same over a workspace of `parts` partial rows written by another producer (dig_mlp_chain_bwd_ln: one per 128 rows = one per workgroup, dig_mlp_chain_ln_parts)
 extern "C" int dig_layernorm_bwd_finalize_parts(const float* workspace, int parts, int D, float* dgamma, float* dbeta, float* dcolsum,
                                                 hipStream_t stream) {
-  if (!workspace || !dgamma || !dbeta || parts <= 0 || D <= 0 || (D & 15)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::layernorm_bwd_finalize_parts(workspace, parts, D, dgamma, dbeta, dcolsum)) return rc;
   hipLaunchKernelGGL(ln_bwd_finalize_kernel, dim3((3 * D) / 16), dim3(256), 0, stream, workspace, parts, D, dgamma, dbeta, dcolsum);
   return dig_check_launch();
 }
@@ -562,7 +552,7 @@ extern "C" int dig_layernorm_bwd_finalize_parts(const float* workspace, int part
 extern "C" int dig_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
                                  const float* rstd, const void* dres, void* dx, float* dgamma, float* dbeta, float* dcolsum,
                                  float* workspace, int rows, int D, int fuse_gelu, hipStream_t stream) {
-  if (!dgamma || !dbeta || (dcolsum && !dres)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::layernorm_bwd(dy, x, gamma, beta, mean, rstd, dres, dx, dgamma, dbeta, dcolsum, workspace, rows, D, fuse_gelu)) return rc;
   const int rc = dig_layernorm_bwd_partials(dy, x, gamma, beta, mean, rstd, dres, dx, workspace, rows, D, fuse_gelu, stream);
   if (rc != DIG_OK) return rc;
   return dig_layernorm_bwd_finalize(workspace, rows, D, dgamma, dbeta, dcolsum, stream);
@@ -583,8 +573,7 @@ extern "C" long long dig_bn_stats_workspace_bytes(int rows, int C) {
 
 // sums[2,C] = (sum_r x, sum_r x^2), overwritten; two-stage and deterministic
 extern "C" int dig_bn_stats(const void* x, float* sums, float* workspace, int rows, int C, hipStream_t stream) {
-  if (!x || !sums || !workspace || rows <= 0 || C <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_stats(x, sums, workspace, rows, C)) return rc;
   const int cb = bn_col_blocks(C);
   const int rpb = bn_rows_per_block(rows, C);
   const int nb = (rows + rpb - 1) / rpb;
@@ -608,10 +597,9 @@ static inline int bn_apply_grid(size_t total8, int C) {
 extern "C" int dig_bn_fwd_apply_running(const void* x, const float* sums, float n_total, float eps, const float* gamma,
                                         const float* beta, int relu, void* y, float* mean_out, float* rstd_out, float momentum,
                                         float* running_mean, float* running_var, int rows, int C, hipStream_t stream) {
-  if (!x || !sums || !y || !mean_out || !rstd_out || rows <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
-  if ((running_mean == nullptr) != (running_var == nullptr) || (running_mean && n_total <= 1.f)) return DIG_ERR_ARG;
-  if ((gamma == nullptr) != (beta == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(y) || !aligned16(sums) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_fwd_apply_running(x, sums, n_total, eps, gamma, beta, relu, y, mean_out, rstd_out, momentum, running_mean, running_var,
+                                               rows, C))
+    return rc;
   const size_t total8 = (size_t)rows * C / 8;
   const int grid = bn_apply_grid(total8, C);
   hipLaunchKernelGGL(bn_fwd_apply_kernel, dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, sums, 1.0f / n_total, eps, gamma,
@@ -628,9 +616,7 @@ extern "C" int dig_bn_fwd_apply(const void* x, const float* sums, float n_total,
 extern "C" int dig_bn_bwd_stats_acc(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                                     const float* beta, int relu, float* sums, float* dbeta_acc, float* dgamma_acc, float* workspace, int rows, int C,
                                     hipStream_t stream) {
-  if (!dy || !x || !mean || !rstd || !sums || !workspace || rows <= 0 || (C & 7)) return DIG_ERR_ARG;
-  if ((dbeta_acc == nullptr) != (dgamma_acc == nullptr)) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(dy) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_bwd_stats_acc(dy, x, mean, rstd, gamma, beta, relu, sums, dbeta_acc, dgamma_acc, workspace, rows, C)) return rc;
   const int cb = bn_col_blocks(C);
   const int rpb = bn_rows_per_block(rows, C);
   const int nb = (rows + rpb - 1) / rpb;
@@ -648,9 +634,7 @@ extern "C" int dig_bn_bwd_stats(const void* dy, const void* x, const float* mean
 extern "C" int dig_bn_bwd_apply(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, int relu, const float* sums, float n_total, void* dx, int rows, int C,
                                 hipStream_t stream) {
-  if (!dy || !x || !mean || !rstd || !sums || !dx || rows <= 0 || (C & 7) || n_total <= 0.f) return DIG_ERR_ARG;
-  if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || !aligned16(mean) || !aligned16(rstd) || !aligned16(sums) ||
-      (gamma && (!aligned16(gamma) || !aligned16(beta)))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::bn_bwd_apply(dy, x, mean, rstd, gamma, beta, relu, sums, n_total, dx, rows, C)) return rc;
   const size_t total8 = (size_t)rows * C / 8;
   const int grid = bn_apply_grid(total8, C);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, stream, (const bf16_t*)dy, (const bf16_t*)x, mean, rstd,
@@ -661,16 +645,10 @@ extern "C" int dig_bn_bwd_apply(const void* dy, const void* x, const float* mean
 
 // Few-row BatchNorm layers in ONE launch each (single rank only: with a process group the cross-rank reduction of the statistics sits between
 // dig_bn_stats and dig_bn_fwd_apply).  rows <= 4096, C a multiple of 32, at least 32 column slabs.
-extern "C" int dig_bn_fused_supported(int rows, int C) { return rows >= 2 && rows <= 4096 && C >= 256 && (C % BNF_COLS) == 0; }
-
 extern "C" int dig_bn_fwd_fused(const void* x, float eps, const float* gamma, const float* beta, int relu, void* y, float* mean_out,
                                 float* rstd_out, float momentum, float* running_mean, float* running_var, int rows, int C, hipStream_t stream) {
-  if (!x || !y || !mean_out || !rstd_out || (gamma == nullptr) != (beta == nullptr) || (running_mean == nullptr) != (running_var == nullptr))
-    return DIG_ERR_ARG;
-  if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::bn_fwd_fused(x, eps, gamma, beta, relu, y, mean_out, rstd_out, momentum, running_mean, running_var, rows, C)) return rc;
   // gamma / beta are read with 16-byte loads (load8f); the statistics and running vectors are held to the three-launch path's rule
-  if (!aligned16(x) || !aligned16(y) || !aligned16(mean_out) || !aligned16(rstd_out) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
-      (running_mean && (!aligned16(running_mean) || !aligned16(running_var)))) return DIG_ERR_ALIGN;
   hipLaunchKernelGGL(bn_fused_kernel<0>, dim3(C / BNF_COLS), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, gamma, beta, relu, eps, (bf16_t*)y, mean_out, rstd_out, momentum, running_mean, running_var,
                      (float*)nullptr, (float*)nullptr, rows, C);
@@ -679,11 +657,7 @@ extern "C" int dig_bn_fwd_fused(const void* x, float eps, const float* gamma, co
 
 extern "C" int dig_bn_bwd_fused(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                 int relu, float* dbeta_acc, float* dgamma_acc, void* dx, int rows, int C, hipStream_t stream) {
-  if (!dy || !x || !mean || !rstd || !dx || (gamma == nullptr) != (beta == nullptr) || (dbeta_acc == nullptr) != (dgamma_acc == nullptr))
-    return DIG_ERR_ARG;
-  if (!dig_bn_fused_supported(rows, C)) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(x) || !aligned16(dy) || !aligned16(dx) || !aligned16(mean) || !aligned16(rstd) || (gamma && (!aligned16(gamma) || !aligned16(beta))) ||
-      (dbeta_acc && (!aligned16(dbeta_acc) || !aligned16(dgamma_acc)))) return DIG_ERR_ALIGN;   // mean / rstd / gamma / beta: 16-byte loads (load8f)
+  if (int rc = dig_rules::bn_bwd_fused(dy, x, mean, rstd, gamma, beta, relu, dbeta_acc, dgamma_acc, dx, rows, C)) return rc;
   hipLaunchKernelGGL(bn_fused_kernel<1>, dim3(C / BNF_COLS), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, mean, rstd, gamma, beta,
                      relu, 0.f, (bf16_t*)dx, (float*)nullptr, (float*)nullptr, 0.f, (float*)nullptr, (float*)nullptr, dbeta_acc, dgamma_acc, rows, C);
   return dig_check_launch();
@@ -691,7 +665,7 @@ extern "C" int dig_bn_bwd_fused(const void* dy, const void* x, const float* mean
 
 extern "C" int dig_bn_update_running(const float* sums, float n_total, float momentum, float* running_mean, float* running_var,
                                      int C, hipStream_t stream) {
-  if (!sums || !running_mean || !running_var || C <= 0 || n_total <= 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::bn_update_running(sums, n_total, momentum, running_mean, running_var, C)) return rc;
   hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, sums, n_total, momentum, running_mean, running_var, C);
   return dig_check_launch();
 }

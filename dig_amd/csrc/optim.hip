@@ -228,8 +228,8 @@ inline int flat_grid(long long n4) { return (int)std::min<long long>(4096, (n4 +
 extern "C" int dig_adamw_step(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n,
                               const unsigned char* group_flags, float lr0, float wd0, float lr1, float wd1, float beta1,
                               float beta2, float eps, int step, float grad_scale, const float* finite_gate, hipStream_t stream) {
-  if (!p || !g || !m || !v || !group_flags || n <= 0 || (n & 255) || step < 1) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step(p, g, m, v, bf16_shadow, n, group_flags, lr0, wd0, lr1, wd1, beta1, beta2, eps, step, grad_scale, finite_gate))
+    return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adamw_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)bf16_shadow, n / 4,
@@ -244,9 +244,9 @@ extern "C" int dig_adamw_step_tr(float* p, const float* g, float* m, float* v, v
                                  const unsigned char* group_flags, float lr0, float wd0, float lr1, float wd1, float beta1,
                                  float beta2, float eps, int step, float grad_scale, const float* finite_gate, const void* mats, int n_mats,
                                  int n_tiles, void* tr_out, hipStream_t stream) {
-  if (!p || !g || !m || !v || !group_flags || n <= 0 || (n & 255) || step < 1 || !mats || n_mats < 1 || n_tiles < 1 || !tr_out) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7)) || (((uintptr_t)tr_out) & 7))
-    return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_tr(p, g, m, v, bf16_shadow, n, group_flags, lr0, wd0, lr1, wd1, beta1, beta2, eps, step, grad_scale,
+                                        finite_gate, mats, n_mats, n_tiles, tr_out))
+    return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const int fb = flat_grid(n / 4);
@@ -257,7 +257,7 @@ extern "C" int dig_adamw_step_tr(float* p, const float* g, float* m, float* v, v
 }
 
 extern "C" int dig_adamw_bias_corrections(float beta1, float beta2, int step, float* out2) {
-  if (!out2 || step < 1) return DIG_ERR_ARG;
+  if (int rc = dig_rules::adamw_bias_corrections(beta1, beta2, step, out2)) return rc;
   out2[0] = (float)(1.0 / (1.0 - pow((double)beta1, (double)step)));
   out2[1] = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
   return DIG_OK;
@@ -266,8 +266,7 @@ extern "C" int dig_adamw_bias_corrections(float beta1, float beta2, int step, fl
 extern "C" int dig_adamw_step_dev(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n,
                                   const unsigned char* group_flags, const float* scalars6, float beta1, float beta2, float eps,
                                   float grad_scale, const float* finite_gate, hipStream_t stream) {
-  if (!p || !g || !m || !v || !group_flags || !scalars6 || n <= 0 || (n & 255)) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_dev(p, g, m, v, bf16_shadow, n, group_flags, scalars6, beta1, beta2, eps, grad_scale, finite_gate)) return rc;
   hipLaunchKernelGGL(adamw_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)bf16_shadow, n / 4,
                      group_flags, 0.f, 0.f, 0.f, 0.f, beta1, beta2, eps, 1.f, 1.f, grad_scale, finite_gate, scalars6, (const AdamTrMat*)nullptr, 0,
                      (bf16_t*)nullptr, 0);
@@ -277,8 +276,8 @@ extern "C" int dig_adamw_step_dev(float* p, const float* g, float* m, float* v, 
 extern "C" int dig_adamw_step_groups(float* p, const float* g, float* m, float* v, void* bf16_shadow, long long n,
                                      const unsigned char* group_idx, const float* lr_tab, const float* wd_tab, float beta1, float beta2,
                                      float eps, int step, float grad_scale, const float* finite_gate, hipStream_t stream) {
-  if (!p || !g || !m || !v || !group_idx || !lr_tab || !wd_tab || n <= 0 || (n & 255) || step < 1) return DIG_ERR_ARG;
-  if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::adamw_step_groups(p, g, m, v, bf16_shadow, n, group_idx, lr_tab, wd_tab, beta1, beta2, eps, step, grad_scale, finite_gate))
+    return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adamw_groups_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)bf16_shadow, n / 4, group_idx,
@@ -287,8 +286,7 @@ extern "C" int dig_adamw_step_groups(float* p, const float* g, float* m, float* 
 }
 
 extern "C" int dig_ema_update(float* pm, const float* p, void* bf16_shadow, long long n, float m, hipStream_t stream) {
-  if (!pm || !p || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(pm) || !aligned16(p) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::ema_update(pm, p, bf16_shadow, n, m)) return rc;
   hipLaunchKernelGGL(ema_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, pm, p, (bf16_t*)bf16_shadow, n / 4, m,
                      (float)(1.0 - (double)m), (const float*)nullptr);
   return dig_check_launch();
@@ -296,18 +294,14 @@ extern "C" int dig_ema_update(float* pm, const float* p, void* bf16_shadow, long
 
 extern "C" int dig_ema_update_dev(float* pm, const float* p, void* bf16_shadow, long long n, const float* m_and_one_minus_m,
                                   hipStream_t stream) {
-  if (!pm || !p || !m_and_one_minus_m || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(pm) || !aligned16(p) || (bf16_shadow && (((uintptr_t)bf16_shadow) & 7))) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::ema_update_dev(pm, p, bf16_shadow, n, m_and_one_minus_m)) return rc;
   hipLaunchKernelGGL(ema_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, pm, p, (bf16_t*)bf16_shadow, n / 4, 0.f, 0.f,
                      m_and_one_minus_m);
   return dig_check_launch();
 }
 
-extern "C" long long dig_sumsq_workspace_bytes(long long n) { return 1024 * sizeof(float); }
-
 extern "C" int dig_sumsq(const float* x, long long n, float* workspace, float* out, hipStream_t stream) {
-  if (!x || !workspace || !out || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::sumsq(x, n, workspace, out)) return rc;
   const int grid = (int)std::min<long long>(1024, (n / 4 + 255) / 256);
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(grid), dim3(256), 0, stream, x, n / 4, workspace);
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, workspace, grid, out);
@@ -315,41 +309,37 @@ extern "C" int dig_sumsq(const float* x, long long n, float* workspace, float* o
 }
 
 extern "C" int dig_cast_f32_to_bf16(const float* x, void* y, long long n, hipStream_t stream) {
-  if (!x || !y || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x) || (((uintptr_t)y) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::cast_f32_to_bf16(x, y, n)) return rc;
   hipLaunchKernelGGL(cast_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, x, (bf16_t*)y, n / 4);
   return dig_check_launch();
 }
 
 extern "C" int dig_cast_bf16_to_f32(const void* x, float* y, long long n, hipStream_t stream) {
-  if (!x || !y || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(y) || (((uintptr_t)x) & 7)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::cast_bf16_to_f32(x, y, n)) return rc;
   hipLaunchKernelGGL(cast_back_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, (const bf16_t*)x, y, n / 4);
   return dig_check_launch();
 }
 
 extern "C" int dig_scale_f32(float* x, long long n, float s, hipStream_t stream) {
-  if (!x || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::scale_f32(x, n, s)) return rc;
   hipLaunchKernelGGL(scale_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, x, n / 4, s);
   return dig_check_launch();
 }
 
 extern "C" int dig_fill_f32(float* x, long long n, float value, hipStream_t stream) {
-  if (!x || n <= 0 || (n & 3)) return DIG_ERR_ARG;
-  if (!aligned16(x)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::fill_f32(x, n, value)) return rc;
   hipLaunchKernelGGL(fill_kernel, dim3(flat_grid(n / 4)), dim3(256), 0, stream, x, n / 4, value);
   return dig_check_launch();
 }
 
 extern "C" int dig_scale_by_device_scalar(float* x, long long n, const float* scalar, float extra, hipStream_t stream) {
-  if (!x || !scalar || n <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::scale_by_device_scalar(x, n, scalar, extra)) return rc;
   hipLaunchKernelGGL(scale_dev_kernel, dim3(flat_grid((n + 3) / 4)), dim3(256), 0, stream, x, n, scalar, extra);
   return dig_check_launch();
 }
 
 extern "C" int dig_pad_cast_rows(const float* src, void* dst, int M, int C, int M_pad, int ld, hipStream_t stream) {
-  if (!src || !dst || M <= 0 || C <= 0 || M_pad < M || ld < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::pad_cast_rows(src, dst, M, C, M_pad, ld)) return rc;
   hipLaunchKernelGGL(pad_cast_kernel, dim3(flat_grid(((long long)M_pad * ld + 3) / 4)), dim3(256), 0, stream, src, (bf16_t*)dst, M, C, M_pad, ld);
   return dig_check_launch();
 }
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const 
 }  // namespace
 
 extern "C" int dig_axpy_f32(float* y, const float* x, long long n, float a, hipStream_t stream) {
-  if (!y || !x || n <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::axpy_f32(y, x, n, a)) return rc;
   hipLaunchKernelGGL(axpy_kernel, dim3(flat_grid((n + 3) / 4)), dim3(256), 0, stream, y, x, n, a);
   return dig_check_launch();
 }

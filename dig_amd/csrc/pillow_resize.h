@@ -15,6 +15,8 @@
 
 #include <cmath>
 
+#include "abi_rules.h"
+
 namespace dig_pillow {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
@@ -58,12 +60,7 @@ DIG_HD inline int clip8(int v) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// taps per output index of one axis for inputs up to in_size
-inline int ksize_for(int in_size, int out_size) {
-  double fs = (double)in_size / out_size;
-  if (fs < 1.0) fs = 1.0;
-  return (int)std::ceil(2.0 * fs) * 2 + 1;
-}
+using dig_rules::ksize_for;   // taps per output index of one axis for inputs up to in_size (abi_rules.h: the LDS rules need it too)
 
 // the three channels of output pixel (yy, xx) of an HWC uint8 image (h x w at src): the horizontal pass is evaluated on the fly for the
 // rows the vertical window needs (an 8-bit intermediate exactly as Pillow's).  kh / bh: [out_w][ksh] / [out_w][2], kv / bv: [out_h][ksv] /

@@ -17,7 +17,7 @@
 namespace {
 
 template <int DK> constexpr int KROW = DK + 2;   // bf16 elements per K / V row in LDS: an odd dword stride at every head dim (13, 25, 33), so consecutive rows hit different banks
-constexpr int MAXQ = 32;
+constexpr int MAXQ = dig_rules::SEQ_ATTN_MAX_LQ;
 
 struct SeqAttnParams {
   const bf16_t *q, *k, *v;
@@ -407,9 +407,7 @@ int launch_bwd(const SeqAttnParams& p, const void* dout, int ldo, const float* l
 extern "C" int dig_seq_attn_fwd_hd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* out, int ldo, float* lse, int B,
                                    int heads, int Lq, int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop,
                                    int head_dim, hipStream_t stream) {
-  if (!q || !k || !v || !out || !lse || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
+  if (int rc = dig_rules::seq_attn_fwd_hd(q, ldq, k, ldk, v, ldv, out, ldo, lse, B, heads, Lq, Lk, scale, causal, lens, drop, head_dim)) return rc;
   SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
   if (head_dim == 24) return launch_fwd<24>(p, out, ldo, lse, B, heads, stream);
   if (head_dim == 48) return launch_fwd<48>(p, out, ldo, lse, B, heads, stream);
@@ -431,11 +429,9 @@ extern "C" int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ld
                                    const float* lse, void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int heads, int Lq,
                                    int Lk, float scale, int causal, const long long* lens, const dig_dropout_t* drop, int head_dim,
                                    hipStream_t stream) {
-  if (!q || !k || !v || !dout || !lse || !dq || !dk || !dv || B <= 0 || heads <= 0 || Lq <= 0 || Lq > MAXQ || Lk <= 0 || Lk > 512) return DIG_ERR_ARG;
-  if (head_dim != 24 && head_dim != 48 && head_dim != 64) return DIG_ERR_UNSUPPORTED;
-  if (256 * head_dim + Lk * (256 + 2 * head_dim) > DIG_SEQ_ATTN_BWD_LDS_LIMIT) return DIG_ERR_UNSUPPORTED;   // lds_bwd: Lk <= 384 / 430 / 512 at head dim 64 / 48 / 24
-  if ((ldk & 7) || (ldv & 7) || !aligned16(k) || !aligned16(v)) return DIG_ERR_ALIGN;   // 16-byte row reads
-  if ((lddk & 7) || (lddv & 7) || !aligned16(dk) || !aligned16(dv)) return DIG_ERR_ALIGN;   // 16-byte dK / dV row stores, on both paths
+  if (int rc = dig_rules::seq_attn_bwd_hd(q, ldq, k, ldk, v, ldv, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, Lq, Lk, scale, causal,
+                                          lens, drop, head_dim))
+    return rc;
   SeqAttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, Lq, Lk, scale, causal, lens, drop ? *drop : dig_dropout_t{}};
   if (head_dim == 24) return launch_bwd<24>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
   if (head_dim == 48) return launch_bwd<48>(p, dout, ldo, lse, dq, lddq, dk, lddk, dv, lddv, B, heads, stream);
@@ -459,7 +455,7 @@ extern "C" int dig_seq_attn_bwd(const void* q, int ldq, const void* k, int ldk, 
 
 extern "C" int dig_seq_embed_fwd(const long long* tokens, const float* emb, const float* pos_table, void* x, int B, int T, int d, int vocab,
                                  hipStream_t stream) {
-  if (!tokens || !emb || !pos_table || !x || B <= 0 || T <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_embed_fwd(tokens, emb, pos_table, x, B, T, d, vocab)) return rc;
   const size_t n = (size_t)B * T * d;
   hipLaunchKernelGGL(seq_embed_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tokens, emb, pos_table, (bf16_t*)x, B * T, T, d, vocab);
   return dig_check_launch();
@@ -467,9 +463,7 @@ extern "C" int dig_seq_embed_fwd(const long long* tokens, const float* emb, cons
 
 extern "C" int dig_seq_embed_bwd_lens(const long long* tokens, const void* dx, float* demb, int n_tok, int d, int vocab, int T,
                                       const long long* lens, hipStream_t stream) {
-  if (!tokens || !dx || !demb || n_tok <= 0 || d <= 0 || vocab <= 0) return DIG_ERR_ARG;
-  if (lens && (T <= 0 || n_tok % T)) return DIG_ERR_ARG;
-  if ((size_t)n_tok * sizeof(int) > 60 * 1024) return DIG_ERR_UNSUPPORTED;
+  if (int rc = dig_rules::seq_embed_bwd_lens(tokens, dx, demb, n_tok, d, vocab, T, lens)) return rc;
   hipLaunchKernelGGL(seq_embed_bwd_kernel, dim3(vocab, (d + 255) / 256), dim3(256), (size_t)n_tok * sizeof(int), stream, tokens,
                      (const bf16_t*)dx, demb, n_tok, d, T > 0 ? T : 1, lens);
   return dig_check_launch();

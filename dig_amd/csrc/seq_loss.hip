@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64) void seq_ls_ce_bwd_kernel(const float* __restri
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_seq_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C,
                                      float* row_workspace, float* loss, hipStream_t stream) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_cross_entropy(input, target, length, B, T, C, row_workspace, loss)) return rc;
   hipLaunchKernelGGL(seq_ce_rows_kernel, dim3(B * T), dim3(64), 0, stream, input, target, length, T, C, row_workspace);
   hipLaunchKernelGGL(fixed_order_sum_kernel, dim3(1), dim3(256), 0, stream, row_workspace, B * T, 1.0f / (float)B, loss);
   return dig_check_launch();
@@ -135,7 +135,7 @@ extern "C" int dig_seq_cross_entropy(const float* input, const long long* target
 
 extern "C" int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar,
                                          int B, int T, int C, void* dlogits, int ldd, hipStream_t stream) {
-  if (!logits || !target || !length || !dlogits || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_cross_entropy_bwd(logits, ld, target, length, gscalar, B, T, C, dlogits, ldd)) return rc;
   hipLaunchKernelGGL(seq_ce_bwd_kernel, dim3(B * T), dim3(64), 0, stream, logits, ld, target, length, gscalar, T, C, 1.0f / (float)B,
                      (bf16_t*)dlogits, ldd);
   return dig_check_launch();
@@ -143,7 +143,7 @@ extern "C" int dig_seq_cross_entropy_bwd(const float* logits, int ld, const long
 
 extern "C" int dig_seq_ls_cross_entropy(const float* input, const long long* target, const long long* length, int B, int T, int C,
                                         float smoothing, float* row_workspace, float* loss, hipStream_t stream) {
-  if (!input || !target || !length || !row_workspace || !loss || B <= 0 || T <= 0 || C <= 0 || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_ls_cross_entropy(input, target, length, B, T, C, smoothing, row_workspace, loss)) return rc;
   hipLaunchKernelGGL(seq_ls_ce_rows_kernel, dim3(B * T), dim3(64), 0, stream, input, target, length, T, C, row_workspace);
   hipLaunchKernelGGL(seq_ls_ce_sum_kernel, dim3(1), dim3(256), 0, stream, row_workspace, length, B, T, 1.f - smoothing, smoothing, loss);
   return dig_check_launch();
@@ -151,7 +151,7 @@ extern "C" int dig_seq_ls_cross_entropy(const float* input, const long long* tar
 
 extern "C" int dig_seq_ls_cross_entropy_bwd(const float* logits, int ld, const long long* target, const long long* length, const float* gscalar,
                                             int B, int T, int C, float smoothing, void* dlogits, int ldd, hipStream_t stream) {
-  if (!logits || !target || !length || !dlogits || B <= 0 || T <= 0 || C <= 0 || ld < C || ldd < C || smoothing < 0.f || smoothing > 1.f) return DIG_ERR_ARG;
+  if (int rc = dig_rules::seq_ls_cross_entropy_bwd(logits, ld, target, length, gscalar, B, T, C, smoothing, dlogits, ldd)) return rc;
   hipLaunchKernelGGL(seq_ls_ce_bwd_kernel, dim3(B * T), dim3(64), 0, stream, logits, ld, target, length, gscalar, B, T, C, 1.f - smoothing,
                      smoothing, (bf16_t*)dlogits, ldd);
   return dig_check_launch();

@@ -19,8 +19,8 @@
 
 namespace {
 
-constexpr int TCV_MAXN = 256;
-constexpr int TCV_MAXQ = 32;
+using dig_rules::TCV_MAXN;
+using dig_rules::TCV_MAXQ;
 constexpr int TCV_KEYS = 8;                    // keys per workgroup of the key-owning backward (two per wave)
 
 struct TcvParams {
@@ -373,24 +373,13 @@ __global__ __launch_bounds__(64) void tcv_fold_kernel(const float* __restrict__ 
   else out_b[col - d] += tot;
 }
 
-int tcv_check(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, int S, int Lq, int N, int heads,
-              int d, int spm) {
-  if (!film || !u || !vk || !mem || !lnc_g || !lnc_b || S <= 0 || Lq <= 0 || N <= 0 || spm <= 0 || S % spm) return DIG_ERR_ARG;
-  if ((d != 128 && d != 384 && d != 512) || heads != d / 64 || N > TCV_MAXN || Lq > TCV_MAXQ) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(film) || !aligned16(u) || !aligned16(vk) || !aligned16(mem)) return DIG_ERR_ALIGN;
-  return DIG_OK;
-}
-
 }  // namespace
 
 // C-ABI: see include/dig_hip.h
 extern "C" int dig_tcv_attn_fwd(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, float eps,
                                 void* c, float* lse, float* wmean, int S, int Lq, int N, int heads, int d, int slots_per_mem,
                                 const dig_dropout_t* drop, hipStream_t stream) {
-  if (!c || !lse) return DIG_ERR_ARG;
-  const int rc = tcv_check(film, u, vk, mem, lnc_g, lnc_b, S, Lq, N, heads, d, slots_per_mem);
-  if (rc) return rc;
-  if (!aligned16(c)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::tcv_attn_fwd(film, u, vk, mem, lnc_g, lnc_b, eps, c, lse, wmean, S, Lq, N, heads, d, slots_per_mem, drop)) return rc;
   TcvParams p{(const bf16_t*)film, (const bf16_t*)u, (const bf16_t*)vk, (const bf16_t*)mem, lnc_g, lnc_b, eps, S, Lq, N, slots_per_mem,
               drop ? *drop : dig_dropout_t{}};
   // consecutive workgroups = the queries of one sequence, then the slots of one memory: they re-read its vk / mem rows from L2 together
@@ -405,11 +394,9 @@ extern "C" int dig_tcv_attn_bwd(const void* film, const void* u, const void* vk,
                                 const void* c, const float* lse, const void* dc, void* du, void* dfilm, void* dvk, void* dmem, float* dlnc_g,
                                 float* dlnc_b, float* workspace, int S, int Lq, int N, int heads, int d, int slots_per_mem,
                                 const dig_dropout_t* drop, hipStream_t stream) {
-  if (!c || !lse || !dc || !du || !dfilm || !dvk || !dmem || !dlnc_g || !dlnc_b || !workspace) return DIG_ERR_ARG;
-  const int rc = tcv_check(film, u, vk, mem, lnc_g, lnc_b, S, Lq, N, heads, d, slots_per_mem);
-  if (rc) return rc;
-  if (slots_per_mem != 1) return DIG_ERR_UNSUPPORTED;
-  if (!aligned16(c) || !aligned16(dc) || !aligned16(du) || !aligned16(dfilm) || !aligned16(dvk) || !aligned16(dmem)) return DIG_ERR_ALIGN;
+  if (int rc = dig_rules::tcv_attn_bwd(film, u, vk, mem, lnc_g, lnc_b, eps, c, lse, dc, du, dfilm, dvk, dmem, dlnc_g, dlnc_b, workspace, S, Lq, N,
+                                       heads, d, slots_per_mem, drop))
+    return rc;
   TcvParams p{(const bf16_t*)film, (const bf16_t*)u, (const bf16_t*)vk, (const bf16_t*)mem, lnc_g, lnc_b, eps, S, Lq, N, 1,
               drop ? *drop : dig_dropout_t{}};
   const int R = S * Lq;

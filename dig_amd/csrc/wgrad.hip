@@ -483,126 +483,36 @@ int launch_wgrad(const WgParams& p, int n_wg, hipStream_t stream) {
   return dig_check_launch();
 }
 
-int fill_probs(const dig_wgrad_prob_t* in, int n, int fn, int wa, WgProb* out, int* tiles_out) {
+int fill_probs(const dig_wgrad_prob_t* in, int n, int fn, int wa, WgProb* out) {   // returns the table's tile count
   int tiles = 0;
   const int TJ = 128 * fn, TI = 128 * wa;
   for (int k = 0; k < n; ++k) {
     const dig_wgrad_prob_t& q = in[k];
-    if (!q.out || q.I <= 0 || q.J <= 0 || (q.I % 128) || (q.J % TJ)) return DIG_ERR_ARG;
-    if ((q.ldo & 3) || !aligned16(q.out)) return DIG_ERR_ALIGN;
     out[k].A = (const bf16_t*)q.A; out[k].B = (const bf16_t*)q.B; out[k].out = q.out;
     out[k].lda = q.lda; out[k].ldb = q.ldb; out[k].ldo = q.ldo; out[k].I = q.I; out[k].J = q.J; out[k].trans_out = q.trans_out;
     out[k].tile0 = tiles;
     tiles += ((q.I + TI - 1) / TI) * (q.J / TJ);
   }
-  *tiles_out = tiles;
-  return DIG_OK;
+  return tiles;
 }
 
 }  // namespace
 
-// C-ABI: see include/dig_hip.h
-extern "C" int dig_wgrad_group_supported(int I, int J, int R) {
-  // (operands are addressed through 32-bit buffer offsets: R rows of at least I / J columns each must stay below 4 GiB -- the launcher
-  //  checks the real leading dimensions again)
-  return (I > 0 && J > 0 && R >= 64 && I % 128 == 0 && (J % 384 == 0 || J % 256 == 0) && R % 64 == 0 &&
-          (unsigned long long)R * (unsigned)I * 2ull < (1ull << 32) && (unsigned long long)R * (unsigned)J * 2ull < (1ull << 32)) ? 1 : 0;
-}
-extern "C" int dig_wgrad_group_fn(int J) { return J % 384 == 0 ? 3 : (J % 256 == 0 ? 2 : 0); }
-
-// rows per R-split for a requested split count (whole groups of four 16-row stages), and the split count that results
-extern "C" int dig_wgrad_group_rows_per_split(int R, int splits) {
-  if (R <= 0 || splits < 1 || R % 64) return 0;
-  return ((R / 64 + splits - 1) / splits) * 64;
-}
-extern "C" int dig_wgrad_group_effective_splits(int R, int splits) {
-  const int per = dig_wgrad_group_rows_per_split(R, splits);
-  return per ? (R + per - 1) / per : 0;
-}
-extern "C" long long dig_wgrad_group_slab_bytes(int total_tiles, int splits, int fn, int wa) {
-  return (long long)total_tiles * splits * 128 * wa * 128 * fn * 4;
-}
-// tiles of one problem: wa = 1: 128 x 128 fn (4 waves, two workgroups per CU);  wa = 2: 256 x 128 fn (8 waves, one workgroup per CU)
-extern "C" int dig_wgrad_group_tiles(int I, int J, int fn, int wa) {
-  if (I <= 0 || J <= 0 || (fn != 2 && fn != 3) || (wa != 1 && wa != 2) || (I % 128) || (J % (128 * fn))) return 0;
-  return ((I + 128 * wa - 1) / (128 * wa)) * (J / (128 * fn));
-}
-
-// Workgroup table of one launch (host memory in, host memory out): tiles_per_prob[n_probs] tiles x S R-splits, the tiles of one
-// (problem, split) pair on one XCD, the eight XCDs loaded evenly.  S = the largest split count <= max_wg / tiles (whole groups of
-// four 16-row stages per split) whose table fits max_wg workgroups (one round at two workgroups per CU: 512 on MI355X); *splits_out
-// receives it.  map_out[n_wg] entries: tile | split << 16, or 0xffffffff (a workgroup that only takes part in the fold).
-// Returns n_wg (a multiple of 8, <= max_out) or a negative error.
-extern "C" int dig_wgrad_group_plan(const int* tiles_per_prob, int n_probs, int R, int max_wg, int* splits_out, unsigned* map_out,
-                                    int max_out) {
-  if (!tiles_per_prob || !map_out || !splits_out || n_probs < 1 || n_probs > DIG_WGRAD_MAX_PROBS || R < 64 || (R % 64) || max_wg < 8) return DIG_ERR_ARG;
-  int tiles = 0;
-  for (int k = 0; k < n_probs; ++k) {
-    if (tiles_per_prob[k] < 1) return DIG_ERR_ARG;
-    tiles += tiles_per_prob[k];
-  }
-  if (tiles > 65535) return DIG_ERR_ARG;
-  struct Grp { int tile0, n, split; };
-  int last_eff = -1;
-  for (int want = std::max(1, std::min(max_wg / tiles, R / 64));; --want) {
-    const int S = dig_wgrad_group_effective_splits(R, want);
-    if (S == last_eff && want > 1) continue;
-    last_eff = S;
-    std::vector<Grp> groups;
-    int tile0 = 0;
-    for (int k = 0; k < n_probs; ++k) {
-      for (int s = 0; s < S; ++s) groups.push_back({tile0, tiles_per_prob[k], s});
-      tile0 += tiles_per_prob[k];
-    }
-    std::stable_sort(groups.begin(), groups.end(), [](const Grp& a, const Grp& b) { return a.n > b.n; });
-    std::vector<unsigned> bins[8];
-    for (const Grp& g : groups) {
-      int best = 0;
-      for (int x = 1; x < 8; ++x)
-        if (bins[x].size() < bins[best].size()) best = x;
-      for (int t = 0; t < g.n; ++t) bins[best].push_back((unsigned)(g.tile0 + t) | ((unsigned)g.split << 16));
-    }
-    size_t len = 0;
-    for (int x = 0; x < 8; ++x) len = std::max(len, bins[x].size());
-    if ((long long)len * 8 > max_wg && want > 1) continue;
-    if ((long long)len * 8 > max_out || S > 65535) return DIG_ERR_ARG;
-    for (size_t k = 0; k < len; ++k)
-      for (int x = 0; x < 8; ++x) map_out[k * 8 + x] = k < bins[x].size() ? bins[x][k] : WG_NONE;
-    *splits_out = S;
-    return (int)(len * 8);
-  }
-}
-
+// C-ABI: see include/dig_hip.h (the planning queries of this launch: abi_queries.inc)
 // One launch: fold the previous launch's slabs (fold_probs / fold_slabs / fold_splits; n_fold = 0: nothing pending) into their
 // gradients, then the partial products of `probs` into `slabs` ([total_tiles][splits] slabs of 128 wa x 128 fn floats).  n_probs = 0:
 // fold only (wg_map may be null; n_wg workgroups share the fold).  All problems of a launch share R, splits and fn.
 extern "C" int dig_wgrad_group(const dig_wgrad_prob_t* probs, int n_probs, const dig_wgrad_prob_t* fold_probs, int n_fold, int R,
                                int splits, const unsigned* wg_map, int n_wg, float* slabs, const float* fold_slabs, int fold_splits,
                                int fn, int wa, hipStream_t stream) {
-  if (n_probs < 0 || n_probs > DIG_WGRAD_MAX_PROBS || n_fold < 0 || n_fold > DIG_WGRAD_MAX_PROBS || (n_probs == 0 && n_fold == 0)) return DIG_ERR_ARG;
-  if ((fn != 2 && fn != 3) || (wa != 1 && wa != 2)) return DIG_ERR_UNSUPPORTED;
-  if (n_wg < 1 || (n_probs > 0 && (!probs || !wg_map || !slabs || R < 64 || (R % 64) || splits < 1))) return DIG_ERR_ARG;
-  if (n_fold > 0 && (!fold_probs || !fold_slabs || fold_splits < 1)) return DIG_ERR_ARG;
+  if (int rc = dig_rules::wgrad_group(probs, n_probs, fold_probs, n_fold, R, splits, wg_map, n_wg, slabs, fold_slabs, fold_splits, fn, wa)) return rc;
   WgParams p{};
-  int tiles = 0, ftiles = 0;
-  int rc = n_probs ? fill_probs(probs, n_probs, fn, wa, p.prob, &tiles) : DIG_OK;
-  if (rc) return rc;
-  rc = n_fold ? fill_probs(fold_probs, n_fold, fn, wa, p.fold, &ftiles) : DIG_OK;
-  if (rc) return rc;
-  for (int k = 0; k < n_probs; ++k) {
-    const WgProb& q = p.prob[k];
-    if (!q.A || !q.B) return DIG_ERR_ARG;
-    if (!aligned16(q.A) || !aligned16(q.B) || (q.lda & 7) || (q.ldb & 7) || q.lda < q.I || q.ldb < q.J) return DIG_ERR_ALIGN;
-    if ((size_t)R * q.lda * 2 >= (1ull << 32) || (size_t)R * q.ldb * 2 >= (1ull << 32)) return DIG_ERR_UNSUPPORTED;
-  }
+  if (n_probs) fill_probs(probs, n_probs, fn, wa, p.prob);
   p.n_prob = n_probs; p.n_fold = n_fold;
   p.R = R; p.splits = splits;
-  p.r_per_split = n_probs ? dig_wgrad_group_rows_per_split(R, splits) : 64;
-  if (n_probs && dig_wgrad_group_effective_splits(R, splits) != splits) return DIG_ERR_ARG;
-  p.fold_splits = fold_splits; p.fold_tiles = ftiles;
+  p.r_per_split = n_probs ? dig_rules::wgrad_group_rows_per_split(R, splits) : 64;
+  p.fold_splits = fold_splits; p.fold_tiles = n_fold ? fill_probs(fold_probs, n_fold, fn, wa, p.fold) : 0;
   p.slabs = slabs; p.fold_slabs = fold_slabs; p.wg_map = wg_map;
-  if (n_probs && !aligned16(slabs)) return DIG_ERR_ALIGN;
-  if (n_fold && !aligned16(fold_slabs)) return DIG_ERR_ALIGN;
   if (wa == 2) return fn == 3 ? launch_wgrad_wide<3, 7>(p, n_wg, stream) : launch_wgrad_wide<2, 8>(p, n_wg, stream);
   return fn == 3 ? launch_wgrad<3>(p, n_wg, stream) : launch_wgrad<2>(p, n_wg, stream);
 }

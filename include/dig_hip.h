@@ -242,7 +242,7 @@ int dig_layernorm_bwd_finalize_parts(const float* workspace, int parts, int D, f
 /* ------------------------------------------------------------------------------------------------------------------
  * BatchNorm1d in training mode, split so that the [2,C] statistics vector can be all-reduced between the halves
  * (nn.BatchNorm1d in _build_mlp, modeling_pretrain_moco_mim_ori.py:463-482, under SyncBatchNorm,
- * run_mae_pretraining_moco.py:390).  x, y, dy, dx: bf16 [rows, C], C % 8 == 0.
+ * run_mae_pretraining_moco.py:390).  x, y, dy, dx: bf16 [rows, C], C > 0 and C % 8 == 0 (DIG_ERR_ARG otherwise, before anything is launched).
  *   dig_bn_stats:      sums[0][c] = sum_r x, sums[1][c] = sum_r x^2   (two-stage, deterministic; workspace from
  *                      dig_bn_stats_workspace_bytes, also used by dig_bn_bwd_stats)
  *   dig_bn_fwd_apply:  mean/var from sums / n_total (biased var); y = [relu](gamma * xhat + beta); gamma == beta == NULL
