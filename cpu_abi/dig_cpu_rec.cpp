@@ -985,6 +985,70 @@ int dig_ctc_loss_bwd(const float* logits, int ld, const long long* target, int l
   return DIG_OK;
 }
 
+// Forced alignment, the rule of include/dig_hip.h as written: v [T][S] in double over the double log-softmax, one choice per cell (0 stay,
+// 1 step, 2 skip: the number of states the back-trace moves down), a later predecessor taken only when strictly larger.
+int dig_ctc_align(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
+                  int C, int blank, int* start, int* end, float* char_logp, float* path_logp, int* frame_label, hipStream_t) {
+  if (int rc = dig_rules::ctc_align(logits, ld, target, ldt, target_len, len_offset, B, T, C, blank, start, end, char_logp, path_logp, frame_label))
+    return rc;
+  const double NINF = -std::numeric_limits<double>::infinity();
+  std::vector<int> ext, state(T);
+  std::vector<double> lp, alpha, v;
+  std::vector<unsigned char> choice;
+  for (int b = 0; b < B; ++b) {
+    int* st = start + (size_t)b * ldt;
+    int* en = end + (size_t)b * ldt;
+    float* cl = char_logp + (size_t)b * ldt;
+    int* fr = frame_label ? frame_label + (size_t)b * T : nullptr;
+    for (int k = 0; k < ldt; ++k) { st[k] = en[k] = -1; cl[k] = 0.f; }
+    double logp = 0.0;
+    bool ok = ctc_forward(logits + (size_t)b * T * ld, ld, target + (size_t)b * ldt, target_len[b] - (long long)len_offset, ldt, T, C, blank, ext,
+                          lp, alpha, logp);
+    const int S = (int)ext.size(), n = S / 2;
+    int s = 0;
+    if (ok) {
+      v.assign((size_t)T * S, NINF);
+      choice.assign((size_t)T * S, 0);
+      v[0] = lp[blank];
+      if (n) v[1] = lp[ext[1]];
+      for (int t = 1; t < T; ++t)
+        for (int q = 0; q < S; ++q) {
+          const double* p = &v[(size_t)(t - 1) * S];
+          double m = p[q];
+          unsigned char c = 0;
+          if (q >= 1 && p[q - 1] > m) { m = p[q - 1]; c = 1; }
+          if (q >= 3 && (q & 1) && ext[q] != ext[q - 2] && p[q - 2] > m) { m = p[q - 2]; c = 2; }
+          v[(size_t)t * S + q] = m + lp[(size_t)t * C + ext[q]];
+          choice[(size_t)t * S + q] = c;
+        }
+      const double* last = &v[(size_t)(T - 1) * S];
+      s = (n && last[S - 2] > last[S - 1]) ? S - 2 : S - 1;
+      ok = last[s] > NINF;
+      if (ok) path_logp[b] = (float)last[s];
+    }
+    if (!ok) {
+      path_logp[b] = -std::numeric_limits<float>::infinity();
+      for (int t = 0; fr && t < T; ++t) fr[t] = -2;
+      continue;
+    }
+    for (int t = T - 1; t >= 0; --t) {
+      state[t] = s;
+      if (t) s -= choice[(size_t)t * S + s];
+    }
+    std::vector<double> sum(n, 0.0);
+    for (int t = 0; t < T; ++t) {
+      const int q = state[t], k = q >> 1;
+      if (fr) fr[t] = (q & 1) ? k : -1;
+      if (!(q & 1)) continue;
+      if (st[k] < 0) st[k] = t;
+      en[k] = t + 1;
+      sum[k] += lp[(size_t)t * C + ext[q]];
+    }
+    for (int k = 0; k < n; ++k) cl[k] = (float)sum[k];
+  }
+  return DIG_OK;
+}
+
 int dig_ctc_greedy_decode(const float* logits, int ld, int B, int T, int C, int blank, int eos, int padding, long long* ids, float* score,
                           int* n, hipStream_t) {
   if (int rc = dig_rules::ctc_greedy_decode(logits, ld, B, T, C, blank, eos, padding, ids, score, n)) return rc;

@@ -103,6 +103,8 @@ HOT_KERNELS = ("mlp_chain_kernel<1, true, false>", "mlp_chain_kernel<2, true, fa
                "ctc_beam_kernel",
                # the CTC lexicon decode (ctc.hip): the three segment widths are inlined into one kernel; states in registers, the table in LDS
                "ctc_lex_score_kernel",
+               # the CTC forced alignment (ctc.hip): a lane's two Viterbi states in registers, emissions / back-pointers / the path in LDS
+               "ctc_align_kernel",
                # beam search of the GRU attention head (gru_attn.hip, decode.hip): the K accumulator sets of a lane / channel pair in registers
                "addattn_fwd_slots_kernel", "attn_beam_advance_kernel")
 LLVM_BIN = os.environ.get("DIG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")

@@ -418,6 +418,11 @@ static inline int ctc_loss_bwd(const float* logits, int ld, const long long* tar
   if (!dlogits || ldd < C) return DIG_ERR_ARG;
   return ctc_common(logits, ld, target, ldt, target_len, B, T, C, blank);
 }
+static inline int ctc_align(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
+                            int C, int blank, int* start, int* end, float* char_logp, float* path_logp, int* frame_label) {
+  if (!start || !end || !char_logp || !path_logp) return DIG_ERR_ARG;                 // (frame_label: nullable)
+  return ctc_common(logits, ld, target, ldt, target_len, B, T, C, blank);
+}
 
 // ---- abiaug.hip
 static inline int abiaug_sample(dig_abi_params* params, long long* info, const int* heights, const int* widths, int n_img, const dig_abi_run* run,

@@ -5,6 +5,7 @@
 //   dig_ctc_greedy_decode  the string rule of ctc_get_str_list (evaluation_metric/metrics.py:220-227) as decoder-shaped rows
 //   dig_ctc_beam_decode    prefix beam search (`--ctc_beam_width`): the best collapsed string over all its alignments, as the same rows
 //   dig_ctc_lexicon_decode the lexicon word of highest likelihood (`--ctc_lexicon`): one alpha recursion per (sample, word), as the same rows
+//   dig_ctc_align          the best alignment of given labels (`--ctc_align_out`): the frames of every character and their log-probability
 //
 // One wave per sample.  The extended label sequence blank, l_0, blank, l_1, ..., l_{n-1}, blank has 2n + 1 <= 127 states: lane i owns
 // state 2i (the blank in front of label i; lane n: the final blank) and state 2i + 1 (label i), so a time step moves ONE value between
@@ -199,6 +200,92 @@ __global__ __launch_bounds__(64) void ctc_kernel(const float* __restrict__ logit
       }
       if (d_is_f32) d32[(size_t)t * ldd + c] = v; else d16[(size_t)t * ldd + c] = f2bf(v);
     }
+  }
+}
+
+// Forced alignment (the rule: include/dig_hip.h at dig_ctc_align): the max-product twin of the alpha recursion above with back-pointers and
+// a back-trace, one wave per sample, lane i owning states 2i and 2i + 1 as in ctc_kernel.  The states are held in double: a step is one
+// add and two or three compares per state, there is no sum to keep small and so nothing to re-centre, and the score of the path is the
+// double sum of its fp32 emissions rounded once.  A step moves one value up a lane (the label state of lane - 1), as ctc_alpha_step does.
+// Dynamic LDS: the T x 64 float emission plane, then T x 64 bytes of back-pointers: byte [t][lane] holds the choice of the lane's blank
+// state in bits 0-1 (0 stay, 1 step) and of its label state in bits 2-3 (0 stay, 1 step, 2 skip), which is also the number of states the
+// back-trace moves down.  The back-trace is wave-uniform (every lane reads the same byte: a broadcast) and leaves the frame's state in
+// path[t]; lane k then walks the row for the span of label k and sums its emissions in ascending t.
+__global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logits, int ld, const long long* __restrict__ target, int ldt,
+                                                       const long long* __restrict__ target_len, int len_offset, int T, int C, int blank,
+                                                       int* __restrict__ start, int* __restrict__ end, float* __restrict__ char_logp,
+                                                       float* __restrict__ path_logp, int* __restrict__ frame_label) {
+  extern __shared__ float dyn[];
+  __shared__ float emb[CTC_MAX_T], lmax[CTC_MAX_T], lsum[CTC_MAX_T];
+  __shared__ int path[CTC_MAX_T];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float* em = dyn;
+  unsigned char* bp = (unsigned char*)(dyn + (size_t)T * 64);
+  const CtcSample s = ctc_sample(target, ldt, target_len, len_offset, b, lane, T, C, blank);
+  int* st = start + (size_t)b * ldt;
+  int* en = end + (size_t)b * ldt;
+  float* cl = char_logp + (size_t)b * ldt;
+  bool ok = s.ok;                                                         // (wave-uniform)
+  double best = -INFINITY;
+  int state = 0;
+  if (ok) {
+    ctc_emissions(logits + (size_t)b * T * ld, ld, T, C, blank, s, lane, em, emb, lmax, lsum);
+    __syncthreads();
+    double vb = lane == 0 ? (double)emb[0] : -INFINITY;
+    double vl = (lane == 0 && s.n > 0) ? (double)em[lane] : -INFINITY;
+    for (int t = 1; t < T; ++t) {
+      double pl = __shfl_up(vl, 1, 64);                                    // the label state of lane - 1
+      if (lane == 0) pl = -INFINITY;
+      // the predecessors in the order stay, step, skip: a later one wins only when strictly larger
+      const bool b_step = pl > vb;
+      const double mb = b_step ? pl : vb;
+      const bool l_step = vb > vl;
+      double ml = l_step ? vb : vl;
+      const bool l_skip = !s.rep && pl > ml;
+      ml = l_skip ? pl : ml;
+      bp[t * 64 + lane] = (unsigned char)((b_step ? 1 : 0) | ((l_skip ? 2 : (l_step ? 1 : 0)) << 2));
+      vb = lane <= s.n ? mb + (double)emb[t] : -INFINITY;
+      vl = lane < s.n ? ml + (double)em[t * 64 + lane] : -INFINITY;
+    }
+    const double fb = __shfl(vb, s.n, 64);
+    const double fl = s.n > 0 ? __shfl(vl, s.n - 1, 64) : -INFINITY;
+    state = fl > fb ? 2 * s.n - 1 : 2 * s.n;
+    best = fl > fb ? fl : fb;
+    ok = best > -INFINITY;                                                // (a path of probability 0, which finite logits never give: as no alignment)
+  }
+  if (!ok) {
+    if (lane < ldt) { st[lane] = -1; en[lane] = -1; cl[lane] = 0.f; }
+    if (lane == 0) path_logp[b] = -INFINITY;
+    if (frame_label && lane < T) frame_label[(size_t)b * T + lane] = -2;
+    return;
+  }
+  __syncthreads();
+  for (int t = T - 1; t >= 0; --t) {
+    if (lane == 0) path[t] = state;
+    if (t) {
+      const int c = bp[t * 64 + (state >> 1)];
+      state = max(state - ((state & 1) ? (c >> 2) & 3 : c & 3), 0);        // (never below 0: lane 0 has no step into its blank and no skip)
+    }
+  }
+  __syncthreads();
+  if (lane < ldt) {
+    int t0 = -1, t1 = -1;
+    double sum = 0.0;
+    if (lane < s.n)
+      for (int t = 0; t < T; ++t)
+        if (path[t] == 2 * lane + 1) {
+          if (t0 < 0) t0 = t;
+          t1 = t + 1;
+          sum += (double)em[t * 64 + lane];
+        }
+    st[lane] = t0;
+    en[lane] = t1;
+    cl[lane] = (float)sum;
+  }
+  if (lane == 0) path_logp[b] = (float)best;
+  if (frame_label && lane < T) {
+    const int p = path[lane];
+    frame_label[(size_t)b * T + lane] = (p & 1) ? p >> 1 : -1;
   }
 }
 
@@ -648,6 +735,17 @@ extern "C" int dig_ctc_loss_bwd(const float* logits, int ld, const long long* ta
   if (B == 0) return DIG_OK;
   hipLaunchKernelGGL(ctc_kernel<true>, dim3(B), dim3(64), (size_t)T * 192 * sizeof(float), stream, logits, ld, target, ldt, target_len, len_offset,
                      gscalar, B, T, C, blank, (float*)nullptr, dlogits, ldd, dlogits_is_f32 ? 1 : 0);
+  return dig_check_launch();
+}
+
+extern "C" int dig_ctc_align(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B,
+                             int T, int C, int blank, int* start, int* end, float* char_logp, float* path_logp, int* frame_label,
+                             hipStream_t stream) {
+  if (int rc = dig_rules::ctc_align(logits, ld, target, ldt, target_len, len_offset, B, T, C, blank, start, end, char_logp, path_logp, frame_label))
+    return rc;
+  if (B == 0) return DIG_OK;
+  hipLaunchKernelGGL(ctc_align_kernel, dim3(B), dim3(64), (size_t)T * 64 * (sizeof(float) + 1), stream, logits, ld, target, ldt, target_len,
+                     len_offset, T, C, blank, start, end, char_logp, path_logp, frame_label);
   return dig_check_launch();
 }
 

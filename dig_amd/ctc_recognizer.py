@@ -14,7 +14,10 @@ alignment; the rule is this project's (the reference has no CTC beam search) and
 rows carry the string's probability in score[:, 0] and 1 elsewhere.  `--ctc_lexicon FILE` (own flag; `ctc_lexicon` here, a `LabelLexicon`)
 makes the evaluation decode the lexicon word of highest likelihood: `dig_ctc_lexicon_decode` scores every (image, word) pair by the sum over
 all alignments, the quantity the criterion computes, where the reference's lexicon metrics snap a decoded string to the nearest word by edit
-distance; rows as the beam's.  Training-mode decodes (the loop's class accuracy) stay greedy.
+distance; rows as the beam's.  Training-mode decodes (the loop's class accuracy) stay greedy.  `align` (own; `--ctc_align_out FILE`) answers
+where in the crop each character of a string is and how sure the model is of it: `dig_ctc_align` finds the best single alignment of given
+labels -- a target row, or the row of any of the three decoders -- and returns every label's frames and its log-probability over them (the
+rule: include/dig_hip.h; `evaluation_metric.CTCAlignment` turns them into character boxes, `frame_columns` crop columns per frame).
 
 Flat arenas, one autograd node, the encoder on the pre-training hot-path kernels (model and step on dig_amd.finetune.EncoderTrain / _EncoderStep); the head is
 `dig_window_pool_*` (the `--use_1d_attdec` pooling), two GEMMs and the fused LayerNorm + GELU launch; loss, gradient and decode are
@@ -78,6 +81,24 @@ def ctc_beam_decode(logits, C, blank, eos, padding, beam_width):
     L.call("dig_ctc_beam_decode", L.ptr(logits), ld, B, T, C, blank, eos, padding, int(beam_width), L.ptr(ids), L.ptr(score), L.ptr(logp), L.ptr(n),
            L.stream())
     return ids, score, logp, n
+
+
+def ctc_align(logits, C, target, length, blank, len_offset=1, want_frames=False):
+    """dig_ctc_align (forced alignment, the rule in include/dig_hip.h) on logits fp32 [B, T, ld >= C]: the best path of the labels of
+    target int64 [B, ldt] (row b: its first length[b] - len_offset cells) through the frames.  Returns (start int32 [B, ldt], end int32
+    [B, ldt]: label k on frames [start, end), -1 past the labels; char_logp fp32 [B, ldt]: the label's log-probability summed over its
+    frames; path_logp fp32 [B]: the whole path's, -inf for a sample without an alignment) and, with want_frames, frame_label int32 [B, T]
+    (the label index of every frame, -1 on a blank frame, -2 without an alignment)."""
+    B, T, ld = logits.shape
+    dev, ldt = logits.device, target.shape[1]
+    start = torch.empty((B, ldt), device=dev, dtype=torch.int32)
+    end = torch.empty((B, ldt), device=dev, dtype=torch.int32)
+    char_logp = torch.empty((B, ldt), device=dev, dtype=F32)
+    path_logp = torch.empty(B, device=dev, dtype=F32)
+    frames = torch.empty((B, T), device=dev, dtype=torch.int32) if want_frames else None
+    L.call("dig_ctc_align", L.ptr(logits), ld, L.ptr(target), ldt, L.ptr(length), len_offset, B, T, C, blank, L.ptr(start), L.ptr(end),
+           L.ptr(char_logp), L.ptr(path_logp), L.ptr(frames), L.stream())
+    return (start, end, char_logp, path_logp, frames) if want_frames else (start, end, char_logp, path_logp)
 
 
 LEX_CHUNK = L.const("DIG_CTC_LEX_CHUNK")                # words per workgroup of the lexicon decode
@@ -391,6 +412,17 @@ class CTCRecModelTrain(EncoderTrain):
             return ctc_greedy_decode(x, x.shape[2], self.blank, self.eos, self.padding)
         ids, score, _, n = ctc_beam_decode(x, x.shape[2], self.blank, self.eos, self.padding, beam_width)
         return ids, score, n
+
+    frame_columns = 128 // EncoderTrain.gw               # crop columns per frame: the head classifies the 32 column means of a patch-4 grid
+
+    def align(self, logits, rows, lengths, len_offset=1):
+        """(start, end, char_logp, path_logp) of csrc/ctc.hip's forced alignment of `rows` through logits [B, 32, nb_classes + 1]: dataset
+        targets with their lengths (which count the closing EOS: len_offset = 1), or, with len_offset = 0, the (ids, n) that `decode`
+        returned, whichever decoder produced them.  Character k of row b covers the crop columns [start * frame_columns, end *
+        frame_columns).  Cells past a row's labels hold -1 / 0; a row wider than 63 cells is cut to 63."""
+        x = logits.detach().float().contiguous()
+        rows = rows.to(x.device).long()[:, :MAX_LEX_WORD_LEN].contiguous()
+        return ctc_align(x, x.shape[2], rows, lengths.to(x.device).long().contiguous(), self.blank, len_offset)
 
     def forward(self, x):
         if self.training:

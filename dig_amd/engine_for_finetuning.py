@@ -3,12 +3,15 @@
 `evaluate()` (:214-285): greedy decode through `dig_amd.recognizer.RecModel`, SeqCrossEntropyLoss, string accuracy and character
 F-measure all on the device; one host read per batch.  A CTC model (`is_ctc`, dig_amd/ctc_recognizer.py) is scored on `model.decode(logits)`
 -- the collapsed frames as decoder-shaped rows -- under SeqCTCLoss, in both functions (a model in training mode decodes greedily; in
-`evaluate` its `ctc_beam_width` chooses between the greedy rule and the prefix beam search); every other model takes the lines it always took.
+`evaluate` its `ctc_beam_width` chooses between the greedy rule and the prefix beam search; with `args.ctc_align_out` it also aligns the
+rows it decoded, or with `args.ctc_align_of` = "target" the targets, by `model.align` and appends one JSON line per image to that file,
+`FILE.rankN` with more than one rank, the meters untouched); every other model takes the lines it always took.
 `train_one_epoch()` (:54-210) with `train_class_batch` (:26-46) for the torch.amp branch (`loss_scaler` given): per-step lr / weight
 decay from the schedules times each group's `lr_scale`, teacher-forced forward, SeqCrossEntropyLoss, backward + grad norm + fused
 AdamW through the scaler object, gradient accumulation (`update_freq`), class accuracy of the arg-max, evaluation every
 `eval_freq` steps.  The meters travel in one pinned asynchronous copy resolved one step later (as in the pre-training engine).
 Mixup, model EMA, the distillation teacher and the deepspeed branch are not built (they raise)."""
+import json
 import math
 import sys
 from typing import Iterable, Optional
@@ -16,7 +19,7 @@ from typing import Iterable, Optional
 import torch
 
 from . import utils
-from .evaluation_metric import edit_distances
+from .evaluation_metric import CTCAlignment, edit_distances
 from .ctc_recognizer import SeqCTCLoss, match_widths
 from .recognizer import SeqCrossEntropyLoss, accuracy, recognition_f_measure
 
@@ -158,6 +161,13 @@ def evaluate(data_loader, model, device, args=None):
     model.eval()
     voc = _vocabulary(data_loader.dataset)
     with_ed = bool(getattr(args, "eval_edit_distance", False))                      # EditDistance (evaluation_metric/metrics.py:142-147) per image
+    align_out = (getattr(args, "ctc_align_out", None) or None) if ctc else None      # --ctc_align_out FILE: one JSON line per image
+    if align_out:
+        to_records = CTCAlignment(data_loader.dataset, model.frame_columns)
+        of_target = getattr(args, "ctc_align_of", "prediction") == "target"
+        if utils.get_world_size() > 1:
+            align_out += f".rank{utils.get_rank()}"
+        n_written = 0
     for batch in metric_logger.log_every(data_loader, 10, header):
         images, target, lens = batch[0], batch[1], batch[-1]
         images = images.to(device, non_blocking=True)
@@ -169,7 +179,13 @@ def evaluate(data_loader, model, device, args=None):
             loss, pred_ids = torch.zeros((), device=output.device), output
         elif ctc:
             loss = criterion(output, target, lens)                               # (on the frames' logits)
-            pred_ids, target = match_widths(model.decode(output)[0], target, model.padding)
+            decoded = model.decode(output)
+            if align_out:                                                        # one more launch: the rows just decoded, or the targets
+                rows, n, off = (target, lens.to(target.device), 1) if of_target else (decoded[0], decoded[2], 0)
+                spans = model.align(output, rows, n, len_offset=off)
+                records = to_records(rows, n - off, *spans)
+                words = to_records.strings(target, lens.to(target.device) - 1)
+            pred_ids, target = match_widths(decoded[0], target, model.padding)
         else:
             loss = criterion(output, target, lens)                               # (on probabilities, as the reference does: :249)
             pred_ids = output.argmax(-1)
@@ -183,6 +199,11 @@ def evaluate(data_loader, model, device, args=None):
         metric_logger.meters['recognition_fmeasure'].update(vals[2], n=batch_size)
         if with_ed:
             metric_logger.meters['edit_distance'].update(vals[3], n=batch_size)
+        if align_out:
+            with open(align_out, "a", encoding="utf-8") as f:
+                for rec, word in zip(records, words):
+                    f.write(json.dumps({"index": n_written, "word": word, **rec}) + "\n")
+                    n_written += 1
     metric_logger.synchronize_between_processes()
     print('* {n} images, Acc {acc.global_avg:.4f} loss {losses.global_avg:.4f} Rec_fmeasure {rec_f.global_avg:.4f}'
           .format(n=metric_logger.acc.count, acc=metric_logger.acc, losses=metric_logger.loss, rec_f=metric_logger.recognition_fmeasure)

@@ -23,6 +23,8 @@ which `dig_string_match` / `dig_tokens_to_text` then read like any other predict
 `CTCAccuracy_with_lexicon` and `CTCEditDistance_with_lexicon` are this project's own (no `factory()` keys: the reference has no such metric):
 they take the CTC head's logits and decode each image to the lexicon word of highest likelihood (`dig_ctc_lexicon_decode`, one launch per
 lexicon level) where the mirrored lexicon metrics snap a decoded string to the nearest word; they compare normalised with normalised.
+`CTCAlignment` is own as well: it turns the forced alignment of the CTC head (`dig_ctc_align`) into one record per image, the character
+boxes in crop columns with a log-probability per character.
 
 Two keys of the reference's factory are left out of `factory()`: `ctc_accuracy` (the function is here, as `CTCAccuracy`; the five keys are what
 the reference's fine-tune path can reach) and `multi_label_fmeasure` (no model emits multi-label outputs; not built)."""
@@ -366,6 +368,46 @@ def CTCEditDistance_with_lexicon(logits, target, dataset=None, file_names=None):
     """The summed edit distances of the same decodes (see `CTCAccuracy_with_lexicon`): [none, lexicons50, lexicons1k, lexiconsfull]."""
     d = _ctc_with_lexicon(logits, target, dataset, file_names if file_names is not None else [])
     return [sum(d[k]) if k in d else 0 for k in ("none",) + _LEVELS]
+
+
+class CTCAlignment:
+    """Records of the CTC head's forced alignment (`dig_ctc_align`; `CTCRecModelTrain.align`), this project's own (no `factory()` key):
+    `CTCAlignment(dataset)(rows, n, start, end, char_logp, path_logp)` -> one dict per image,
+        {"text": str, "path_logp": float, "chars": [[char, x0, x1, logp], ...]}
+    from the label rows [B, >= ldt] that were aligned, their label counts n [B] (without EOS) and the four outputs of the alignment.
+    Character k covers the crop columns [x0, x1) = [start * frame_columns, end * frame_columns) and has the log-probability logp on them;
+    `text` is the concatenation of the characters.  A class id is turned into its character by the dataset's vocabulary, the rule
+    `dig_tokens_to_text` / `RecPostProcess` start from, but nothing is normalised away, since every label has a box: punctuation and case
+    stay, and a class that is no character (UNKNOWN; EOS or PADDING inside a row) reads U+FFFD.  An image without an alignment
+    (path_logp -inf) has `path_logp` None and no `chars`; its `text` is still the row's.  One host read per call."""
+    NO_CHAR = "\ufffd"
+
+    def __init__(self, dataset, frame_columns=4):
+        self.voc = [c if len(c) == 1 else self.NO_CHAR for c in _voc(dataset)]
+        self.frame_columns = int(frame_columns)
+
+    def strings(self, rows, n):
+        """The rows' first n[b] labels as strings by the same rule (the ground-truth word of a record).  One host read."""
+        host = torch.cat([rows, n.to(rows.device).reshape(-1, 1).to(rows.dtype)], dim=1).tolist()
+        voc = self.voc
+        return ["".join(voc[c] if 0 <= c < len(voc) else self.NO_CHAR for c in r[:max(0, min(r[-1], len(r) - 1))]) for r in host]
+
+    def __call__(self, rows, n, start, end, char_logp, path_logp):
+        B, ldt = start.shape
+        dev = start.device
+        parts = [rows.to(dev)[:, :ldt], n.to(dev).reshape(B, 1), start, end, char_logp, path_logp.reshape(B, 1)]
+        host = torch.cat([p.double() for p in parts], dim=1).tolist()
+        voc, fc, out = self.voc, self.frame_columns, []
+        for r in host:
+            k = max(0, min(int(r[ldt]), ldt))
+            ids, st, en, lp, path = r[:k], r[ldt + 1:], r[2 * ldt + 1:], r[3 * ldt + 1:], r[4 * ldt + 1]
+            chars = [voc[int(c)] if 0 <= int(c) < len(voc) else self.NO_CHAR for c in ids]
+            if path == float("-inf"):
+                out.append({"text": "".join(chars), "path_logp": None, "chars": []})
+            else:
+                out.append({"text": "".join(chars), "path_logp": path,
+                            "chars": [[chars[i], int(st[i]) * fc, int(en[i]) * fc, lp[i]] for i in range(k)]})
+        return out
 
 
 __factory = {

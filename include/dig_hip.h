@@ -698,6 +698,31 @@ int dig_ctc_lexicon_decode(const float* logits, int ld, int B, int T, int C, int
                            const int* word_len, int ldw, int W, const int* lex_begin, const int* lex_count, int max_count,
                            int* best_index, float* logp, long long* ids, float* score, int* n, float* scores /* nullable */,
                            void* workspace, long long workspace_bytes, hipStream_t stream);
+/* dig_ctc_align: forced alignment (`--ctc_align_out`; this project's own rule, the reference has no alignment): the single best path of
+ * given labels through the frames, the Viterbi (max-product) twin of the alpha recursion of dig_ctc_loss, with the frames of every label
+ * and the log-probability the model gives the label on them.  The labels may be a ground-truth word or the row of any of the decoders.
+ * Inputs are exactly those of dig_ctc_loss: logits fp32 rows of ld >= C columns, columns [C, ld) never read; n_b = target_len[b] -
+ *   len_offset clamped to [0, ldt] (len_offset = 1 for dataset rows that end in EOS, 0 for decode rows with their n); lp[t][c] = the
+ *   log-softmax of frame t as dig_ctc_loss forms it (double differences and a double sum, rounded to fp32 once).
+ * States of a sample: s = 0..2n; an even state is the blank, state 2k + 1 is label l_k.  v[0][0] = lp[0][blank], v[0][1] = lp[0][l_0]
+ *   when n > 0, every other state -inf.
+ * Recursion for t > 0: v[t][s] = lp[t][cls(s)] + max over the predecessors, taken in this order: stay (s), step (s - 1), skip (s - 2,
+ *   only for odd s >= 3 with l_k != l_{k-1}).  On a tie the predecessor earlier in that order wins.  A state whose predecessors are all
+ *   -inf stays -inf.  The states are sums in double of the fp32 lp.
+ * End: state 2n, unless n > 0 and v[T-1][2n-1] is strictly larger.  The back-trace follows the recorded choices.
+ * Outputs: start, end [B][ldt] int32: label k sits on frames [start, end), the consecutive frames in state 2k + 1, so end > start;
+ *   cells k >= n_b hold -1.  char_logp [B][ldt] fp32 = the sum of lp[t][l_k] over the span in ascending t, accumulated in double and
+ *   rounded once; cells k >= n_b hold 0.  path_logp [B] fp32 = the score of the whole path, blanks included.  frame_label (nullable)
+ *   [B][T] int32: k on a frame in label k's state, -1 on a blank frame.
+ * No alignment: a sample with n + adjacent equal labels > T, or holding a label outside [0, C) or equal to `blank` (no index is formed
+ *   from such a label; a best path of probability 0, which finite logits never give, counts the same): path_logp = -inf, all start /
+ *   end cells -1, char_logp 0, frame_label -2.  n = 0 is valid: the all-blank path, path_logp = sum_t lp[t][blank].
+ * One launch, one wave per sample; no floating-point atomics: two launches on the same input give the same bits.
+ * Null pointer other than frame_label, non-positive dimension, B < 0, ld < C, blank outside [0, C): DIG_ERR_ARG.  Outside 1 <= T <= 64,
+ * 2 <= C <= 256, ldt <= 63: DIG_ERR_UNSUPPORTED.  B == 0: DIG_OK without a launch.  A refused call writes nothing. */
+int dig_ctc_align(const float* logits, int ld, const long long* target, int ldt, const long long* target_len, int len_offset, int B, int T,
+                  int C, int blank, int* start, int* end, float* char_logp, float* path_logp, int* frame_label /* nullable */,
+                  hipStream_t stream);
 
 /* ---- dropout / stochastic depth of the fine-tune step (README.md:100-118: --drop 0.1 --attn_drop_rate 0.1 --drop_path 0.1; the
  * recognition decoder's hard-wired dropout = 0.1, models/decoder.py:141).  Replaces nn.Dropout (modeling_finetune.py:51,83-85,271;

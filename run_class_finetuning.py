@@ -42,7 +42,12 @@ What is different, on purpose:
   * own flags: --data_set image_list, --synthetic N, --eval_edit_distance (adds the EditDistance meter to `evaluate`), --ctc_beam_width K
     (with --decoder_type ctc: `evaluate` decodes by CTC prefix beam search of width K <= 32, said once; 0, the default, is the greedy collapse;
     the training loop's class accuracy stays greedy), --ctc_lexicon FILE (with --decoder_type ctc: a UTF-8 file, one word per line;
-    `evaluate` decodes each image to the word of FILE with the highest CTC likelihood, said once; not together with --ctc_beam_width).
+    `evaluate` decodes each image to the word of FILE with the highest CTC likelihood, said once; not together with --ctc_beam_width),
+    --ctc_align_out FILE (with --decoder_type ctc: `evaluate` makes one more device call per batch, the forced alignment of the rows it just
+    decoded through the frames, and appends one JSON line per image to FILE in evaluation order, `FILE.rankN` with more than one rank:
+    {"index", "word" (the ground truth), "text", "path_logp", "chars": [[char, x0, x1, logp], ...]} with the character boxes in crop columns;
+    FILE is emptied when the run starts; said once; meters and return values stay as they are), --ctc_align_of {prediction,target} (what
+    --ctc_align_out aligns: the decoded rows, the default, or the ground-truth targets).
 
 Multi-rank runs are wired (samplers, FlatGradComm, the meters' all-reduce) but only the single-rank path is tested."""
 import argparse
@@ -116,6 +121,10 @@ def get_args(argv=None):
     a("--ctc_beam_width", type=int, default=0, help="with --decoder_type ctc: evaluate with a CTC prefix beam search of this width (1..32); 0 = greedy")
     a("--ctc_lexicon", type=str, default=None, metavar="FILE",
       help="with --decoder_type ctc: evaluate by decoding each image to the most probable word of FILE (UTF-8, one word per line)")
+    a("--ctc_align_out", type=str, default=None, metavar="FILE",
+      help="with --decoder_type ctc: evaluate also aligns every image's string to its frames and writes one JSON line per image to FILE")
+    a("--ctc_align_of", type=str, default="prediction", choices=("prediction", "target"),
+      help="what --ctc_align_out aligns: the rows the evaluation decoded (default) or the ground-truth targets")
     # fine-tuning
     a("--finetune", default="", help="pre-training checkpoint to start from")
     a("--model_key", default="model|module", type=str)
@@ -226,6 +235,16 @@ def refuse_unbuilt(args):
         from dig_amd.ctc_recognizer import read_lexicon_file
         if not read_lexicon_file(args.ctc_lexicon):
             raise SystemExit(f"--ctc_lexicon {args.ctc_lexicon}: the file holds no word (one per line; empty lines are skipped)")
+    if args.ctc_align_out is not None:
+        if args.decoder_type != "ctc":
+            raise SystemExit(f"--ctc_align_out with --decoder_type {args.decoder_type}: the forced alignment places a string on the CTC head's frames "
+                             "(--decoder_type ctc); the autoregressive heads have no frames to align to")
+        if not os.path.isdir(os.path.dirname(os.path.abspath(args.ctc_align_out))):
+            raise SystemExit(f"--ctc_align_out {args.ctc_align_out}: the directory {os.path.dirname(os.path.abspath(args.ctc_align_out))} does not exist")
+        if os.path.isdir(args.ctc_align_out):
+            raise SystemExit(f"--ctc_align_out {args.ctc_align_out}: a directory, not a file")
+    elif args.ctc_align_of != "prediction":
+        raise SystemExit(f"--ctc_align_of {args.ctc_align_of} without --ctc_align_out FILE: there is no alignment to choose the rows of")
     if (args.input_h, args.input_w) != (32, 128):
         raise SystemExit(f"--input_h {args.input_h} --input_w {args.input_w}: the encoders are built for 32 x 128 crops")
     paths = [args.data_path] if isinstance(args.data_path, str) else list(args.data_path)
@@ -373,6 +392,11 @@ def main(args):
         if model.ctc_lexicon is not None:
             print(f"evaluation decoder = the most probable of the {len(model.ctc_lexicon.words)} words of {args.ctc_lexicon} by CTC likelihood "
                   f"({model.ctc_lexicon.n_rows} label rows; --ctc_lexicon); the training loop's accuracy decodes greedily")
+        if args.ctc_align_out is not None:
+            mine = args.ctc_align_out + (f".rank{utils.get_rank()}" if utils.get_world_size() > 1 else "")
+            open(mine, "w").close()                                            # (every evaluate() of the run appends)
+            print(f"evaluation also writes the CTC forced alignment of the {'targets' if args.ctc_align_of == 'target' else 'decoded rows'} to {mine}: "
+                  f"one JSON line per image, character boxes in crop columns ({model.frame_columns} per frame; --ctc_align_out)")
     elif args.smoothing > 0.:
         criterion = SeqLabelSmoothingCrossEntropyLoss(smoothing=args.smoothing)
         criterion.ignore_index = dataset_train.class_to_idx["PADDING"]
