@@ -58,6 +58,16 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def stream_key(dev):
+    """The current stream of `dev` as a dictionary key (the raw handle as an int; 0 for a device that has no streams): what per-stream
+    caches such as scratch.py key on."""
+    if dev.type != "cuda":
+        return 0
+    if _raw_stream is not None and dev.index is not None:
+        return _raw_stream(dev.index)
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
 _fns = {}
 _protos = None
 _returns = {}
@@ -92,6 +102,8 @@ def _prototypes():
             types = []
             for prm in m.group(3).split(","):
                 prm = " ".join(prm.split())
+                if prm in ("", "void"):
+                    continue
                 if "*" in prm:
                     types.append(ctypes.c_void_p)
                     continue

@@ -23,6 +23,9 @@ extern "C" int dig_mlp_chain_colsum_rows(int R) { return dig_rules::mlp_chain_co
 extern "C" long long dig_lexicon_search_workspace_bytes(int B, int max_count) { return dig_rules::lexicon_search_workspace_bytes(B, max_count); }
 extern "C" long long dig_ctc_lexicon_workspace_bytes(int B, int T, int C, int max_count) { return dig_rules::ctc_lexicon_workspace_bytes(B, T, C, max_count); }
 extern "C" long long dig_sumsq_workspace_bytes(long long n) { return dig_rules::sumsq_workspace_bytes(n); }
+extern "C" long long dig_mse_workspace_bytes() { return dig_rules::mse_workspace_bytes(); }
+extern "C" long long dig_ce_rows_workspace_bytes(int n) { return dig_rules::ce_rows_workspace_bytes(n); }
+extern "C" long long dig_tcv_attn_bwd_workspace_bytes(int S, int Lq, int heads, int d) { return dig_rules::tcv_attn_bwd_workspace_bytes(S, Lq, heads, d); }
 
 // Workgroup table of one launch (host memory in, host memory out): tiles_per_prob[n_probs] tiles x S R-splits, the tiles of one
 // (problem, split) pair on one XCD, the eight XCDs loaded evenly.  S = the largest split count <= max_wg / tiles (whole groups of

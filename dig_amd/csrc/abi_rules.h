@@ -124,6 +124,16 @@ static inline long long ctc_lexicon_workspace_bytes(int B, int T, int C, int max
   return keys + (long long)B * T * C * (long long)sizeof(float);
 }
 static inline long long sumsq_workspace_bytes(long long) { return 1024 * (long long)sizeof(float); }
+// dig_mse_fwd_bwd_ws: the ticket word + one block sum per workgroup of its launch
+constexpr int MSE_MAX_BLOCKS = 256;
+static inline long long mse_workspace_bytes() { return (1 + MSE_MAX_BLOCKS) * (long long)sizeof(float); }
+// dig_ce_rows_ws: the ticket word + the three sums of each row
+static inline long long ce_rows_workspace_bytes(int n) { return n < 0 ? 0 : (1 + 3LL * n) * (long long)sizeof(float); }
+// dig_tcv_attn_bwd: [S Lq][2d] each query row's share of (dlnc_g | dlnc_b), then [S Lq][heads] delta
+static inline long long tcv_attn_bwd_workspace_bytes(int S, int Lq, int heads, int d) {
+  if (S <= 0 || Lq <= 0 || Lq > TCV_MAXQ || heads <= 0 || d <= 0 || d > 512 || heads > d) return 0;   // (past these the entry point refuses; the product stays in 64 bits)
+  return (long long)S * Lq * (2LL * d + heads) * (long long)sizeof(float);
+}
 
 // ---- sizes the launchers and the rules share
 static inline long long sgemm_rows_per_split(int R, int r_splits) {  // whole 64-deep K steps per split

@@ -815,7 +815,7 @@ extern "C" int dig_mse_fwd_bwd_ws(const float* pred, int ld_pred, const float* t
   if (int rc = dig_rules::mse_fwd_bwd_ws(pred, ld_pred, target, M, C, gscale, loss, dpred, ld_dpred, workspace)) return rc;
   const int ldd = dpred ? ld_dpred : C;
   const int total = M * ldd;
-  hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(std::min(256, (total + 255) / 256)), dim3(256), 0, stream, pred, ld_pred, target, M, C,
+  hipLaunchKernelGGL(mse_fwd_bwd_kernel, dim3(std::min(dig_rules::MSE_MAX_BLOCKS, (total + 255) / 256)), dim3(256), 0, stream, pred, ld_pred, target, M, C,
                      1.0f / ((float)M * C), gscale, loss, (bf16_t*)dpred, ldd, workspace);
   return dig_check_launch();
 }

@@ -7,6 +7,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from . import scratch
 
 cf = ctypes.c_float
 cll = ctypes.c_longlong
@@ -17,23 +18,13 @@ OUT_BF16, OUT_F32, OUT_F32_PARTIAL = 0, 1, 2
 # K-tile depth of the MFMA GEMM: 64 for direct/direct (forward), 32 when a transpose-read operand is involved
 # (dgrad / wgrad): measured on MI355X, see profiles/r01_gemm_bk_sweep.txt
 GEMM_BK_FWD, GEMM_BK_BWD = 64, 32
-_ws = {}
-
-
-def _stream_id(dev):
-    """Raw handle of the current stream of `dev` (a dictionary key; see _lib.stream for why not torch.cuda.current_stream())."""
-    if L._raw_stream is not None and dev.index is not None:
-        return L._raw_stream(dev.index)
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _workspace(dev, numel):
-    """Per-device fp32 scratch for split-R partial slabs (grown on demand, reused across launches on one stream)."""
-    key = (dev, _stream_id(dev))        # one scratch per stream: launches on a stream are ordered
-    w = _ws.get(key)
-    if w is None or w.numel() < numel:
-        w = _ws[key] = torch.empty(max(numel, 1 << 22), device=dev, dtype=F32)
-    return w
+# Smallest allocation (fp32 elements) of the scratch.py tags: "slabs" (split-R partial slabs, the attention-backward sums), "partials"
+# (column-sum / LayerNorm / BatchNorm partial sums), "mse" / "ce" (the zeroed areas of the loss reductions), "wgrad_group0" / "1"
+# (WgradGroup's two slab sets); "batch" (GradReduceBatch: pending until flush()) is one fixed size
+SLAB_FLOOR, PARTIAL_FLOOR, LOSS_FLOOR, GROUP_FLOOR = 1 << 22, 1 << 20, 4096, 1 << 24
+# Two names of the former scratch accessors, kept as empty attributes: earlier revisions of tests/cpu_abi_util.py save and restore them
+# around a test, and the tests of those revisions must still run against this module.  Nothing reads them; scratch comes from scratch.get.
+_workspace = _workspace2 = None
 
 
 def gemm(A, B, I, J, R, *, ta=False, tb=False, out=None, out_kind=OUT_BF16, bias=None, resid=None, pre=None, alpha=1.0,
@@ -104,7 +95,7 @@ def narrow_splits(rows, out_cols, K):
 
 
 def _split_gemm_bf16(A, B, I, J, R, tb, bk, sp, out):
-    ws = _workspace(A.device, sp * I * J)
+    ws = scratch.get("slabs", A.device, sp * I * J, floor=SLAB_FLOOR)
     gemm(A, B, I, J, R, tb=tb, out=ws, out_kind=OUT_F32_PARTIAL, splits=sp, ldc=J, bk=bk)
     if out is None:
         out = torch.empty((I, J), device=A.device, dtype=BF16)
@@ -362,22 +353,12 @@ def wgrad(dy, x, dw, I, J, rows):
     also performs the += into the gradient arena."""
     tiles = ((I + 127) // 128) * ((J + 127) // 128)
     sp, bk = wgrad_splits(rows, tiles)
-    ws = _workspace(dy.device, sp * I * J)
+    ws = scratch.get("slabs", dy.device, sp * I * J, floor=SLAB_FLOOR)
     gemm(dy, x, I, J, rows, ta=True, tb=True, out=ws, out_kind=OUT_F32_PARTIAL, splits=sp, ldc=J, bk=bk)
     L.call("dig_reduce_partials", L.ptr(ws), sp, cll(I * J), L.ptr(dw), 1, L.stream())
 
 
 BATCH_SLABS = os.environ.get("DIG_BATCH_SLABS", "1") != "0"
-_ws3 = {}
-
-
-def _batch_workspace(dev, numel):
-    key = (dev, _stream_id(dev) if dev.type == "cuda" else 0)
-    w = _ws3.get(key)
-    if w is None or w.numel() < numel:
-        w = _ws3[key] = torch.empty(numel, device=dev, dtype=F32)
-    return w
-
 
 COLSUM_MAX_SEGS = L.const("DIG_COLSUM_MAX_SEGS")
 
@@ -415,7 +396,7 @@ class GradReduceBatch:
             return
         if self.off + need > self.SLAB_FLOATS:
             self.flush()
-        ws = _batch_workspace(dy.device, self.SLAB_FLOATS)[self.off:self.off + need]      # its own scratch: slabs stay pending until flush()
+        ws = scratch.get("batch", dy.device, self.SLAB_FLOATS)[self.off:self.off + need]      # its own tag: slabs stay pending until flush()
         self.off += need
         gemm(dy, x, I, J, rows, ta=True, tb=True, out=ws, out_kind=OUT_F32_PARTIAL, splits=sp, ldc=J, bk=bk)
         self.slabs.append((ws, dw, I * J, sp))
@@ -482,7 +463,7 @@ def linear_wgrad(dy, x, dw, rows=None, assign=False):
 WGRAD_GROUP = os.environ.get("DIG_WGRAD_GROUP", "1") != "0"
 WGRAD_GROUP_WA = int(os.environ.get("DIG_WGRAD_WA", "2"))            # 1: 128-row tiles, 4 waves, two workgroups per CU;  2: 256-row tiles, 8 waves, one per CU
 WGRAD_GROUP_SLOTS = int(os.environ.get("DIG_WGRAD_SLOTS", "0")) or 512 // WGRAD_GROUP_WA     # workgroups per launch: one round on 256 CUs
-_wg_plans, _wg_slabs = {}, {}
+_wg_plans = {}
 
 
 class _WgProb(ctypes.Structure):
@@ -543,13 +524,6 @@ class WgradGroup:
             pl = _wg_plans[key] = (sp.value, n, m.to(self.dev))
         return pl
 
-    def _slabs(self, nbytes):
-        key = (str(self.dev), _stream_id(self.dev) if self.dev.type == "cuda" else 0, self.set)
-        w = _wg_slabs.get(key)
-        if w is None or w.numel() * 4 < nbytes:
-            w = _wg_slabs[key] = torch.empty((max(nbytes, 1 << 26) + 3) // 4, device=self.dev, dtype=F32)
-        return w
-
     def _structs(self, items):
         arr = (_WgProb * max(len(items), 1))()
         for k, (A, B, dw, trans) in enumerate(items):
@@ -561,7 +535,7 @@ class WgradGroup:
 
     def next_slabs(self, nbytes):
         """The slab set the next launch writes.  The two sets alternate: a launch fills one while it folds the other."""
-        slabs = self._slabs(nbytes)
+        slabs = scratch.get(f"wgrad_group{self.set}", self.dev, (nbytes + 3) // 4, floor=GROUP_FLOOR)
         self.set ^= 1
         return slabs
 
@@ -688,23 +662,11 @@ def wgrad_block_plan(dev, rows, D, Fh):
     return WgradBlockPlan(grp.fn, WGRAD_GROUP_WA, splits, n_wg, wmap, trans, grp, sum(tiles) * splits * 128 * WGRAD_GROUP_WA * 128 * grp.fn * 4)
 
 
-_ws2 = {}
-
-
-def _workspace2(dev, numel):
-    """Second fp32 scratch (column-sum / LayerNorm-backward partials)."""
-    key = (dev, _stream_id(dev))
-    w = _ws2.get(key)
-    if w is None or w.numel() < numel:
-        w = _ws2[key] = torch.empty(max(numel, 1 << 20), device=dev, dtype=F32)
-    return w
-
-
 def colsum(x, out, rows=None, cols=None):
     """out[c] += sum_r x[r, c]  (two-stage, deterministic)."""
     rows = x.shape[0] if rows is None else rows
     cols = x.shape[1] if cols is None else cols
-    ws = _workspace2(x.device, 1024 * cols)
+    ws = scratch.get("partials", x.device, scratch.floats("dig_colsum_workspace_bytes", rows, cols), floor=PARTIAL_FLOOR)
     L.call("dig_colsum", L.ptr(x), L.ptr(out), L.ptr(ws), rows, cols, x.stride(0), L.stream())
 
 
@@ -726,7 +688,7 @@ def layernorm_bwd(dy, x, gamma, beta, mean, rstd, dres, dgamma, dbeta, gelu=Fals
     rows, D = x.shape
     dx = torch.empty_like(x) if out is None else out
     if not defer:
-        ws = _workspace2(x.device, 1024 * 3 * D)
+        ws = scratch.get("partials", x.device, scratch.floats("dig_layernorm_bwd_workspace_bytes", rows, D), floor=PARTIAL_FLOOR)
         L.call("dig_layernorm_bwd", L.ptr(dy), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd), L.ptr(dres), L.ptr(dx),
                L.ptr(dgamma), L.ptr(dbeta), L.ptr(dres_colsum), L.ptr(ws), rows, D, int(gelu), L.stream())
         return dx
@@ -781,7 +743,7 @@ def tcv_attn_bwd(film, u, vk, mem, lnc_g, lnc_b, c, lse, dc, dlnc_g, dlnc_b, S, 
     vis_cond_norm's gradients into dlnc_g / dlnc_b (fp32 [d])."""
     d = vk.shape[1]
     du, dfilm, dvk, dmem = torch.empty_like(u), torch.empty_like(film), torch.empty_like(vk), torch.empty_like(mem)
-    ws = _workspace(u.device, S * Lq * (2 * d + heads))
+    ws = scratch.get("slabs", u.device, scratch.floats("dig_tcv_attn_bwd_workspace_bytes", S, Lq, heads, d), floor=SLAB_FLOOR)
     L.call("dig_tcv_attn_bwd", L.ptr(film), L.ptr(u), L.ptr(vk), L.ptr(mem), L.ptr(lnc_g), L.ptr(lnc_b), cf(eps), L.ptr(c), L.ptr(lse), L.ptr(dc),
            L.ptr(du), L.ptr(dfilm), L.ptr(dvk), L.ptr(dmem), L.ptr(dlnc_g), L.ptr(dlnc_b), L.ptr(ws), S, Lq, N, heads, d, 1,
            ctypes.byref(drop) if drop is not None else None, L.stream())
@@ -881,7 +843,7 @@ def patch_embed_bwd_mfma(dy, img, mask_u8, dW, dbias, dmask_token, D, gh, gw):
     P = torch.empty((n_tok, 64), device=img.device, dtype=BF16)
     L.call("dig_patchify_bf16", L.ptr(img), L.ptr(mask_u8), L.ptr(P), img.shape[0], gh, gw, L.stream())
     wgrad(dy, P, dW, D, 48, n_tok)
-    ws = _workspace2(dy.device, 2 * 1024 * D)
+    ws = scratch.get("partials", dy.device, 2 * scratch.floats("dig_colsum_workspace_bytes", n_tok, D), floor=PARTIAL_FLOOR)
     L.call("dig_colsum_masked", L.ptr(dy), L.ptr(mask_u8), L.ptr(dbias), L.ptr(dmask_token), L.ptr(ws), n_tok, D, L.stream())
 
 
@@ -962,22 +924,10 @@ def mim_target(img, idx, M, gh, gw, normalize=False):
     return tgt
 
 
-_loss_ws = {}
-
-
-def _loss_workspace(dev, tag, numel):
-    """Zero-initialised fp32 scratch of the deterministic loss reductions (the kernels leave its ticket word at zero)."""
-    key = (str(dev), tag, _stream_id(dev) if dev.type == "cuda" else 0)
-    w = _loss_ws.get(key)
-    if w is None or w.numel() < numel:
-        w = _loss_ws[key] = torch.zeros(max(numel, 4096), device=dev, dtype=F32)
-    return w
-
-
 def mse_fwd_bwd(pred, ld_pred, target, M, C, gscale, loss, dpred, ld_dpred):
     """loss += mean((pred - target)^2) with the block sums added in block order (no floating-point atomics: the logged value is bit-stable)."""
-    L.call("dig_mse_fwd_bwd_ws", L.ptr(pred), ld_pred, L.ptr(target), M, C, cf(gscale), L.ptr(loss), L.ptr(dpred), ld_dpred,
-           L.ptr(_loss_workspace(pred.device, "mse", 257)), L.stream())
+    ws = scratch.get("mse", pred.device, scratch.floats("dig_mse_workspace_bytes"), zero=True, floor=LOSS_FLOOR)     # (its ticket word stays zero)
+    L.call("dig_mse_fwd_bwd_ws", L.ptr(pred), ld_pred, L.ptr(target), M, C, cf(gscale), L.ptr(loss), L.ptr(dpred), ld_dpred, L.ptr(ws), L.stream())
 
 
 def add_bf16(a, b, out):
@@ -988,13 +938,9 @@ def gelu_bwd(dact, pre, out):
     L.call("dig_gelu_bwd", L.ptr(dact), L.ptr(pre), L.ptr(out), cll(dact.numel()), L.stream())
 
 
-def _bn_ws_floats(rows, C):
-    return L.query("dig_bn_stats_workspace_bytes", int(rows), int(C)) // 4
-
-
 def bn_stats(x, sums):
     """sums[2,C] = (sum_r x, sum_r x^2) -- overwritten, deterministic."""
-    ws = _workspace2(x.device, _bn_ws_floats(x.shape[0], x.shape[1]))
+    ws = scratch.get("partials", x.device, scratch.floats("dig_bn_stats_workspace_bytes", x.shape[0], x.shape[1]), floor=PARTIAL_FLOOR)
     L.call("dig_bn_stats", L.ptr(x), L.ptr(sums), L.ptr(ws), x.shape[0], x.shape[1], L.stream())
 
 
@@ -1045,7 +991,7 @@ def bn_update_running(sums, n_total, momentum, rm, rv):
 def bn_bwd_stats(dy, x, mean, rstd, gamma, beta, relu, sums, dbeta=None, dgamma=None):
     """sums[0] = sum g, sums[1] = sum g * x_hat over this rank's rows; dbeta / dgamma (both or neither): the layer's affine gradients,
     += those LOCAL sums in the same launch."""
-    ws = _workspace2(x.device, _bn_ws_floats(x.shape[0], x.shape[1]))
+    ws = scratch.get("partials", x.device, scratch.floats("dig_bn_stats_workspace_bytes", x.shape[0], x.shape[1]), floor=PARTIAL_FLOOR)
     L.call("dig_bn_bwd_stats_acc", L.ptr(dy), L.ptr(x), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(beta), int(relu), L.ptr(sums),
            L.ptr(dbeta), L.ptr(dgamma), L.ptr(ws), x.shape[0], x.shape[1], L.stream())
 
@@ -1087,7 +1033,7 @@ def sgemm(A, B, C, I, J, R, trans_b, alpha):
         # R-slices of 128 make it one round of 512 workgroups; the slab sum is a 2 MB pass (50.8 -> ~25 us per launch, twice per step)
         sp = R // 128
     if sp > 1:
-        ws = _workspace(A.device, sp * I * J)
+        ws = scratch.get("slabs", A.device, sp * I * J, floor=SLAB_FLOOR)
         L.call("dig_sgemm", L.ptr(A), L.ptr(B), L.ptr(ws), I, J, R, A.stride(0), B.stride(0), J, int(trans_b), cf(alpha), sp, L.stream())
         L.call("dig_reduce_partials", L.ptr(ws), sp, cll(I * J), L.ptr(C), 0, L.stream())
     else:
@@ -1097,8 +1043,8 @@ def sgemm(A, B, C, I, J, R, trans_b, alpha):
 def ce_rows(logits, label_offset, gscale, out3):
     """The rows' loss / hit counts are added in row order (no floating-point atomics)."""
     n = logits.shape[0]
-    L.call("dig_ce_rows_ws", L.ptr(logits), n, logits.shape[1], label_offset, cf(gscale), L.ptr(out3),
-           L.ptr(_loss_workspace(logits.device, "ce", 1 + 3 * n)), L.stream())
+    ws = scratch.get("ce", logits.device, scratch.floats("dig_ce_rows_workspace_bytes", n), zero=True, floor=LOSS_FLOOR)     # (its ticket word stays zero)
+    L.call("dig_ce_rows_ws", L.ptr(logits), n, logits.shape[1], label_offset, cf(gscale), L.ptr(out3), L.ptr(ws), L.stream())
 
 
 def infonce_finish(stats, loss_scale, acc_scale):

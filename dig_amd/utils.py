@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import ops, scratch
 
 
 # ------------------------------------------------------------------------------------------------ schedules
@@ -86,10 +86,12 @@ def get_grad_norm_(parameters=None, norm_type: float = 2.0, model=None):
         raise NotImplementedError("only the L2 norm is used by the pre-training recipe")
     g = model.flat_grads
     ws = getattr(model, "_norm_ws", None)
-    if ws is None or ws.device != g.device:
-        ws = model._norm_ws = torch.empty(1024 + 1, device=g.device, dtype=torch.float32)
-    ops.sumsq(g, ws[:1024], ws[1024:])
-    return ws[1024].sqrt()
+    need = scratch.floats("dig_sumsq_workspace_bytes", g.numel()) + 1
+    if ws is None or ws.device != g.device or ws.numel() != need:
+        # dig_sumsq's partial sums, then its one output float (the model's own: the optimizer step reads it as its gate long after)
+        ws = model._norm_ws = torch.empty(need, device=g.device, dtype=torch.float32)
+    ops.sumsq(g, ws[:-1], ws[-1:])
+    return ws[-1].sqrt()
 
 
 class NativeScalerWithGradNormCount:
@@ -113,9 +115,9 @@ class NativeScalerWithGradNormCount:
         # the squared norm doubles as the update's gate: after a non-finite loss the optimizer launch changes nothing (GradScaler's
         # inf-skip, utils/utils.py:498-504), so the weights a caller sees after the late `sys.exit(1)` of the engine are the last good ones
         if adamw_dev_scalars is not None:           # captured step (dig_amd/step_graph.py): schedule values come from device memory
-            optimizer.step(grad_scale=scale, finite_gate=model._norm_ws[1024:], dev_scalars=adamw_dev_scalars)
+            optimizer.step(grad_scale=scale, finite_gate=model._norm_ws[-1:], dev_scalars=adamw_dev_scalars)
         else:
-            optimizer.step(grad_scale=scale, finite_gate=model._norm_ws[1024:])
+            optimizer.step(grad_scale=scale, finite_gate=model._norm_ws[-1:])
         return norm
 
     def state_dict(self):

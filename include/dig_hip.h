@@ -355,8 +355,11 @@ int dig_sgemm(const float* A, const float* B, float* C, int I, int J, int R, int
 int dig_ce_rows(float* logits, int n, int m, int label_offset, float gscale, float* out3, hipStream_t stream);
 /* The two loss reductions with a caller-owned workspace instead of floating-point atomics: the partial sums (one per workgroup / row) are
  * added in a fixed order by the last workgroup to finish, so the logged loss values are bit-reproducible (gradients never depended on
- * them).  workspace: 257 floats (dig_mse_fwd_bwd_ws) / 1 + 3 n floats (dig_ce_rows_ws), ZERO before the first use; a launch leaves
- * workspace[0] at zero again, so launches on one stream can share it.  NULL workspace = the atomic forms above. */
+ * them).  workspace: 257 floats (dig_mse_fwd_bwd_ws, dig_mse_workspace_bytes) / 1 + 3 n floats (dig_ce_rows_ws,
+ * dig_ce_rows_workspace_bytes; 0 for n < 0), ZERO before the first use; a launch leaves workspace[0] at zero again, so launches on one
+ * stream can share it.  NULL workspace = the atomic forms above. */
+long long dig_mse_workspace_bytes(void);
+long long dig_ce_rows_workspace_bytes(int n);
 int dig_mse_fwd_bwd_ws(const float* pred, int ld_pred, const float* target, int M, int C, float gscale, float* loss, void* dpred,
                        int ld_dpred, float* workspace, hipStream_t stream);
 int dig_ce_rows_ws(float* logits, int n, int m, int label_offset, float gscale, float* out3, float* workspace, hipStream_t stream);
@@ -807,7 +810,8 @@ int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ldk, const vo
  * pointers 16-byte aligned (-2).
  * dig_tcv_attn_bwd (slots_per_mem must be 1): from the forward's inputs, c, lse and dc [R, heads * d] -> du [R, heads * d], dfilm [R, 2d]
  * (the tanh derivative applied), dvk [M * N, d], dmem [M * N, d] (the residual term only: the path through vk is the caller's GEMM /
- * LayerNorm backward), all bf16 and overwritten; dlnc_g, dlnc_b [d] fp32, ACCUMULATED into.  workspace: R * (2d + heads) floats.
+ * LayerNorm backward), all bf16 and overwritten; dlnc_g, dlnc_b [d] fp32, ACCUMULATED into.  workspace: R * (2d + heads) floats
+ * (dig_tcv_attn_bwd_workspace_bytes, a 64-bit product; 0 when an argument is not positive, Lq > 32, d > 512 or heads > d).
  * delta = dc . c is re-summed over the keys in fp32 (the bf16 c is accepted and checked, not read: dlogit sums to zero over the keys only for
  * an exact delta, and du = sum_k dlogit cond[k] keeps none of what the rows of cond share -- a rounding error of c would not cancel there).
  * Deterministic (every sum has a fixed order, no floating-point atomics); a query row's c / lse / wmean / du / dfilm do not depend on
@@ -815,6 +819,7 @@ int dig_seq_attn_bwd_hd(const void* q, int ldq, const void* k, int ldk, const vo
 int dig_tcv_attn_fwd(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, float eps,
                      void* c, float* lse, float* wmean, int S, int Lq, int N, int heads, int d, int slots_per_mem,
                      const dig_dropout_t* drop, hipStream_t stream);
+long long dig_tcv_attn_bwd_workspace_bytes(int S, int Lq, int heads, int d);
 int dig_tcv_attn_bwd(const void* film, const void* u, const void* vk, const void* mem, const float* lnc_g, const float* lnc_b, float eps,
                      const void* c, const float* lse, const void* dc, void* du, void* dfilm, void* dvk, void* dmem, float* dlnc_g,
                      float* dlnc_b, float* workspace, int S, int Lq, int N, int heads, int d, int slots_per_mem,

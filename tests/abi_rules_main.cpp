@@ -229,7 +229,9 @@ static void the_rest() {
   if (R::gemm_effective_splits(65536, 18) != 18 || R::gemm_effective_splits(716, 8) != 6 || R::gemm_effective_splits(IMAX, 1) != 1 ||
       R::layernorm_bwd_parts(IMAX) != 1024 || R::layernorm_bwd_parts(1) != 1 || R::mlp_chain_ln_parts(IMAX) != 16777216 ||
       R::wgrad_group_effective_splits(IMAX - 63, IMAX) != 33554431 || R::wgrad_group_tiles(IMAX - 127, 256, 2, 1) != 16777215 ||
-      R::ksize_for(32, 32) != 5 || R::ksize_for(10048, 128) != 315 || R::ksize_for(10049, 128) != 317) {
+      R::ksize_for(32, 32) != 5 || R::ksize_for(10048, 128) != 315 || R::ksize_for(10049, 128) != 317 ||
+      R::mse_workspace_bytes() != 1028 || R::ce_rows_workspace_bytes(IMAX) != 4 + 12LL * IMAX || R::ce_rows_workspace_bytes(0) != 4 ||
+      R::tcv_attn_bwd_workspace_bytes(IMAX, 32, 8, 512) != 4LL * IMAX * 32 * 1032 || R::tcv_attn_bwd_workspace_bytes(IMAX, IMAX, IMAX, IMAX) != 0) {
     ++failures;
     std::printf("a query disagrees with its documented value\n");
   }

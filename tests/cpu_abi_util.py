@@ -19,28 +19,21 @@ def build():
 
 @contextlib.contextmanager
 def cpu_abi_backend():
-    from dig_amd import _lib, ops
+    from dig_amd import _lib, scratch
     lib = ctypes.CDLL(build())
-    saved = (_lib._lib, dict(_lib._fns), _lib.stream, ops._workspace, ops._workspace2)
-    scratch = {}
-
-    def workspace(tag):
-        def get(dev, numel):
-            w = scratch.get(tag)
-            if w is None or w.numel() < numel:
-                w = scratch[tag] = torch.empty(max(numel, 1 << 20), dtype=torch.float32)
-            return w
-        return get
+    saved = (_lib._lib, dict(_lib._fns), _lib.stream, _lib.stream_key)
+    dev = torch.device("cpu")
     _lib._lib = lib
     _lib._fns.clear()
     _lib.stream = lambda: None                      # the CPU build ignores its stream argument
-    ops._workspace, ops._workspace2 = workspace("a"), workspace("b")
+    _lib.stream_key = lambda dev: 0
     try:
-        yield torch.device("cpu")
+        yield dev
     finally:
-        _lib._lib, _lib.stream, ops._workspace, ops._workspace2 = saved[0], saved[2], saved[3], saved[4]
+        _lib._lib, _lib.stream, _lib.stream_key = saved[0], saved[2], saved[3]
         _lib._fns.clear()
         _lib._fns.update(saved[1])
+        scratch.drop(dev)                           # no CPU tensor outlives the fixture
 
 
 def exported():

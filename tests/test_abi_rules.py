@@ -68,7 +68,8 @@ def test_the_shared_queries_are_defined_once():
     names = re.findall(r'^extern "C" (?:int|long long) (dig_\w+)\(', inc, re.M)
     for q in ("dig_gemm_effective_splits", "dig_wgrad_group_effective_splits", "dig_layernorm_bwd_parts", "dig_layernorm_bwd_workspace_bytes",
               "dig_bn_fused_supported", "dig_attn_block_supported", "dig_mlp_chain_supported", "dig_mlp_chain_ln_parts",
-              "dig_lexicon_search_workspace_bytes", "dig_ctc_lexicon_workspace_bytes"):
+              "dig_lexicon_search_workspace_bytes", "dig_ctc_lexicon_workspace_bytes", "dig_sumsq_workspace_bytes", "dig_mse_workspace_bytes",
+              "dig_ce_rows_workspace_bytes", "dig_tcv_attn_bwd_workspace_bytes"):
         assert q in names, q
     units = glob.glob(os.path.join(ROOT, "dig_amd", "csrc", "*.hip")) + glob.glob(os.path.join(ROOT, "cpu_abi", "*.cpp"))
     for u in units:
@@ -242,6 +243,22 @@ def test_table_entry_points_refuse_bad_entries(abi_dev):
     _refused(ALIGN, "dig_wgrad_group", probs, 1, None, 0, R, 1, P(wmap), 8, _off(slabs, 4), None, 1, 2, 1, L.stream())
     _refused(ALIGN, "dig_wgrad_group", None, 0, probs, 1, R, 1, None, 8, None, _off(slabs, 8), 1, 2, 1, L.stream())
     assert _untouched(a, b, ta, tb, A, B, out, slabs)
+
+
+def test_the_loss_and_attention_backward_workspace_queries(abi_dev):
+    """dig_mse_workspace_bytes, dig_ce_rows_workspace_bytes, dig_tcv_attn_bwd_workspace_bytes against the sizes include/dig_hip.h states in
+    words: 257 floats; 1 + 3 n floats (one float at n = 0, nothing for n < 0); S Lq (2 d + heads) floats as a 64-bit product (nothing when an
+    argument is not positive)."""
+    q = _L().query
+    assert q("dig_mse_workspace_bytes") == 257 * 4
+    for n in (0, 1, 7, 4096, 2 ** 31 - 1):
+        assert q("dig_ce_rows_workspace_bytes", n) == (1 + 3 * n) * 4, n
+    assert q("dig_ce_rows_workspace_bytes", -1) == 0
+    for S, Lq, heads, d in ((1, 1, 2, 128), (3, 5, 2, 128), (2, 25, 8, 512), (65535, 32, 8, 512), (2 ** 31 - 1, 32, 8, 512)):
+        assert q("dig_tcv_attn_bwd_workspace_bytes", S, Lq, heads, d) == S * Lq * (2 * d + heads) * 4, (S, Lq, heads, d)
+    assert 65535 * 32 * (2 * 512 + 8) * 4 > 2 ** 32 and 65535 * 32 * (2 * 512 + 8) > 2 ** 31         # neither the bytes nor the floats fit an int
+    for bad in ((0, 5, 2, 128), (3, 0, 2, 128), (3, 5, 0, 128), (3, 5, 2, 0), (-1, 5, 2, 128), (3, 33, 2, 128), (3, 5, 8, 513), (3, 5, 129, 128)):
+        assert q("dig_tcv_attn_bwd_workspace_bytes", *bad) == 0, bad
 
 
 # ------------------------------------------------------------------------------------------------ 3. magnitude rules, stand-alone

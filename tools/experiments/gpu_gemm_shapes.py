@@ -38,7 +38,7 @@ def wgrad(name, I, J, bks=(32, 64, 244, 264, 242), splits=(8, 16, 24, 32, 40, 48
     for bk in bks:
         for sp0 in splits:
             sp = ops.L.lib().dig_gemm_effective_splits(R, sp0)
-            ws = ops._workspace(dev, sp * I * J)
+            ws = ops.scratch.get("slabs", dev, sp * I * J, floor=ops.SLAB_FLOOR)
             tg = bench(lambda: ops.gemm(dy, x, I, J, R, ta=True, tb=True, out=ws, out_kind=ops.OUT_F32_PARTIAL, splits=sp, ldc=J, bk=bk))
             t = bench(lambda: (ops.gemm(dy, x, I, J, R, ta=True, tb=True, out=ws, out_kind=ops.OUT_F32_PARTIAL, splits=sp, ldc=J, bk=bk),
                                ops.L.call("dig_reduce_partials", ops.L.ptr(ws), sp, ops.cll(I * J), ops.L.ptr(dw), 1, ops.L.stream())))
